@@ -10,14 +10,23 @@ collective inside a step); value = pixels all ranks produced / max-over-ranks
 time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task
-description), including
+Prints ONE JSON line on rank 0, including
   roofline     - algorithmic bytes per launch / mean kernel time measured with
                  HIP events on the kernel's own stream, against 8 TB/s HBM
+and, with --full only (work of its own after the timed steps, not needed by `value`),
   cpu_baseline - the CPU oracle (a port of the reference path, NOT envutil's
                  SIMD binary) timed on this box's host cores on a band of rows
-                 of the same frame.
+                 of the same frame, and those rows compared bit for bit with the GPU's
+  host_boundary.render_to_host_ms / d2h_reference - the frame rendered into a host
+                 buffer, and plain device -> host copies of it.
+
+--dump-outputs DIR writes the frame the last timed step produced (rank 0, after any
+gather) as float32 .npy: DIR/output.npy (rows, cols, channels) when it fits in
+DUMP_BYTES, else DIR/output_sample.npy (n, channels), the pixels at a fixed seeded
+sample of flat pixel indices. The inputs are seeded, so two builds run with the same
+arguments can be compared file for file.
 """
 import argparse
 import ctypes as C
@@ -59,6 +68,8 @@ WORKLOAD_TEXT = {
 }
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec
 BAND_ROWS = 64          # multi-GPU tiling unit (eu_target.band_rows): two XCD units of the kernels
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this much of the frame is written
+DUMP_SEED = 1234
 
 
 class _DevBuf:
@@ -83,6 +94,22 @@ def synth_on_device(torch, dev, w, h, nch):
     return img
 
 
+def dump_outputs(path, frame):
+    """frame (rows, cols, channels) f32 torch tensor -> path/output.npy, or, when larger than
+    DUMP_BYTES, path/output_sample.npy: the pixels at sorted flat indices drawn with DUMP_SEED
+    (the same indices for every run of a workload)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    h, w, nch = frame.shape
+    if frame.numel() * 4 <= DUMP_BYTES:
+        np.save(os.path.join(path, "output.npy"), frame.cpu().numpy())
+        return
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, h * w, DUMP_BYTES // (4 * nch)))
+    sample = frame.reshape(h * w, nch)[torch.from_numpy(idx).to(frame.device)]
+    np.save(os.path.join(path, "output_sample.npy"), sample.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -93,7 +120,13 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--probe-stages", action="store_true",
                     help="diagnostic: also time the kernel stopped after the ray / coordinate stage")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and the host boundary (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the frame of the last timed step under DIR as .npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -304,15 +337,18 @@ def main():
             same = rc == 0 and torch.equal(whole.cpu().view(torch.int32), frame.view(torch.int32))
             print(f"REHEARSAL world {world}: gathered frame identical to a single launch: {same}", file=sys.stderr)
             del whole
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, frame)
         del frame
-
+    elif a.dump_outputs:
+        dump_outputs(a.dump_outputs, out)
 
     # ---- the boundary with HOST buffers (never `value`): pixels in, pixels out ----
     # load = H2D of the source + prefilter/brace on the device; render_to_host =
     # kernel + D2H of the frame into pageable memory (second call: pages touched)
     host_ms = None
     pcie = None
-    if world == 1 and nsrcs == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and nsrcs == 1 and not a.no_cpu_baseline:
         hbuf = np.empty((r1 - r0, tw, nch), np.float32)
         ea.render(args, src, nch, r0, r1, out=hbuf)
         th0 = time.perf_counter()
@@ -441,7 +477,7 @@ def main():
     }
 
     # ---- CPU baseline: the oracle (a port) on a band of rows, rank 0, N=1 ----
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import euo
         import jobs

@@ -1,17 +1,48 @@
 """ctypes bindings of oracle/_ref/libref_zimt.so - the reference's own zimt
-headers compiled in place from /root/reference. Only present in the build
-container; tests that need it are marked 'ref' and skip elsewhere."""
+headers compiled in place from a reference checkout (oracle/Makefile, REF). Only
+present where that checkout is; tests marked 'ref' compare with it live there, and
+elsewhere with the SHA-256 of its results recorded in tests/golden/ref_digests.json
+(same())."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "_ref", "libref_zimt.so")
+DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")
+RECORDING = False       # tests/golden/make_ref_digests.py: collect into RECORDED, skip the check against DIGESTS
+RECORDED = {}
 
 
 def available():
     return os.path.exists(LIB)
+
+
+def digest(a):
+    """SHA-256 of an array's float32 bits and shape"""
+    a = np.ascontiguousarray(a, np.float32)
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+_digests = None
+
+
+def same(key, ours, reference):
+    """True when `ours` is bit for bit the reference's result: `reference()` (a call into the library) where
+    the library is built - and then its digest must be the one recorded under `key` - else the recorded digest"""
+    global _digests
+    if _digests is None:
+        _digests = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
+    if not available():
+        return digest(ours) == _digests[key]
+    ref = np.ascontiguousarray(reference(), np.float32)
+    RECORDED[key] = digest(ref)
+    assert RECORDING or _digests.get(key) == RECORDED[key], f"tests/golden/ref_digests.json is stale at {key}"
+    ours = np.ascontiguousarray(ours, np.float32)
+    return ours.shape == ref.shape and (ours.view(np.uint32) == ref.view(np.uint32)).all()
 
 
 _lib = None

@@ -1,8 +1,8 @@
 """--mask_for's functors pinned (round 3): the oracle's euo_mask_paint - what oracle/eu_oracle.c's mount_eval puts
 in the place of the interpolated pixel - against the REFERENCE's own masking_t and alpha_masking_t
 (masking.h:70-135; the header includes nothing but zimt, so it compiles in place into oracle/_ref).
-Live where /root/reference exists, and against tests/golden/mask_golden.npz (generated from the same library)
-everywhere. The HIP path is compared with the oracle in tests/test_mask_for.py."""
+Live where that library is built (elsewhere against the digests of its results, refz.same), and against
+tests/golden/mask_golden.npz (generated from the same library) everywhere. The HIP path is compared with the oracle in tests/test_mask_for.py."""
 import ctypes as C
 import os
 
@@ -52,14 +52,16 @@ def test_fixture(paint):
         assert (ref == paint).all()
 
 
-@pytest.mark.skipif(not refz.available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("paint", [0.0, 1.0])
 def test_live(paint):
     for name, core, deg, crd in mask_cases.cases():
-        r = refz.RefSpline(core, deg, 3, 3)
-        r.prefilter(deg)
-        assert (bits(oracle_alpha_masking(core, deg, crd, paint)) == bits(refz.alpha_masking(r, paint, crd))).all(), name
+        r = refz.RefSpline(core, deg, 3, 3) if refz.available() else None
+        if r:
+            r.prefilter(deg)
+        assert refz.same(f"alpha_masking_{name}_{int(paint)}", oracle_alpha_masking(core, deg, crd, paint),
+                         lambda: refz.alpha_masking(r, paint, crd)), name
     rng = np.random.default_rng(7)
     for nch in (1, 3):
         px = rng.random((53, nch), dtype=np.float32)
-        assert (bits(oracle_mask(px, 2 if paint else 1)) == bits(refz.masking(nch, paint, 53))).all()
+        assert refz.same(f"masking_{nch}_{int(paint)}", oracle_mask(px, 2 if paint else 1),
+                         lambda: refz.masking(nch, paint, 53))

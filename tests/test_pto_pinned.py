@@ -1,8 +1,8 @@
 """The product's PTO reader (include/eu_frontend.hpp: pto_script) against the REFERENCE's own parser
 (pto.h:72-180, pto_parser_type), line group by line group and field by field.
 
-* live (only where /root/reference exists): pto.h compiled in place into oracle/_ref/libref_zimt.so
-  (ref_pto_parse), both parsers on every script of tests/pto_cases.py;
+* live: pto.h compiled in place into oracle/_ref/libref_zimt.so (ref_pto_parse), both parsers on every
+  script of tests/pto_cases.py, output for output (where that library is not built: against the fixture);
 * fixture: tests/golden/pto_golden.json holds the reference parser's output for the same scripts (generated
   by tests/golden/make_pto_golden.py), so the comparison also runs where the reference is absent."""
 import ctypes as C
@@ -60,10 +60,11 @@ def test_fixture(dump, name):
         assert mine[head] == theirs[head], head
 
 
-@pytest.mark.skipif(not refz.available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("name", sorted(pto_cases.CASES))
 def test_live(dump, name):
     text = pto_cases.CASES[name]
-    assert dump(text) == ref_parse(text)
-    # and the fixture is what the reference says today
-    assert json.load(open(GOLDEN))[name] == ref_parse(text)
+    golden = json.load(open(GOLDEN))[name]
+    if refz.available():
+        # the fixture is what the reference says today
+        assert golden == ref_parse(text)
+    assert dump(text) == golden
