@@ -84,42 +84,20 @@ __global__ __launch_bounds__(256) EU2_OCC void eu_render2_kernel(const eu_render
 }
 
 // ---------------------------------------------------------------------------
-// LDS-staged variant (no twining): 32x16 output tiles, still two pixels per
-// lane (rows y and y+8 of one column), so that the tile's source footprint is a
-// compact box for ANY orientation of the mapping (polar cube faces, rotated
-// targets). The box is copied into LDS once with coalesced row reads - every
-// source texel passes the texture addresser once per tile instead of once per
-// tap - and the (d+1)^2 taps are 16-byte LDS reads. Tiles whose box exceeds the
-// LDS budget (pole of a lat/lon source, the +-180 degree seam, strong
-// minification) gather from global memory like eu_render2_kernel; the choice is
-// per workgroup.
+// 32x16 output tiles (no twining), still two pixels per lane (rows y and y+8 of one
+// column): the hybrid's tile layout (eu_render_params::layout == 2). The four lanes the
+// memory pipe serves together (a quad) form a 2x2 pixel block, which touches about the
+// same number of cache lines for every orientation of the mapping (polar cube faces,
+// rotated targets); a wave covers 32x2 pixels.
 // ---------------------------------------------------------------------------
 
 #define EU3_TW 32
 #define EU3_TH 16
-#define EU3_LDS_BYTES (36 * 1024)
 
-__device__ __forceinline__ int eu_wmin(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int eu_wmax(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
-template <int NCH, int DEG, int PRJ, bool STAGE>
+template <int NCH, int DEG, int PRJ>
 __global__ __launch_bounds__(256, 4) void eu_render3_kernel(const eu_render_params p)
 {
-  constexpr int TEX = NCH == 3 ? 4 : NCH;              // floats per LDS texel
-  constexpr int CAP = STAGE ? EU3_LDS_BYTES / (TEX * 4) : 4;   // texels
-  __shared__ __attribute__((aligned(16))) float tile[CAP * TEX];
   __shared__ __attribute__((aligned(16))) float atab[EU_ATAN_TAB_FLOATS];
-  __shared__ int bbw[4][4];
   if constexpr (PRJ != EU_CUBEMAP) {
     if (threadIdx.x < EU_ATAN_TAB_ENTRIES) eu_atan_tab_entry(threadIdx.x, atab + 8 * threadIdx.x);
   }
@@ -127,19 +105,9 @@ __global__ __launch_bounds__(256, 4) void eu_render3_kernel(const eu_render_para
   if (b < 0) return;                                   // whole workgroup
   __syncthreads();
   const int tile_y = b / p.tiles_x, tile_x = b - tile_y * p.tiles_x;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // lane -> pixel inside the 32x16 tile. Staged: rows of 32. Direct gathers: the
-  // four lanes the memory pipe serves together (a quad) form a 2x2 pixel block,
-  // which touches about the same number of cache lines for every orientation of
-  // the mapping; a wave covers 32x2 pixels either way.
-  int lx, ly;
-  if constexpr (STAGE) { lx = threadIdx.x & 31; ly = threadIdx.x >> 5; }
-  else {
-    const int l = threadIdx.x & 63;
-    lx = ((l >> 2) << 1) | (l & 1);
-    ly = ((threadIdx.x >> 6) << 1) | ((l >> 1) & 1);
-  }
+  const int l = threadIdx.x & 63;
+  const int lx = ((l >> 2) << 1) | (l & 1);
+  const int ly = ((threadIdx.x >> 6) << 1) | ((l >> 1) & 1);
   const int x = tile_x * EU3_TW + lx;
   const int ya = p.row_begin + tile_y * EU3_TH + ly, yb = ya + 8;
   const bool la = x < p.width && ya < p.row_end, lb = x < p.width && yb < p.row_end;
@@ -186,29 +154,6 @@ __global__ __launch_bounds__(256, 4) void eu_render3_kernel(const eu_render_para
   const int ixa = hit.x ? (int)fx.x : DEG / 2, iya = hit.x ? (int)fy.x : DEG / 2;
   const int ixb = hit.y ? (int)fx.y : DEG / 2, iyb = hit.y ? (int)fy.y : DEG / 2;
 
-  // bounding box of the base positions of all hitting pixels of the tile
-  bool fits = false;
-  int mnx = INT_MAX, mny = INT_MAX, mxx = INT_MIN, mxy = INT_MIN;
-  int bx0 = 0, by0 = 0;
-  long long bw = 0, bh = 0;
-  if constexpr (STAGE) {
-  if (hit.x) { mnx = ixa; mxx = ixa; mny = iya; mxy = iya; }
-  if (hit.y) { mnx = min(mnx, ixb); mxx = max(mxx, ixb); mny = min(mny, iyb); mxy = max(mxy, iyb); }
-  mnx = eu_wmin(mnx); mny = eu_wmin(mny); mxx = eu_wmax(mxx); mxy = eu_wmax(mxy);
-  if (lane == 0) { bbw[wave][0] = mnx; bbw[wave][1] = mny; bbw[wave][2] = mxx; bbw[wave][3] = mxy; }
-  __syncthreads();
-  mnx = min(min(bbw[0][0], bbw[1][0]), min(bbw[2][0], bbw[3][0]));
-  mny = min(min(bbw[0][1], bbw[1][1]), min(bbw[2][1], bbw[3][1]));
-  mxx = max(max(bbw[0][2], bbw[1][2]), max(bbw[2][2], bbw[3][2]));
-  mxy = max(max(bbw[0][3], bbw[1][3]), max(bbw[2][3], bbw[3][3]));
-  mnx = __builtin_amdgcn_readfirstlane(mnx); mny = __builtin_amdgcn_readfirstlane(mny);
-  mxx = __builtin_amdgcn_readfirstlane(mxx); mxy = __builtin_amdgcn_readfirstlane(mxy);
-  const bool any = mnx != INT_MAX;
-  bx0 = mnx - DEG / 2; by0 = mny - DEG / 2;
-  bw = (long long)mxx - mnx + DEG + 1; bh = (long long)mxy - mny + DEG + 1;
-  fits = any && bw * bh <= CAP;
-  }
-
   constexpr int order = DEG + 1;
   eu_f2 wx[order], wy[order];
   if constexpr (DEG >= 2) {
@@ -223,40 +168,10 @@ __global__ __launch_bounds__(256, 4) void eu_render3_kernel(const eu_render_para
   }
 
   float pxa[NCH], pxb[NCH];
-  if (fits) {
-    const int ibw = (int)bw, ibh = (int)bh;
-    // stage the box: wave w copies rows w, w+4, ...; lanes run along x
-    for (int rr = wave; rr < ibh; rr += 4) {
-      const float *g = s.base + (long long)(by0 + rr) * s.es1 + (long long)bx0 * NCH;
-      for (int c = lane; c < ibw; c += 64) {
-        const float *q = g + (long long)c * NCH;
-        float *d = tile + (rr * ibw + c) * TEX;
-        if constexpr (NCH == 3) {
-          float v0 = q[0], v1 = q[1], v2 = q[2];
-          *reinterpret_cast<float4 *>(d) = make_float4(v0, v1, v2, 0.0f);
-        } else if constexpr (NCH == 4) {
-          *reinterpret_cast<float4 *>(d) = *reinterpret_cast<const float4 *>(q);
-        } else if constexpr (NCH == 2) {
-          *reinterpret_cast<float2 *>(d) = *reinterpret_cast<const float2 *>(q);
-        } else {
-          d[0] = q[0];
-        }
-      }
-    }
-    __syncthreads();
-    const int pitch = ibw * TEX;
-    // lanes without a hit read the box origin (their result is discarded)
-    const int oa = hit.x ? ((iya - mny) * ibw + (ixa - mnx)) * TEX : 0;
-    const int ob = hit.y ? ((iyb - mny) * ibw + (ixb - mnx)) * TEX : 0;
-    eu_lptr lt = (eu_lptr)tile;
-    eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + oa, pitch, wxa, wya, tx.x, ty.x, pxa);
-    eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + ob, pitch, wxb, wyb, tx.y, ty.y, pxb);
-  } else {
-    const float *pa = s.base + (long long)(ixa - DEG / 2) * NCH + (long long)(iya - DEG / 2) * s.es1;
-    const float *pb = s.base + (long long)(ixb - DEG / 2) * NCH + (long long)(iyb - DEG / 2) * s.es1;
-    eu_accumulate1<NCH, DEG>(pa, s.es1, wxa, wya, tx.x, ty.x, pxa);
-    eu_accumulate1<NCH, DEG>(pb, s.es1, wxb, wyb, tx.y, ty.y, pxb);
-  }
+  const float *pa = s.base + (long long)(ixa - DEG / 2) * NCH + (long long)(iya - DEG / 2) * s.es1;
+  const float *pb = s.base + (long long)(ixb - DEG / 2) * NCH + (long long)(iyb - DEG / 2) * s.es1;
+  eu_accumulate1<NCH, DEG>(pa, s.es1, wxa, wya, tx.x, ty.x, pxa);
+  eu_accumulate1<NCH, DEG>(pb, s.es1, wxb, wyb, tx.y, ty.y, pxb);
   constexpr int ncol = (NCH == 2 || NCH == 4) ? NCH - 1 : NCH;
   const bool bright = s.brighten != 1.0f;
   if (la) {
@@ -283,19 +198,13 @@ __global__ __launch_bounds__(256, 4) void eu_render3_kernel(const eu_render_para
 template <int NCH, int DEG, int PRJ>
 static int launch2_ndp(const eu_render_params &p, hipStream_t st)
 {
-  // EU_HIP_LDS: 0 = row-strip tiles (eu_render2_kernel), 1 = 32x16 tiles staged
-  // through LDS, 2 = 32x16 tiles with direct gathers
-  static const int env_lds = [] { const char *e = getenv("EU_HIP_LDS"); return e ? atoi(e) : 0; }();
-  const int use_lds = p.layout == 1 ? 0 : p.layout == 2 ? 2 : env_lds;
-  if (!p.twine && use_lds && p.norm_mode == EU_NORM_NONE) {
+  if (p.layout == 2 && !p.twine && p.norm_mode == EU_NORM_NONE) {
     eu_render_params q = p;
     q.tiles_x = (p.width + EU3_TW - 1) / EU3_TW;
     q.tiles_y = (p.row_end - p.row_begin + EU3_TH - 1) / EU3_TH;
-    static const int unit3 = [] { const char *e = getenv("EU_HIP_UNIT3"); return e ? atoi(e) : 2; }();
-    q.unit_rows = unit3 > 0 ? unit3 : 2;
+    q.unit_rows = 2;
     dim3 grid3((unsigned)eu_xcd_grid(q.tiles_x, q.tiles_y, q.unit_rows)), block3(256);
-    if (use_lds == 1) hipLaunchKernelGGL((eu_render3_kernel<NCH, DEG, PRJ, true>), grid3, block3, 0, st, q);
-    else hipLaunchKernelGGL((eu_render3_kernel<NCH, DEG, PRJ, false>), grid3, block3, 0, st, q);
+    hipLaunchKernelGGL((eu_render3_kernel<NCH, DEG, PRJ>), grid3, block3, 0, st, q);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, p.unit_rows)), block(256);
@@ -334,8 +243,7 @@ extern "C" int eu_launch_render2(const eu_render_params *pp, void *stream)
   if (p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return 1;
   if (p.src.prj != EU_SPHERICAL && p.src.prj != EU_CUBEMAP && p.src.prj != EU_BIATAN6) return 1;
   if (p.src.degree < 1 || p.src.degree > 3 || p.src.es0 != p.nch) return 1;
-  static const int unit_rows = [] { const char *e = getenv("EU_HIP_UNIT"); return e ? atoi(e) : EU2_UNIT_ROWS; }();
-  p.unit_rows = unit_rows > 0 ? unit_rows : EU2_UNIT_ROWS;
+  p.unit_rows = EU2_UNIT_ROWS;
   // rotated targets and twined jobs walk their units column by column (eu_xcd_tile): their source lines are
   // shared between vertically neighbouring tiles. EU_HIP_COLMAJOR=0 / 1 forces one walk (A/B runs).
   {

@@ -9,7 +9,8 @@
 //      rectilinear / cylindrical target of a lat/lon source: stepper.h hoists the same
 //      invariants per segment), that half of the chain - the longitude atan2f, the square
 //      root, the x gate, split and weights - comes from a per-column table that a small
-//      pre-pass kernel fills with the very same device functions,
+//      pre-pass kernel fills with the very same device functions (eu_render5_kernel, the
+//      form for lat/lon sources; eu_render4s_kernel serves cubemap and biatan6 sources),
 //   2. reduces the integer base positions to the tile's bounding box (DPP row shifts +
 //      row broadcasts, no LDS traffic, no barrier),
 //   3. copies the box from the braced container straight into LDS with LDS-DMA
@@ -54,9 +55,6 @@
 #define EU4_WL_DYN(x) (16 * (EU4_SHARDS + 1 + (x)))       // eu_render5_kernel: next batch of XCD x's second loop
 #define EU4_WL_ENTRIES (16 * (EU4_SHARDS + 16))          // entry k of list s at + k * EU4_SHARDS + s
 #define EU4_UNIT_ROWS 4    // tile rows per XCD unit (32 pixel rows)
-#ifndef EU4_ASM_TAPS
-#define EU4_ASM_TAPS 0      // 1: the tap reads issued by hand (eu4_taps2), 0: left to the compiler
-#endif
 #define EU4_COL_FLOATS 8   // per-column table: ix, tx, wx[0..3], sqrt(rx^2 + rz^2), longitude
 #define EU4_MAX_PLANS 16
 
@@ -90,102 +88,7 @@ __device__ __forceinline__ void eu4_box_reduce(int &mn0, int &mn1, int &mx0, int
 typedef __attribute__((address_space(3))) void *eu4_lds_void;
 typedef const __attribute__((address_space(1))) void *eu4_gbl_void;
 
-// The (d+1)^2 taps of BOTH pixels of a lane from the LDS image, window row by window row,
-// with the LDS reads issued by hand: the texels of row j + 1 are requested behind the wait for
-// row j and ahead of row j's sums, so one row of reads is in flight under one row of arithmetic
-// and at most two rows (64 registers) are live. Left to the compiler, all 32 reads of the two
-// pixels are hoisted to the top and what they return is spilled to scratch. Asm loads are
-// invisible to the compiler's s_waitcnt bookkeeping: every row has its own wait statement that
-// names the destinations (lgkmcnt(0): scalar loads may share the counter and return out of
-// order). The arithmetic is eu_accumulate1's: the reference's weighted sum in the reference's
-// order (zimt/eval.h:904-1059).
-typedef float eu4_f4 __attribute__((ext_vector_type(4)));
-
-// `dep`: a value of the arithmetic that has to be finished before these reads are issued (the
-// compiler otherwise sinks the sums below all the requests and keeps every row live)
-template <int ORDER>
-__device__ __forceinline__ void eu4_row_request(unsigned a, unsigned b, eu4_f4 *ta, eu4_f4 *tb, float &dep)
-{
-  if constexpr (ORDER == 4) {
-    asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:16\n\t"
-                 "ds_read_b128 %2, %8 offset:32\n\tds_read_b128 %3, %8 offset:48\n\t"
-                 "ds_read_b128 %4, %9\n\tds_read_b128 %5, %9 offset:16\n\t"
-                 "ds_read_b128 %6, %9 offset:32\n\tds_read_b128 %7, %9 offset:48"
-                 : "=&v"(ta[0]), "=&v"(ta[1]), "=&v"(ta[2]), "=&v"(ta[3]),
-                   "=&v"(tb[0]), "=&v"(tb[1]), "=&v"(tb[2]), "=&v"(tb[3])
-                 : "v"(a), "v"(b), "v"(dep) : "memory");
-  } else if constexpr (ORDER == 3) {
-    asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:16\n\tds_read_b128 %2, %6 offset:32\n\t"
-                 "ds_read_b128 %3, %7\n\tds_read_b128 %4, %7 offset:16\n\tds_read_b128 %5, %7 offset:32"
-                 : "=&v"(ta[0]), "=&v"(ta[1]), "=&v"(ta[2]), "=&v"(tb[0]), "=&v"(tb[1]), "=&v"(tb[2])
-                 : "v"(a), "v"(b), "v"(dep) : "memory");
-  } else {
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\t"
-                 "ds_read_b128 %2, %5\n\tds_read_b128 %3, %5 offset:16"
-                 : "=&v"(ta[0]), "=&v"(ta[1]), "=&v"(tb[0]), "=&v"(tb[1])
-                 : "v"(a), "v"(b), "v"(dep) : "memory");
-  }
-}
-
-template <int ORDER>
-__device__ __forceinline__ void eu4_row_wait(eu4_f4 *ta, eu4_f4 *tb)
-{
-  if constexpr (ORDER == 4)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ta[0]), "+v"(ta[1]), "+v"(ta[2]), "+v"(ta[3]),
-                                          "+v"(tb[0]), "+v"(tb[1]), "+v"(tb[2]), "+v"(tb[3]) :: "memory");
-  else if constexpr (ORDER == 3)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ta[0]), "+v"(ta[1]), "+v"(ta[2]),
-                                          "+v"(tb[0]), "+v"(tb[1]), "+v"(tb[2]) :: "memory");
-  else
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ta[0]), "+v"(ta[1]), "+v"(tb[0]), "+v"(tb[1]) :: "memory");
-}
-
-// a, b: LDS byte addresses of the two windows; pitch_bytes: bytes per LDS row
-template <int NCH, int DEG>
-__device__ __forceinline__ void eu4_taps2(unsigned a, unsigned b, unsigned pitch_bytes, const float *wxa,
-                                          const float *wya, const float *wxb, const float *wyb,
-                                          eu_f2 tx, eu_f2 ty, float *outa, float *outb)
-{
-  constexpr int order = DEG + 1;
-  eu4_f4 ta[2][order], tb[2][order];
-  float suma[NCH], sumb[NCH];
-  float dep = 0.0f;
-  eu4_row_request<order>(a, b, ta[0], tb[0], dep);
-#pragma unroll
-  for (int j = 0; j < order; j++) {
-    eu4_row_wait<order>(ta[j & 1], tb[j & 1]);
-    if (j + 1 < order) {
-      a += pitch_bytes; b += pitch_bytes;
-      // behind the sums of row j - 1
-      if (j >= 1) dep = suma[NCH - 1] + sumb[NCH - 1];
-      eu4_row_request<order>(a, b, ta[(j + 1) & 1], tb[(j + 1) & 1], dep);
-    }
-    if constexpr (DEG == 1) {
-      // _eval_linear, eval.h:1014-1059: wl = 1 - t, wr = t
-      const float wl0a = 1.0f - tx.x, wr0a = tx.x, wl0b = 1.0f - tx.y, wr0b = tx.y;
-#pragma unroll
-      for (int c = 0; c < NCH; c++) {
-        float ra = ta[j & 1][0][c] * wl0a; ra = ra + ta[j & 1][1][c] * wr0a;
-        float rb = tb[j & 1][0][c] * wl0b; rb = rb + tb[j & 1][1][c] * wr0b;
-        if (j == 0) { suma[c] = ra * (1.0f - ty.x); sumb[c] = rb * (1.0f - ty.y); }
-        else { suma[c] = suma[c] + ra * ty.x; sumb[c] = sumb[c] + rb * ty.y; }
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < NCH; c++) {
-        float ra = ta[j & 1][0][c] * wxa[0], rb = tb[j & 1][0][c] * wxb[0];
-#pragma unroll
-        for (int i = 1; i < order; i++) { ra = ra + wxa[i] * ta[j & 1][i][c]; rb = rb + wxb[i] * tb[j & 1][i][c]; }
-        if (j == 0) { suma[c] = ra * wya[0]; sumb[c] = rb * wyb[0]; }
-        else { suma[c] = suma[c] + ra * wya[j]; sumb[c] = sumb[c] + rb * wyb[j]; }
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NCH; c++) { outa[c] = suma[c]; outb[c] = sumb[c]; }
-}
-
-
+typedef float eu4_f4 __attribute__((ext_vector_type(4)));   // one 16-byte LDS texel
 
 // one LDS-DMA row: lane c fetches 16 bytes at sb + voff into LDS dst + 16 c (M0 = dst is written
 // in the statement that uses it and restored for the compiler)
@@ -230,12 +133,11 @@ struct eu4_plan {
 #endif
 
 // ---------------------------------------------------------------------------
-// one tile of the staged kernel. HOIST: the x half of the coordinate chain comes from the
-// column table `ct` (this tile row's plan).
+// one tile of the staged kernel
 // ---------------------------------------------------------------------------
-template <int NCH, int DEG, int PRJ, bool HOIST>
+template <int NCH, int DEG, int PRJ>
 __device__ __forceinline__ void eu4_tile(const eu_render_params &p, const eu4_plan &w, const float *atab,
-                                         float *wtile, const float *ct, int tile_y, int x0, int lane)
+                                         float *wtile, int tile_y, int x0, int lane)
 {
   constexpr int TEX = 4;                              // floats per LDS texel
   constexpr int order = DEG + 1;
@@ -254,77 +156,40 @@ __device__ __forceinline__ void eu4_tile(const eu_render_params &p, const eu4_pl
   eu_i2 hit, ok = { -1, -1 };
   int ixa, ixb;
   float wxa[order], wxb[order];
-  if constexpr (HOIST) {
-    // column entries of the two pixels: ix, tx, wx[0..3], sqrt(rx^2 + rz^2), longitude
-    const float4 *ea = (const float4 *)(ct + (size_t)xac * EU4_COL_FLOATS);
-    const float4 *eb = (const float4 *)(ct + (size_t)xbc * EU4_COL_FLOATS);
-    const float4 a0 = ea[0], a1 = ea[1], b0 = eb[0], b1 = eb[1];
-    const float A1 = rt[1], B1 = rt[4];
+  // rays of both pixels (stepper.h: ray = B * c0 (+ C * c1) + A)
+  eu_ray2 r;
+  {
+    const float A0 = rt[0], A1 = rt[1], A2 = rt[2], B0 = rt[3], B1 = rt[4], B2 = rt[5];
     const eu_f2 c0 = { p.col[xac], p.col[xbc] };
-    const eu_f2 ryy = B1 * c0 + A1;
-    // the atanf table is complete behind this wait (LDS-DMA, issued at kernel entry)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ixa = __float_as_int(a0.x); ixb = __float_as_int(b0.x);
-    ok = ok & (eu_i2){ ixa != INT_MIN ? -1 : 0, ixb != INT_MIN ? -1 : 0 };
-    tx = (eu_f2){ a0.y, b0.y };
-    if constexpr (DEG >= 2) {
-      wxa[0] = a0.z; wxa[1] = a0.w; wxa[2] = a1.x; wxb[0] = b0.z; wxb[1] = b0.w; wxb[2] = b1.x;
-      if constexpr (DEG == 3) { wxa[3] = a1.y; wxb[3] = b1.y; }
+    if (p.form == EU_FORM_BCA) {
+      const float C0 = rt[6], C1 = rt[7], C2 = rt[8];
+      const float *colB = p.col + p.width;
+      const eu_f2 c1 = { colB[xac], colB[xbc] };
+      r.x = B0 * c0 + C0 * c1 + A0;
+      r.y = B1 * c0 + C1 * c1 + A1;
+      r.z = B2 * c0 + C2 * c1 + A2;
     } else {
-#pragma unroll
-      for (int i = 0; i < order; i++) { wxa[i] = 0.0f; wxb[i] = 0.0f; }
+      r.x = B0 * c0 + A0;
+      r.y = B1 * c0 + A1;
+      r.z = B2 * c0 + A2;
     }
-    const eu_f2 qs = { a1.z, b1.z };
-    // ray_to_ll_t's latitude (geometry.h:297-299) and the y half of md_to_spline
-    // (environment.h:988-1006): eu_coord2_ok's operations on the y coordinate
-    const eu_f2 lat = eu_atan2f_2_tab_ok(ryy, qs, atab, 1, ok);
-    hit = (eu_i2){ -1, -1 };
-    if (!s.always_hit) {
-      const eu_f2 lon = { a1.w, b1.w };
-      hit = (lon >= s.wex0) & (lon <= s.wex1) & (lat >= s.wex2) & (lat <= s.wex3);
+    if (p.norm_mode == EU_NORM_DIV) {
+      eu_f2 sqn = r.x * r.x; sqn = sqn + r.y * r.y; sqn = sqn + r.z * r.z;
+      const eu_f2 n = { sqrtf(sqn.x), sqrtf(sqn.y) };
+      r.x = r.x / n; r.y = r.y / n; r.z = r.z / n;
     }
-    eu_f2 i1 = { (float)((double)lat.x - s.tex_y0), (float)((double)lat.y - s.tex_y0) };
-    if (s.cdiv_ok) i1 = eu_div2_const(i1, s.ext_h, s.rcp_ext_h);
-    else i1 = i1 / s.ext_h;
-    i1 = i1 * s.total_h; i1 = i1 - .5f;
-    const eu_f2 sy = i1 - s.win_y_off;
-    gy = eu_gate2_ok(sy, s.gate1, s.lower1, s.upper1, ok);
-  } else {
-    // rays of both pixels (stepper.h: ray = B * c0 (+ C * c1) + A)
-    eu_ray2 r;
-    {
-      const float A0 = rt[0], A1 = rt[1], A2 = rt[2], B0 = rt[3], B1 = rt[4], B2 = rt[5];
-      const eu_f2 c0 = { p.col[xac], p.col[xbc] };
-      if (p.form == EU_FORM_BCA) {
-        const float C0 = rt[6], C1 = rt[7], C2 = rt[8];
-        const float *colB = p.col + p.width;
-        const eu_f2 c1 = { colB[xac], colB[xbc] };
-        r.x = B0 * c0 + C0 * c1 + A0;
-        r.y = B1 * c0 + C1 * c1 + A1;
-        r.z = B2 * c0 + C2 * c1 + A2;
-      } else {
-        r.x = B0 * c0 + A0;
-        r.y = B1 * c0 + A1;
-        r.z = B2 * c0 + A2;
-      }
-      if (p.norm_mode == EU_NORM_DIV) {
-        eu_f2 sqn = r.x * r.x; sqn = sqn + r.y * r.y; sqn = sqn + r.z * r.z;
-        const eu_f2 n = { sqrtf(sqn.x), sqrtf(sqn.y) };
-        r.x = r.x / n; r.y = r.y / n; r.z = r.z / n;
-      }
-    }
-    // the atanf table is complete behind this wait (LDS-DMA, issued at kernel entry)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    eu_f2 sx, sy;
-    hit = eu_coord2_ok<PRJ>(s, r, sx, sy, atab, ok);
-    const eu_f2 gx = eu_gate2_ok(sx, s.gate0, s.lower0, s.upper0, ok);
-    gy = eu_gate2_ok(sy, s.gate1, s.lower1, s.upper1, ok);
-    eu_f2 fx;
-    if constexpr (DEG & 1) fx = (eu_f2){ floorf(gx.x), floorf(gx.y) };
-    else fx = (eu_f2){ roundf(gx.x), roundf(gx.y) };
-    tx = gx - fx;
-    ixa = (int)fx.x; ixb = (int)fx.y;
   }
+  // the atanf table is complete behind this wait (LDS-DMA, issued at kernel entry)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  eu_f2 sx, sy;
+  hit = eu_coord2_ok<PRJ>(s, r, sx, sy, atab, ok);
+  const eu_f2 gx = eu_gate2_ok(sx, s.gate0, s.lower0, s.upper0, ok);
+  gy = eu_gate2_ok(sy, s.gate1, s.lower1, s.upper1, ok);
+  eu_f2 fx;
+  if constexpr (DEG & 1) fx = (eu_f2){ floorf(gx.x), floorf(gx.y) };
+  else fx = (eu_f2){ roundf(gx.x), roundf(gx.y) };
+  tx = gx - fx;
+  ixa = (int)fx.x; ixb = (int)fx.y;
   hit = hit & (eu_i2){ va ? -1 : 0, vb ? -1 : 0 };
   eu_f2 fy;
   if constexpr (DEG & 1) fy = (eu_f2){ floorf(gy.x), floorf(gy.y) };
@@ -377,32 +242,25 @@ __device__ __forceinline__ void eu4_tile(const eu_render_params &p, const eu4_pl
     float wya[order], wyb[order];
     if constexpr (DEG >= 2) {
       eu_weights2<DEG>(s.wm, ty, wy);
-      if constexpr (!HOIST) eu_weights2<DEG>(s.wm, tx, wx);
+      eu_weights2<DEG>(s.wm, tx, wx);
     }
 #pragma unroll
     for (int i = 0; i < order; i++) {
       if constexpr (DEG >= 2) {
         wya[i] = wy[i].x; wyb[i] = wy[i].y;
-        if constexpr (!HOIST) { wxa[i] = wx[i].x; wxb[i] = wx[i].y; }
+        wxa[i] = wx[i].x; wxb[i] = wx[i].y;
       } else {
         wya[i] = wyb[i] = 0.0f;
-        if constexpr (!HOIST) { wxa[i] = wxb[i] = 0.0f; }
+        wxa[i] = wxb[i] = 0.0f;
       }
     }
     // lanes without a hit read the box origin
     const int oa = hit.x ? ((iya - mny) * ibw + (ixa - mnx)) * TEX : 0;
     const int ob = hit.y ? ((iyb - mny) * ibw + (ixb - mnx)) * TEX : 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if EU4_ASM_TAPS
-    eu4_taps2<NCH, DEG>(lds_tile + (unsigned)oa * 4u, lds_tile + (unsigned)ob * 4u, (unsigned)ibw * (TEX * 4u),
-                        wxa, wya, wxb, wyb, tx, ty, qa, qb);
-#else
-    {
-      eu_lptr lt = (eu_lptr)wtile;
-      eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + oa, ibw * TEX, wxa, wya, tx.x, ty.x, qa);
-      eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + ob, ibw * TEX, wxb, wyb, tx.y, ty.y, qb);
-    }
-#endif
+    eu_lptr lt = (eu_lptr)wtile;
+    eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + oa, ibw * TEX, wxa, wya, tx.x, ty.x, qa);
+    eu_accumulate1<NCH, DEG, TEX, int, eu_lptr>(lt + ob, ibw * TEX, wxb, wyb, tx.y, ty.y, qb);
   } else {
 #pragma unroll
     for (int c = 0; c < NCH; c++) { qa[c] = 0.0f; qb[c] = 0.0f; }
@@ -421,8 +279,8 @@ __device__ __forceinline__ void eu4_tile(const eu_render_params &p, const eu4_pl
   if (vb) eu_put<NCH>(orow, xb, qb);
 }
 
-// the staged kernel: one 16x8 tile per wave, EU4_WAVES0 waves (neighbouring tiles of one tile
-// row) per workgroup; they share nothing but the atanf table
+// the staged kernel of cubemap and biatan6 sources: one 16x8 tile per wave, EU4_WAVES0 waves
+// (neighbouring tiles of one tile row) per workgroup; they share nothing but the atanf table
 template <int NCH, int DEG, int PRJ>
 __global__ __launch_bounds__(64 * EU4_WAVES0, EU4_OCC0) void eu_render4s_kernel(const eu_render_params p, const eu4_plan w)
 {
@@ -454,12 +312,7 @@ __global__ __launch_bounds__(64 * EU4_WAVES0, EU4_OCC0) void eu_render4s_kernel(
     __syncthreads();
   }
   if (tile_x >= w.tiles16) return;
-  const int plan = PRJ == EU_SPHERICAL ? w.tileplan[tile_y] : -1;
-  if (plan >= 0)
-    eu4_tile<NCH, DEG, PRJ, PRJ == EU_SPHERICAL>(p, w, atab, tile, w.coltab + (size_t)plan * p.width * EU4_COL_FLOATS,
-                                                  tile_y, tile_x * EU4_TW, lane);
-  else
-    eu4_tile<NCH, DEG, PRJ, false>(p, w, atab, tile, nullptr, tile_y, tile_x * EU4_TW, lane);
+  eu4_tile<NCH, DEG, PRJ>(p, w, atab, tile, tile_y, tile_x * EU4_TW, lane);
 }
 
 // one 16x8 tile by direct gathers: (d+1)^2 taps from global memory, every scalar fallback of the
@@ -608,14 +461,10 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
 template <int NCH, int DEG, int PRJ>
 static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
 {
-  // EU_HIP_R5: 1 (default) the persistent staged kernel of round 3, 0 round 2's one-tile-per-workgroup form
-  // (unset: the persistent kernel for lat/lon sources - headline 1.13 vs 1.22 ms for the launch-level hybrid of
-  // the direct-gather kernels -, round 2's form for cubemap sources: config 3 1.00 vs 1.22 ms)
-  const char *r5env = getenv("EU_HIP_R5");
-  const bool use5 = r5env ? r5env[0] != '0' : PRJ == EU_SPHERICAL;
-  if (use5) {
+  // lat/lon sources: the persistent staged kernel (headline 1.13 vs 1.22 ms for the launch-level hybrid of the
+  // direct-gather kernels); cubemap / biatan6 sources: one tile per workgroup (config 3 1.00 vs 1.22 ms)
+  if constexpr (PRJ == EU_SPHERICAL) {
     // as many workgroups as are resident at once (a persistent kernel must not queue a second round)
-    static const int per_cu_env = [] { const char *e = getenv("EU_HIP_R5_WGS"); return e ? atoi(e) : 0; }();   // A/B runs
     static const int cus = [] {
       int dev = 0, n = 0;
       if (hipGetDevice(&dev) != hipSuccess) return 0;
@@ -626,12 +475,8 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
     // non-zero difference 'angle - origin' is at least 2^-73)
     auto mag_ok = [](double v) { const double a = v < 0 ? -v : v; return a == 0.0 || (a >= 0x1p-20 && a <= 0x1p20); };
     const bool fast = p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && p.band_count <= 1 && p.src.brighten == 1.0f &&
-                      (p.src.prj != EU_SPHERICAL ||
-                       (p.src.always_hit && mag_ok(p.src.tex_x0) && mag_ok(p.src.tex_y0) && p.src.ext_w >= 0x1p-20f &&
-                        p.src.ext_w <= 0x1p20f && p.src.ext_h >= 0x1p-20f && p.src.ext_h <= 0x1p20f && p.tab_finite));
-    static const bool dbg = getenv("EU_HIP_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "eu_render5: fast %d (form %d norm %d bands %d brighten %g always_hit %d cdiv_ok %d)\n", (int)fast, p.form,
-                     p.norm_mode, p.band_count, (double)p.src.brighten, p.src.always_hit, p.src.cdiv_ok);
+                      p.src.always_hit && mag_ok(p.src.tex_x0) && mag_ok(p.src.tex_y0) && p.src.ext_w >= 0x1p-20f &&
+                      p.src.ext_w <= 0x1p20f && p.src.ext_h >= 0x1p-20f && p.src.ext_h <= 0x1p20f && p.tab_finite;
     int per_cu = 0;
     if (fast) {
       static const int occ = [] { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, eu_render5_kernel<NCH, DEG, PRJ, true>, 64 * EU5_WAVES, 0) == hipSuccess ? n : 0; }();
@@ -640,7 +485,6 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
       static const int occ = [] { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, eu_render5_kernel<NCH, DEG, PRJ, false>, 64 * EU5_WAVES, 0) == hipSuccess ? n : 0; }();
       per_cu = occ;
     }
-    if (per_cu_env > 0) per_cu = std::min(per_cu, per_cu_env);
     const int wgs = (cus / 8) * 8 * per_cu;
     if (wgs <= 0) return -1;
     if (fast) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);

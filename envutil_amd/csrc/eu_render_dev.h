@@ -9,13 +9,6 @@
 #include "eu_math.h"
 #include "eu_math2.h"
 
-#ifndef EU_COORD_LEAN
-#define EU_COORD_LEAN 0      // 1: eu_source_coordinate with range-checked FMA forms of its divisions and square roots (measured: config 5 7.3 -> 9.3 ms with EU_COORD_SINCOS, the multi-facet kernel spills three times as much)
-#endif
-#ifndef EU_COORD_SINCOS
-#define EU_COORD_SINCOS 0    // 1: the fisheye mounts sinf and cosf of one angle from one reduction (config 5: 7.3 -> 8.7 ms)
-#endif
-
 #define EU_TILE_W 64
 #define EU_TILE_H 4
 
@@ -329,20 +322,12 @@ __device__ __forceinline__ bool eu_source_coordinate(const eu_src_dev &s, float 
     }
     default: {                 // ray_to_fish_t, geometry.h:513-531
       const float q2 = rx * rx + ry * ry;
-#if EU_COORD_LEAN
-      const float q = eu_sqrt2_guarded((eu_f2){ q2, q2 }).x;     // sqrtf's bits, a quarter of its cycles
-#else
       const float q = sqrtf(q2);
-#endif
       const eu_f2 a = eu_atan2f_2((eu_f2){ rz, ry }, (eu_f2){ q, rx });
       float r = (float)1.57079632679489661923 - a.x;
       float phi = a.y;
       float sn, cs;
-#if EU_COORD_SINCOS
-      eu_sincosf_120(phi, &sn, &cs);     // |phi| <= pi: eu_cosf(phi), eu_sinf(phi) from one reduction
-#else
       cs = eu_cosf(phi); sn = eu_sinf(phi);
-#endif
       c0 = r * cs;
       c1 = r * sn;
       break;
@@ -355,12 +340,7 @@ __device__ __forceinline__ bool eu_source_coordinate(const eu_src_dev &s, float 
     {
       float sqn = c0 * c0;
       sqn = sqn + c1 * c1;
-#if EU_COORD_LEAN
-      const float sq = eu_sqrt2_guarded((eu_f2){ sqn, sqn }).x;
-      float x = eu_div2_guarded((eu_f2){ sq, sq }, (eu_f2){ s.lens_s, s.lens_s }).x;     // sqrtf(sqn) / s.lens_s
-#else
       float x = sqrtf(sqn) / s.lens_s;
-#endif
       float sum = 0.0f, power = 1.0f;
       sum = sum + s.lens_d * power; power = power * x;
       sum = sum + s.lens_c * power; power = power * x;
@@ -384,11 +364,7 @@ __device__ __forceinline__ bool eu_source_coordinate(const eu_src_dev &s, float 
   // (x and y as one pair: packed operations, and the two divisions as one range-checked FMA sequence -
   // the bits of `/`, a quarter of its cycles)
   eu_f2 i = { (float)((double)c0 - s.tex_x0), (float)((double)c1 - s.tex_y0) };
-#if EU_COORD_LEAN
-  i = eu_div2_guarded(i, (eu_f2){ s.ext_w, s.ext_h });
-#else
   i = i / (eu_f2){ s.ext_w, s.ext_h };
-#endif
   i = i * (eu_f2){ s.total_w, s.total_h };
   i = i - .5f;
   i = i - (eu_f2){ s.win_x_off, s.win_y_off };

@@ -310,12 +310,6 @@ __global__ __launch_bounds__(64) void filter_stacked_kernel(iir_dev f, float *co
 #ifndef EU_IIR_AHEAD
 #define EU_IIR_AHEAD 3
 #endif
-#ifdef EU_IIR_EXPERIMENT   // timing experiments only (results are wrong): 1 no recursion, 2 no requests, 4 no write-back
-__device__ int iir_exp;
-#define IIR_EXP(bit) (iir_exp & (bit))
-#else
-#define IIR_EXP(bit) 0
-#endif
 #define EU_IIR_BUFS (EU_IIR_AHEAD + 1)
 
 typedef __attribute__((address_space(3))) float *iir_lptr;
@@ -357,7 +351,7 @@ template <int NCH, int R> struct tile_rows {
   __device__ int chain_off() const { return (lane / NCH) * PITCH + lane % NCH; }
   __device__ void request(unsigned lds, int blk) const
   {
-    if (mover() && !IIR_EXP(2)) {
+    if (mover()) {
       const float *s = g + (long long)blk * (64 * NCH);
 #pragma unroll
       for (int r = 0; r < R; r++) iir_dma16(lds + r * (PITCH * 4), s + r * ls);
@@ -365,7 +359,7 @@ template <int NCH, int R> struct tile_rows {
   }
   __device__ void writeback(iir_lptr t, int blk) const
   {
-    if (mover() && !IIR_EXP(4)) {
+    if (mover()) {
       float *d = g + (long long)blk * (64 * NCH);
       iir_f4 v[R];
 #pragma unroll
@@ -392,14 +386,12 @@ template <int L, bool STACKED> struct tile_cols {
   __device__ void request(unsigned lds, int blk) const
   {
     const int n0 = blk * 64 + lane / (L / 4);
-    if (IIR_EXP(2)) return;
 #pragma unroll
     for (int q = 0; q < OPS; q++) iir_dma16(lds + q * 1024, rowptr(n0 + q * RPI));
   }
   __device__ void writeback(iir_lptr t, int blk) const
   {
     const int n0 = blk * 64 + lane / (L / 4);
-    if (IIR_EXP(4)) return;
     iir_f4 v[OPS];
 #pragma unroll
     for (int q = 0; q < OPS; q++) v[q] = *(iir_l4ptr)(t + q * 256 + lane * 4);
@@ -456,7 +448,7 @@ __device__ __forceinline__ float stream_causal(const T &tl, float *smem, float *
     const bool keep = !ckpt || b == 0 || b == nblk - 1;
     iir_lptr tile = (iir_lptr)smem + (b % EU_IIR_BUFS) * B::BUF;
     if (ckpt && active) iir_store4(ckpt + b * 64, X);
-    if (active && !IIR_EXP(1)) {
+    if (active) {
       iir_lptr t = tile + tl.chain_off();
       float a[64];
 #pragma unroll
@@ -507,7 +499,7 @@ __device__ __forceinline__ void stream_anticausal(const T &tl, float *smem, cons
     }
     const bool redo = ckpt && b != 0 && b != nblk - 1;
     iir_lptr tile = (iir_lptr)smem + (j % EU_IIR_BUFS) * B::BUF;
-    if (active && !IIR_EXP(1)) {
+    if (active) {
       iir_lptr t = tile + tl.chain_off();
       float a[64];
 #pragma unroll
@@ -979,22 +971,14 @@ void launch_brace(float *container, long long SX, long long SY, int nch, int axi
 // checked against on the device, tests/test_gpu_prefilter_stream.py)
 int iir_stream_on()   // bit 0: rows, bit 1: columns, bit 2: checkpoints + recomputation (3 passes per axis)
 {
-#ifdef EU_IIR_EXPERIMENT
-  const char *d = getenv("EU_HIP_IIR_EXP");
-  int dv = d ? atoi(d) : 0;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(iir_exp), &dv, sizeof dv);
-#endif
   const char *e = getenv("EU_HIP_IIR_STREAM");
   return e ? atoi(e) : 7;
 }
 
 // lines per wavefront: few, so that the lines of a large image make more wavefronts than the
 // chip has SIMDs (1024) and a SIMD has two recursions to alternate between
-int iir_env(const char *name, int dflt)
-{
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+constexpr int IIR_ROWS = 8;    // rows of the row sweep
+constexpr int IIR_COLS = 32;   // adjacent floats of the column sweeps
 
 // Scratch for the checkpoints of the streamed sweeps (stream_causal): groups x blocks x 64 floats,
 // stream-ordered allocation. Only when every pole's horizon lies inside the first block (iacc
@@ -1012,34 +996,23 @@ float *iir_ckpt_alloc(const iir_dev &f, long long groups, int len, hipStream_t s
 }
 void iir_ckpt_free(float *p, hipStream_t st) { if (p) (void)hipFreeAsync(p, st); }
 
-// groups of lines -> workgroups of `wpg` independent wavefronts with `wave_lds` bytes each
+// groups of lines -> one wavefront with `wave_lds` bytes per workgroup (measured: 1, 2 and 4 wavefronts
+// per workgroup take the same time, the sweeps are not bound by where the wavefronts sit; 1 keeps the
+// LDS request under 64 KB)
 template <class K, class... A>
 void launch_stream(K kernel, unsigned groups, size_t wave_lds, hipStream_t st, A... args)
 {
-  // measured: 1, 2 and 4 wavefronts per workgroup take the same time (the sweeps are not bound by
-  // where the wavefronts sit); 1 keeps the LDS request under 64 KB
-  int wpg = iir_env("EU_HIP_IIR_WPG", 1);
-  if (wpg < 1 || wpg > 4) wpg = 1;
-  while (wpg > 1 && wpg * wave_lds > 160 * 1024) wpg--;
-  const size_t lds = wpg * wave_lds;
-  (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kernel, dim3((groups + wpg - 1) / wpg), dim3(64 * wpg), lds, st, args..., groups);
-}
-
-template <int NCH, int R>
-void launch_rows_nr(const iir_dev &f, float *base, unsigned groups, long long line_stride, int len, float *ck, hipStream_t st)
-{
-  launch_stream(filter_rows_stream_kernel<NCH, R>, groups,
-                sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_rows<NCH, R>>::BUF, st, f, base, line_stride, len, ck);
+  (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave_lds);
+  hipLaunchKernelGGL(kernel, dim3(groups), dim3(64), wave_lds, st, args..., groups);
 }
 
 template <int NCH>
-unsigned launch_rows_nch(int R, const iir_dev &f, float *base, long long nl, long long line_stride, int len, hipStream_t st)
+unsigned launch_rows_nch(const iir_dev &f, float *base, long long nl, long long line_stride, int len, hipStream_t st)
 {
-  const unsigned groups = (unsigned)(nl / R);
+  const unsigned groups = (unsigned)(nl / IIR_ROWS);
   float *ck = iir_ckpt_alloc(f, groups, len, st);
-  if (R == 4) launch_rows_nr<NCH, 4>(f, base, groups, line_stride, len, ck, st);
-  else launch_rows_nr<NCH, 8>(f, base, groups, line_stride, len, ck, st);
+  launch_stream(filter_rows_stream_kernel<NCH, IIR_ROWS>, groups,
+                sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_rows<NCH, IIR_ROWS>>::BUF, st, f, base, line_stride, len, ck);
   iir_ckpt_free(ck, st);
   return groups;
 }
@@ -1049,16 +1022,15 @@ void launch_filter_rows(const iir_dev &f, float *base, long long nl, int nch, lo
                         int len, hipStream_t st)
 {
   long long done = 0;
-  const int R = iir_env("EU_HIP_IIR_ROWS", 8) == 4 ? 4 : 8;
-  if ((iir_stream_on() & 1) && len >= 64 && nch >= 1 && nch <= 4 && nl >= R) {
+  if ((iir_stream_on() & 1) && len >= 64 && nch >= 1 && nch <= 4 && nl >= IIR_ROWS) {
     unsigned groups;
     switch (nch) {
-      case 1: groups = launch_rows_nch<1>(R, f, base, nl, line_stride, len, st); break;
-      case 2: groups = launch_rows_nch<2>(R, f, base, nl, line_stride, len, st); break;
-      case 3: groups = launch_rows_nch<3>(R, f, base, nl, line_stride, len, st); break;
-      default: groups = launch_rows_nch<4>(R, f, base, nl, line_stride, len, st);
+      case 1: groups = launch_rows_nch<1>(f, base, nl, line_stride, len, st); break;
+      case 2: groups = launch_rows_nch<2>(f, base, nl, line_stride, len, st); break;
+      case 3: groups = launch_rows_nch<3>(f, base, nl, line_stride, len, st); break;
+      default: groups = launch_rows_nch<4>(f, base, nl, line_stride, len, st);
     }
-    done = (long long)groups * R;
+    done = (long long)groups * IIR_ROWS;
   }
   if (done < nl)
     hipLaunchKernelGGL(filter_lines_kernel, dim3(blocks_for((nl - done) * nch, 64)), dim3(64), 0, st, f,
@@ -1069,14 +1041,13 @@ void launch_filter_rows(const iir_dev &f, float *base, long long nl, int nch, lo
 void launch_filter_cols(const iir_dev &f, float *base, long long nfloats, long long es, int len, hipStream_t st)
 {
   long long done = 0;
-  const int L = iir_env("EU_HIP_IIR_COLS", 32) == 16 ? 16 : 32;
-  if ((iir_stream_on() & 2) && len >= 64 && nfloats >= L) {
-    const unsigned groups = (unsigned)(nfloats / L);
+  if ((iir_stream_on() & 2) && len >= 64 && nfloats >= IIR_COLS) {
+    const unsigned groups = (unsigned)(nfloats / IIR_COLS);
     float *ck = iir_ckpt_alloc(f, groups, len, st);
-    if (L == 16) launch_stream(filter_cols_stream_kernel<16>, groups, sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<16, false>>::BUF, st, f, base, es, len, ck);
-    else launch_stream(filter_cols_stream_kernel<32>, groups, sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<32, false>>::BUF, st, f, base, es, len, ck);
+    launch_stream(filter_cols_stream_kernel<IIR_COLS>, groups,
+                  sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<IIR_COLS, false>>::BUF, st, f, base, es, len, ck);
     iir_ckpt_free(ck, st);
-    done = (long long)groups * L;
+    done = (long long)groups * IIR_COLS;
   }
   if (done < nfloats)
     hipLaunchKernelGGL(filter_lines_kernel, dim3(blocks_for(nfloats - done, 64)), dim3(64), 0, st, f,
@@ -1087,14 +1058,13 @@ void launch_filter_cols(const iir_dev &f, float *base, long long nfloats, long l
 void launch_filter_stacked(const iir_dev &f, float *core, long long nfloats, long long row_es, int H, hipStream_t st)
 {
   long long done = 0;
-  const int L = iir_env("EU_HIP_IIR_COLS", 32) == 16 ? 16 : 32;
-  if ((iir_stream_on() & 2) && 2 * H >= 64 && nfloats >= L) {
-    const unsigned groups = (unsigned)(nfloats / L);
+  if ((iir_stream_on() & 2) && 2 * H >= 64 && nfloats >= IIR_COLS) {
+    const unsigned groups = (unsigned)(nfloats / IIR_COLS);
     float *ck = iir_ckpt_alloc(f, groups, 2 * H, st);
-    if (L == 16) launch_stream(filter_stacked_stream_kernel<16>, groups, sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<16, true>>::BUF, st, f, core, nfloats, row_es, H, ck);
-    else launch_stream(filter_stacked_stream_kernel<32>, groups, sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<32, true>>::BUF, st, f, core, nfloats, row_es, H, ck);
+    launch_stream(filter_stacked_stream_kernel<IIR_COLS>, groups,
+                  sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<IIR_COLS, true>>::BUF, st, f, core, nfloats, row_es, H, ck);
     iir_ckpt_free(ck, st);
-    done = (long long)groups * L;
+    done = (long long)groups * IIR_COLS;
   }
   if (done < nfloats)
     hipLaunchKernelGGL(filter_stacked_kernel, dim3(blocks_for(nfloats - done, 64)), dim3(64), 0, st, f,

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of environment switches on bench workloads: VARIANTS="EU_HIP_PLANAR=0 EU_HIP_PLANAR=1" WORKLOADS="headline config3"
+# A/B of environment switches on bench workloads: VARIANTS="EU_HIP_R4=0 EU_HIP_R4=1" WORKLOADS="headline config3"
 set -e
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 make -s -C oracle _build/libeu_oracle.so

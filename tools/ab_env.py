@@ -2,7 +2,7 @@
 """Render one bench workload under several environment settings (read by the library on every
 call), compare every frame with the first one bit for bit on the GPU and time each setting with
 eu_hip_render_timed. usage:
-    python tools/ab_env.py WORKLOAD "EU_HIP_R4=0" "EU_HIP_R4=1" "EU_HIP_R4=1 EU_HIP_R5=0" ...
+    python tools/ab_env.py WORKLOAD "EU_HIP_R4=0" "EU_HIP_R4=1" "EU_HIP_R4=0 EU_HIP_COLMAJOR=1" ...
 Prints one line per setting: kernel ms (HIP events, mean of N launches), differing floats."""
 import ctypes as C
 import os
