@@ -120,6 +120,9 @@ def lib():
     L.eu_hip_cubemap_metrics.argtypes = [i32, f64, i32, i32, vp, vp, vp, vp]
     L.eu_hip_container_geometry.argtypes = [i32, i32, i32, C.c_int64, C.c_int64, vp]
     L.eu_hip_source_load.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_source_load_edited.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_facet_alpha_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.eu_hip_facet_alpha_rows.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32]
     L.eu_hip_source_adopt.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     L.eu_hip_source_alloc.argtypes = [vp, i32, i32, i32, vp]
     L.eu_hip_source_device_ptr.argtypes = [vp, vp, vp]
@@ -199,6 +202,97 @@ def facet_alpha(pixels, polygons=(), crop=None, crop_kind=0):
     return alpha
 
 
+class FacetEdit(C.Structure):
+    """struct eu_facet_edit"""
+    _fields_ = [("polygons", C.c_void_p), ("npolygons", C.c_int32),
+                ("crop_kind", C.c_int32), ("crop_x0", C.c_int32), ("crop_x1", C.c_int32),
+                ("crop_y0", C.c_int32), ("crop_y1", C.c_int32),
+                ("pixel_channels", C.c_int32), ("pixels_on_device", C.c_int32)]
+
+
+def _facet_edit(polygons, crop, crop_kind, pixel_channels, on_device):
+    """(eu_facet_edit, objects it points into) for masks as a list of (xs, ys) and a crop (x0, x1, y0, y1)"""
+    keep = [(np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)) for x, y in polygons]
+    arr = (MaskPolygon * max(len(keep), 1))()
+    for i, (x, y) in enumerate(keep):
+        arr[i].n, arr[i].x, arr[i].y = len(x), x.ctypes.data, y.ctypes.data
+    e = FacetEdit()
+    e.polygons, e.npolygons = C.cast(arr, C.c_void_p), len(keep)
+    e.crop_kind = crop_kind if crop is not None else 0
+    e.crop_x0, e.crop_x1, e.crop_y0, e.crop_y1 = crop if crop is not None else (0, 0, 0, 0)
+    e.pixel_channels, e.pixels_on_device = pixel_channels, int(on_device)
+    return e, (keep, arr)
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _torch_ptr(t):
+    """address of a float32 tensor on the library's device, once the work queued on it is done"""
+    import torch
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise EuError("a torch tensor handed over as pixels is float32, contiguous and on the device")
+    torch.cuda.current_stream(t.device).synchronize()
+    return t.data_ptr()
+
+
+def facet_alpha_rows(width, height, polygons=(), crop=None, crop_kind=0):
+    """eu_hip_facet_alpha_rows: the integer row plan of the alpha plane before the binomial. Returns
+    (keep (h, 2), row_start (h + 1), spans (n, 2)): pixel (x, y) is 0 iff x is outside keep[y] or
+    inside one of spans[row_start[y]:row_start[y + 1]]. Host function."""
+    e, hold = _facet_edit(polygons, crop, crop_kind, 0, False)
+    keep = np.zeros((height, 2), np.int32)
+    row_start = np.zeros(height + 1, np.int32)
+    args = (width, height, e.polygons, e.npolygons, e.crop_kind, e.crop_x0, e.crop_x1, e.crop_y0, e.crop_y1)
+    n = _check(lib().eu_hip_facet_alpha_rows(*args, None, None, None, 0))
+    spans = np.zeros((n, 2), np.int32)
+    _check(lib().eu_hip_facet_alpha_rows(*args, _ptr(keep), _ptr(row_start), _ptr(spans), n))
+    return keep, row_start, spans
+
+
+def facet_alpha_dev(pixels, polygons=(), crop=None, crop_kind=0, shape=None, nchannels=4, want_alpha=True):
+    """eu_hip_facet_alpha_dev: facet_alpha on the device. `pixels` ((h, w, 2|4) float32) is edited in
+    place: a torch tensor on the library's device where it lies, a numpy array through a device copy.
+    pixels=None with shape=(h, w): the alpha plane alone. Returns the plane (numpy) if want_alpha."""
+    L = lib()
+    tmp = []
+
+    def dev(nbytes):
+        q = C.c_void_p()
+        _check(L.eu_hip_malloc(C.byref(q), nbytes))
+        tmp.append(q)
+        return q
+
+    try:
+        if pixels is None:
+            h, w = shape
+            nch, pdev = nchannels, None
+        else:
+            if pixels.ndim != 3 or (not _is_torch(pixels) and (pixels.dtype != np.float32 or not pixels.flags.c_contiguous)):
+                raise EuError("facet_alpha_dev: pixels are (h, w, nchannels) float32, contiguous")
+            h, w, nch = pixels.shape
+            if _is_torch(pixels):
+                pdev = C.c_void_p(_torch_ptr(pixels))
+            else:
+                pdev = dev(pixels.nbytes)
+                _check(L.eu_hip_memcpy_h2d(pdev, _ptr(pixels), pixels.nbytes))
+        e, hold = _facet_edit(polygons, crop, crop_kind, nch, True)
+        adev = dev(4 * w * h) if want_alpha or pixels is None else None
+        _check(L.eu_hip_facet_alpha_dev(pdev, w, h, nch, C.byref(e), adev, None))
+        _check(L.eu_hip_sync())
+        if pixels is not None and not _is_torch(pixels):
+            _check(L.eu_hip_memcpy_d2h(_ptr(pixels), pdev, pixels.nbytes))
+        if adev is None:
+            return None
+        alpha = np.zeros((h, w), np.float32)
+        _check(L.eu_hip_memcpy_d2h(_ptr(alpha), adev, alpha.nbytes))
+        return alpha
+    finally:
+        for q in tmp:
+            L.eu_hip_free(q)
+
+
 def cubemap_metrics(face_px, face_fov=math.pi / 2, support_min=8, tile_px=64):
     sec, lf = C.c_int64(), C.c_int64()
     refc, m2p = C.c_double(), C.c_double()
@@ -263,13 +357,27 @@ class Source:
 
     @classmethod
     def load(cls, fct, pixels, spline_degree, prefilter_degree=None, support_min=8,
-             tile_size=64):
-        """pixels -> braced + prefiltered coefficients, on the device"""
+             tile_size=64, masks=(), crop=None, crop_kind=0):
+        """pixels -> braced + prefiltered coefficients, on the device. `pixels`: a numpy array or a
+        float32 torch tensor on the library's device. masks (PTO exclude polygons, a list of (xs, ys)),
+        crop (x0, x1, y0, y1) with crop_kind 1 rectangular / 2 elliptic: source_t's alpha edit, made on
+        the device on the way into the container (eu_hip_source_load_edited); the pixels may then have
+        one channel fewer than the facet, which gains its alpha channel here."""
         if prefilter_degree is None:
             prefilter_degree = spline_degree
-        pixels = np.ascontiguousarray(pixels, np.float32)
         cf = fct.c_struct()
         h = C.c_void_p()
+        on_device = _is_torch(pixels)
+        if not on_device:
+            pixels = np.ascontiguousarray(pixels, np.float32)
+        # (h, w, channels); (h, w) for the one channel of a facet that gains alpha; else as the facet says
+        pch = pixels.shape[2] if pixels.ndim == 3 else 1 if pixels.ndim == 2 and fct.nchannels == 2 else fct.nchannels
+        if on_device or len(masks) or crop is not None or pch != fct.nchannels:
+            e, hold = _facet_edit(masks, crop, crop_kind, pch, on_device)
+            ptr = C.c_void_p(_torch_ptr(pixels)) if on_device else _ptr(pixels)
+            _check(lib().eu_hip_source_load_edited(C.byref(cf), ptr, C.byref(e), spline_degree, prefilter_degree,
+                                                   support_min, tile_size, C.byref(h)))
+            return cls(h, fct)
         _check(lib().eu_hip_source_load(C.byref(cf), _ptr(pixels), spline_degree,
                                         prefilter_degree, support_min, tile_size, C.byref(h)))
         return cls(h, fct)

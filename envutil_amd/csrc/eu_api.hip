@@ -14,6 +14,7 @@
 #include "eu_device.h"
 #include "eu_setup_math.h"
 #include "eu_imageprep.h"
+#include "eu_alpha.h"
 #include "eu_math2.h"
 
 extern "C" int eu_launch_render(const eu_render_params *p, void *stream);
@@ -100,6 +101,8 @@ struct context {
   std::vector<unsigned char> mplan_key;
   int mplan_form = 0, mplan_norm = 0;
   float *strip = nullptr; size_t strip_cap = 0;   // eu_hip_render_devices: this slot's rows before they are gathered
+  float *aplan = nullptr; size_t aplan_cap = 0;   // row plan of the last device alpha edit (int32 words)
+  hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
 // One context per device SLOT. A process that never calls eu_hip_init_devices has one slot (one process per
 // GPU, the set-up bench.py's multi-rank runs use); eu_hip_init_devices makes a slot per listed device, and every
@@ -882,6 +885,52 @@ int launch_render(const eu_render_params *p, void *st)
   return eu_launch_render(p, st);
 }
 
+
+// ---- PTO masks and lens crops on the device (eu_alpha.hip) ----------------------------------------
+
+// the refusals of eu_hip_facet_alpha, for an eu_facet_edit; *asked: the edit changes anything at all
+int check_edit(const eu_facet_edit *e, int nch, const char *who, bool *asked)
+{
+  const std::string w(who);
+  *asked = false;
+  if (!e) return EU_OK;
+  if (e->npolygons < 0 || (e->npolygons > 0 && !e->polygons) || e->crop_kind < 0 || e->crop_kind > 2)
+    return fail(EU_ERR_ARGUMENT, w + ": polygons / crop kind");
+  for (int i = 0; i < e->npolygons; i++)
+    if (e->polygons[i].n < 0 || (e->polygons[i].n > 0 && (!e->polygons[i].x || !e->polygons[i].y)))
+      return fail(EU_ERR_ARGUMENT, w + ": polygon without vertices");
+  if (e->pixel_channels < 1 || (e->pixel_channels != nch && e->pixel_channels != nch - 1))
+    return fail(EU_ERR_ARGUMENT, w + ": pixel_channels must be the facet's nchannels or one less");
+  *asked = e->npolygons > 0 || e->crop_kind != 0 || e->pixel_channels != nch;
+  if (*asked && nch != 2 && nch != 4)
+    return fail(EU_ERR_ARGUMENT, w + ": a masked or cropped facet has 2 or 4 channels (alpha last)");
+  return EU_OK;
+}
+
+// the row plan of an edit (eu::facet_alpha_rows), uploaded into the context's plan buffer; fills p's tables
+int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
+{
+  std::vector<eu::mask_polygon> ps;
+  for (int i = 0; e && i < e->npolygons; i++) ps.push_back({ e->polygons[i].n, e->polygons[i].x, e->polygons[i].y });
+  std::vector<int> plan, row_start, spans;
+  try {
+    eu::facet_alpha_rows(w, h, ps.data(), int(ps.size()), e ? e->crop_kind : 0, e ? e->crop_x0 : 0, e ? e->crop_x1 : 0,
+                         e ? e->crop_y0 : 0, e ? e->crop_y1 : 0, plan, row_start, spans);
+    plan.insert(plan.end(), row_start.begin(), row_start.end());
+    plan.insert(plan.end(), spans.begin(), spans.end());
+  } catch (...) { return fail(EU_ERR_MEMORY, "facet alpha: host memory"); }
+  // an earlier edit on a caller's stream may still read the buffer
+  if (g.aplan_user) { HIPCHK(hipStreamSynchronize(g.aplan_user)); g.aplan_user = nullptr; }
+  HIPCHK(hipStreamSynchronize(g.stream));
+  int rc;
+  if ((rc = grow(&g.aplan, &g.aplan_cap, plan.size() + 2))) return rc;
+  HIPCHK(hipMemcpy(g.aplan, plan.data(), plan.size() * sizeof(int), hipMemcpyHostToDevice));
+  p->keep = reinterpret_cast<const int32_t *>(g.aplan);
+  p->row_start = p->keep + size_t(h) * 2;
+  p->spans = p->row_start + size_t(h) + 1;
+  return EU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1043,6 +1092,138 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if (e != hipSuccess || rc) {
     (void)hipFree(s->dev);
     delete s;
+    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
+    return fail(rc, "device set-up stage failed");
+  }
+  *out = s;
+  return EU_OK;
+}
+
+int eu_hip_facet_alpha_rows(int width, int height, const eu_mask_polygon *polygons, int npolygons, int crop_kind,
+                            int crop_x0, int crop_x1, int crop_y0, int crop_y1, int32_t *keep, int32_t *row_start,
+                            int32_t *spans, int max_spans)
+{
+  if (width <= 0 || height <= 0) return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: empty image");
+  if (npolygons < 0 || (npolygons > 0 && !polygons) || crop_kind < 0 || crop_kind > 2)
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: polygons / crop kind");
+  std::vector<eu::mask_polygon> ps;
+  for (int i = 0; i < npolygons; i++) {
+    if (polygons[i].n < 0 || (polygons[i].n > 0 && (!polygons[i].x || !polygons[i].y)))
+      return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: polygon without vertices");
+    ps.push_back({ polygons[i].n, polygons[i].x, polygons[i].y });
+  }
+  std::vector<int> k, r, sp;
+  try {
+    eu::facet_alpha_rows(width, height, ps.data(), int(ps.size()), crop_kind, crop_x0, crop_x1, crop_y0, crop_y1, k, r, sp);
+  } catch (...) { return fail(EU_ERR_MEMORY, "facet_alpha_rows: host memory"); }
+  const size_t n = sp.size() / 2;
+  if (n > size_t(INT32_MAX)) return fail(EU_ERR_UNSUPPORTED, "facet_alpha_rows: too many spans");
+  if (keep) memcpy(keep, k.data(), k.size() * sizeof(int32_t));
+  if (row_start) memcpy(row_start, r.data(), r.size() * sizeof(int32_t));
+  if (spans) {
+    if (max_spans < 0 || n > size_t(max_spans)) return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: span buffer too small");
+    if (n) memcpy(spans, sp.data(), sp.size() * sizeof(int32_t));
+  }
+  return int(n);
+}
+
+int eu_hip_facet_alpha_dev(void *pixels_dev, int width, int height, int nchannels, const eu_facet_edit *edit,
+                           float *alpha_out_dev, void *stream)
+{
+  if (width <= 0 || height <= 0 || (nchannels != 2 && nchannels != 4) || (!pixels_dev && !alpha_out_dev))
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_dev: width x height x {2, 4} channels");
+  bool asked;
+  int rc;
+  if ((rc = check_edit(edit, nchannels, "facet_alpha_dev", &asked))) return rc;
+  if (edit && edit->pixel_channels != nchannels)
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_dev: an edit in place keeps the channel count");
+  if ((rc = ensure_init())) return rc;
+  eu_alpha_params p {};
+  if ((rc = upload_alpha_plan(edit, width, height, &p))) return rc;
+  p.src = p.dst = static_cast<float *>(pixels_dev);
+  p.alpha_out = alpha_out_dev;
+  p.src_pitch = p.dst_pitch = size_t(width);
+  p.w = width; p.h = height; p.nch = p.src_ch = nchannels;
+  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
+  if (eu_launch_facet_alpha(&p, st)) return fail(EU_ERR_NO_DEVICE, "facet_alpha_dev: kernel launch failed");
+  if (stream) g.aplan_user = st;
+  return EU_OK;
+}
+
+int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
+                              int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  bool asked;
+  if ((rc = check_edit(edit, fct->nchannels, "source_load_edited", &asked))) return rc;
+  const bool on_device = edit && edit->pixels_on_device;
+  if (!asked && !on_device)
+    return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
+                              tile_size, out);
+  if ((rc = ensure_init())) return rc;
+  int bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  const int nch = s->nch, src_ch = edit->pixel_channels;
+  const bool cube = is_cube(fct->projection);
+  eu::metrics m {};
+  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  // the plane of the edit: the facet's window; cubemaps: the stack of six faces
+  const int w = cube ? int(m.face_px) : int(s->geom.core[0]), h = cube ? int(6 * m.face_px) : int(s->geom.core[1]);
+  const size_t npix = size_t(w) * size_t(h);
+  float *staged = nullptr, *faces = nullptr;     // host pixels at their own channel count; the faces of a cubemap
+  int prc = 0;
+  hipError_t e = hipSuccess;
+  const float *src = static_cast<const float *>(pixels);
+  if (!on_device) {
+    e = hipMalloc((void **)&staged, npix * src_ch * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(staged, pixels, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    src = staged;
+  }
+  if (e == hipSuccess && cube) e = hipMalloc((void **)&faces, npix * nch * sizeof(float));
+  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
+  if (e == hipSuccess) {
+    // pixels -> faces / core of the container through the edit (in place of the plain load's strided copy)
+    const eu_container &gm = s->geom;
+    eu_alpha_params p {};
+    p.src = src;
+    p.dst = cube ? faces : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
+    p.src_pitch = size_t(w);
+    p.dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
+    p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
+    if (asked) {
+      prc = upload_alpha_plan(edit, w, h, &p);
+      if (!prc && eu_launch_facet_alpha(&p, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_edited: kernel launch failed");
+    } else {
+      e = hipMemcpy2DAsync(p.dst, p.dst_pitch * nch * sizeof(float), src, size_t(w) * nch * sizeof(float),
+                           size_t(w) * nch * sizeof(float), size_t(h), hipMemcpyDeviceToDevice, g.stream);
+    }
+  }
+  if (e == hipSuccess && !prc) {
+    if (cube) {
+      rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
+                                   m.refc_md, m.model_to_px, prefilter_degree, g.stream);
+    } else {
+      // as eu_hip_source_load: full spherical images get the two-axis periodic scheme
+      int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
+                      && fct->width == 2 * fct->height;
+      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, g.stream);
+    }
+  }
+  const hipError_t e2 = hipStreamSynchronize(g.stream);
+  if (e == hipSuccess) e = e2;
+  if (staged) (void)hipFree(staged);
+  if (faces) (void)hipFree(faces);
+  if (e != hipSuccess || rc || prc) {
+    (void)hipFree(s->dev);
+    delete s;
+    if (prc) return prc;           // the plan's upload or the edit's launch: the message is set
     if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
     return fail(rc, "device set-up stage failed");
   }

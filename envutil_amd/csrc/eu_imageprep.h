@@ -1,8 +1,9 @@
 // Load-time edits of a facet's pixels that PTO scripts ask for: exclude masks (k-lines) and lens
-// crops (the S clause of an i-line). Host code, run once per image before the pixels go to the
-// device (source_t's constructor, environment.h:700-890, does the same on the CPU before it
-// prefilters): an alpha plane starts at 1, polygons and the outside of the crop clear it, a 5-tap
-// binomial softens it along both axes, every channel of the image is multiplied by it.
+// crops (the S clause of an i-line). Host code (source_t's constructor, environment.h:700-890,
+// does the same on the CPU before it prefilters): an alpha plane starts at 1, polygons and the
+// outside of the crop clear it, a 5-tap binomial softens it along both axes, every channel of the
+// image is multiplied by it. facet_alpha is the whole edit on the host (eu_hip_facet_alpha);
+// facet_alpha_rows is the part of it the device form (eu_alpha.hip) takes from the host.
 //
 // Arithmetic follows the reference operation for operation (float products and sums, no
 // contraction), including the ORDER of the five products in the binomial: zimt's fir_filter
@@ -19,9 +20,11 @@
 namespace eu {
 
 // fill_polygon (envutil_basic.cc:236-320): scan lines, crossings with their direction, fill
-// where the winding number is not zero. clear(x, y) is called for every pixel inside.
+// where the winding number is not zero. emit(y, x0, x1) is called for every run [x0, x1) of row y
+// the polygon covers, clipped to [left, right) - in the order the reference fills them; a run may
+// be empty. This is the one copy of the rule: the per-pixel form and the row plan both read it.
 template <class F>
-inline void fill_polygon(const float *px, const float *py, int n, int left, int top, int right, int bot, F clear)
+inline void polygon_spans(const float *px, const float *py, int n, int left, int top, int right, int bot, F emit)
 {
   std::vector<int> node_x(size_t(n > 0 ? n : 1)), dir(size_t(n > 0 ? n : 1));
   for (int y = top; y < bot; y++) {
@@ -55,10 +58,17 @@ inline void fill_polygon(const float *px, const float *py, int n, int left, int 
       if (node_x[size_t(i + 1)] > left) {
         if (node_x[size_t(i)] < left) node_x[size_t(i)] = left;
         if (node_x[size_t(i + 1)] > right) node_x[size_t(i + 1)] = right;
-        for (int x = node_x[size_t(i)]; x < node_x[size_t(i + 1)]; x++) clear(x, y);
+        emit(y, node_x[size_t(i)], node_x[size_t(i + 1)]);
       }
     }
   }
+}
+
+// clear(x, y) is called for every pixel inside the polygon
+template <class F>
+inline void fill_polygon(const float *px, const float *py, int n, int left, int top, int right, int bot, F clear)
+{
+  polygon_spans(px, py, n, left, top, right, bot, [&](int y, int x0, int x1) { for (int x = x0; x < x1; x++) clear(x, y); });
 }
 
 // zimt's REFLECT extrapolation (zimt/extrapolate.h:141-155)
@@ -172,6 +182,69 @@ inline void facet_alpha(float *alpha, int w, int h, const mask_polygon *polys, i
     for (int y = y0; y < y1; y++) binomial_line(alpha + size_t(y) * w, tmp.data() + size_t(y) * w, w, 1);
   });
   parallel_rows(h, [&](int y0, int y1) { binomial_rows(tmp.data(), alpha, w, h, y0, y1); });
+}
+
+// The stage-0 alpha plane (before the binomial) holds 0 and 1 only, and which pixels are 0 can be said
+// with integers: per row y the interval [keep[2y], keep[2y+1]) of columns the crop keeps (the whole
+// row without a crop, empty outside it) and the runs [x0, x1) the polygons clear, as CSR (row_start:
+// h + 1 offsets; spans: pairs, polygon by polygon in the order fill_polygon produces them). Pixel
+// (x, y) is 0 iff x is outside the row's interval or inside one of its runs. This is what the device
+// form of facet_alpha (eu_alpha.hip) reads: no floating point crosses over.
+inline void facet_alpha_rows(int w, int h, const mask_polygon *polys, int npolys, int crop_kind, int cx0, int cx1,
+                             int cy0, int cy1, std::vector<int> &keep, std::vector<int> &row_start,
+                             std::vector<int> &spans)
+{
+  keep.assign(size_t(h) * 2, 0);
+  for (int y = 0; y < h; y++) keep[size_t(y) * 2 + 1] = w;
+  if (crop_kind == 2) {
+    // the elliptic crop, with facet_alpha's own expressions; the kept set of a row,
+    // !(fabsf(float(x) - mx) > xmargin), is an interval around the column nearest to mx - its ends are
+    // found by evaluating that predicate (bisection), not by solving for them
+    const float a = float(std::fabs(double(cx1 - cx0)) / 2.0), b = float(std::fabs(double(cy1 - cy0)) / 2.0);
+    const float mx = float((cx0 + cx1) / 2.0), my = float((cy0 + cy1) / 2.0);
+    const float fc = std::floor(mx);
+    const int xc = !(fc > 0.0f) ? 0 : fc > float(w - 1) ? w - 1 : int(fc);
+    for (int y = 0; y < h; y++) {
+      int &k0 = keep[size_t(y) * 2], &k1 = keep[size_t(y) * 2 + 1];
+      const float dy = std::fabs(float(y) - my);
+      if (dy > b) { k0 = k1 = 0; continue; }
+      const float xmargin = float(std::sqrt(double(a * a) * (1.0 - double((dy * dy) / (b * b)))));
+      auto kept = [&](int x) { return !(std::fabs(float(x) - mx) > xmargin); };
+      // |float(x) - mx| is smallest at floor(mx) or the column after it (clamped to the image)
+      int c = xc;
+      if (!kept(c)) {
+        c = xc + 1 < w ? xc + 1 : xc;
+        if (!kept(c)) { k0 = k1 = 0; continue; }
+      }
+      int lo = 0, hi = c;              // first kept column in [0, c]
+      while (lo < hi) { const int m = lo + (hi - lo) / 2; if (kept(m)) hi = m; else lo = m + 1; }
+      k0 = lo;
+      lo = c; hi = w - 1;              // last kept column in [c, w - 1]
+      while (lo < hi) { const int m = lo + (hi - lo + 1) / 2; if (kept(m)) lo = m; else hi = m - 1; }
+      k1 = lo + 1;
+    }
+  } else if (crop_kind == 1) {
+    const int k0 = cx0 < 0 ? 0 : cx0 > w ? w : cx0, k1 = cx1 < 0 ? 0 : cx1 > w ? w : cx1;
+    for (int y = 0; y < h; y++) {
+      const bool in = y >= cy0 && y < cy1 && k0 < k1;
+      keep[size_t(y) * 2] = in ? k0 : 0;
+      keep[size_t(y) * 2 + 1] = in ? k1 : 0;
+    }
+  }
+  std::vector<int> run;                // y, x0, x1 in the order of emission
+  for (int p = 0; p < npolys; p++)
+    polygon_spans(polys[p].x, polys[p].y, polys[p].n, 0, 0, w, h, [&](int y, int x0, int x1) {
+      if (x0 < x1) { run.push_back(y); run.push_back(x0); run.push_back(x1); }
+    });
+  row_start.assign(size_t(h) + 1, 0);
+  for (size_t i = 0; i < run.size(); i += 3) row_start[size_t(run[i]) + 1]++;
+  for (int y = 0; y < h; y++) row_start[size_t(y) + 1] += row_start[size_t(y)];
+  spans.assign(run.size() / 3 * 2, 0);
+  std::vector<int> at(row_start.begin(), row_start.end() - 1);
+  for (size_t i = 0; i < run.size(); i += 3) {
+    const size_t k = size_t(at[size_t(run[i])]++);
+    spans[2 * k] = run[i + 1]; spans[2 * k + 1] = run[i + 2];
+  }
 }
 
 }  // namespace eu

@@ -89,6 +89,10 @@ struct facet_spec : public facet_base
   // pixels_prepared: the caller has applied masks and crop to `pixels` (prepare_facet_pixels,
   // eu_imageprep.hpp - what source_t's constructor does after read_image_data)
   bool pixels_prepared = false;
+  // channels of `pixels` where payload() makes that edit itself (has_pto_mask / has_lens_crop and
+  // !pixels_prepared): nchannels, or nchannels - 1 for an image that gains its alpha channel in the
+  // edit (envutil_main.cc:1062-1075). 0: nchannels.
+  int pixel_channels = 0;
   const float *pixels = nullptr;  // window_width x window_height x nchannels (cubemaps: 6 faces)
 };
 
@@ -226,15 +230,10 @@ struct hip_dispatch : public dispatch_base
     if (projection != args.projection) return EU_ERR_ARGUMENT;
     if ((ninputs == 9) != !args.twine_spread.empty()) return EU_ERR_ARGUMENT;
     if (args.tethered ? !args.p_screen_data : !args.p_output) return EU_ERR_ARGUMENT;
-    // PTO masks and lens crops edit the pixels at load time (prepare_facet_pixels) and must have
-    // been applied by the caller; an unknown synopsis is the reference's assert(false)
-    // (envutil_payload.cc:2316-2318)
+    // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
     if (args.synopsis != "panorama" && args.synopsis != "hdr_merge") return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
     if (args.single >= int(args.facet_spec_v.size()) || args.solo >= int(args.facet_spec_v.size())) return EU_ERR_ARGUMENT;
-    for (const auto &fct : args.facet_spec_v)
-      if ((fct.has_pto_mask || fct.has_lens_crop) && !fct.pixels_prepared && !resident.count(fct.asset_key))
-        return EU_ERR_UNSUPPORTED;
     std::vector<eu_source *> srcs;
     for (size_t fi = 0; fi < args.facet_spec_v.size(); fi++) {
       // --solo: only that facet takes part (fuse(), envutil_payload.cc:2085-2127)
@@ -244,8 +243,24 @@ struct hip_dispatch : public dispatch_base
       if (it == resident.end()) {
         eu_facet e = to_eu(fct);
         eu_source *s = nullptr;
-        int rc = eu_hip_source_load(&e, fct.pixels, args.spline_degree, args.prefilter_degree,
-                                    args.support_min, args.tile_size, &s);
+        int rc;
+        if ((fct.has_pto_mask || fct.has_lens_crop) && !fct.pixels_prepared) {
+          // PTO masks and lens crops edit the pixels at load time, as source_t's constructor does
+          // (environment.h:700-890) - here on the device, on the way into the container
+          std::vector<eu_mask_polygon> polys;
+          for (const auto &m : fct.pto_mask_v)
+            if (m.variant == 0) polys.push_back({ int(m.vx.size()), m.vx.data(), m.vy.data() });   // other variants: ignored, as there
+          eu_facet_edit ed {};
+          ed.polygons = polys.data(); ed.npolygons = int(polys.size());
+          ed.crop_kind = !fct.has_lens_crop ? 0 : fct.projection == FISHEYE ? 2 : 1;
+          ed.crop_x0 = fct.crop_x0; ed.crop_x1 = fct.crop_x1; ed.crop_y0 = fct.crop_y0; ed.crop_y1 = fct.crop_y1;
+          ed.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
+          rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
+                                         args.support_min, args.tile_size, &s);
+        } else {
+          rc = eu_hip_source_load(&e, fct.pixels, args.spline_degree, args.prefilter_degree,
+                                  args.support_min, args.tile_size, &s);
+        }
         if (rc != EU_OK) return rc;
         it = resident.emplace(fct.asset_key, s).first;
       } else {

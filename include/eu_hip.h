@@ -204,6 +204,27 @@ typedef struct eu_mask_polygon { int n; const float *x; const float *y; } eu_mas
 int  eu_hip_facet_alpha(float *pixels, int width, int height, int nchannels,
                         const eu_mask_polygon *polygons, int npolygons, int crop_kind,
                         int crop_x0, int crop_x1, int crop_y0, int crop_y1, float *alpha_out);
+/* rows of the stage-0 alpha plane (before the binomial): pixel (x, y) is 0 iff x is outside
+ * keep[2y] .. keep[2y+1] or inside one of the spans row_start[y] .. row_start[y+1] (pairs [x0, x1),
+ * clipped to the image). keep: 2 x height, row_start: height + 1 entries (either may be NULL).
+ * spans == NULL: count only. Returns the number of spans or a negative eu_status (EU_ERR_ARGUMENT
+ * when there are more than max_spans). Host function: this integer plan is all the device form of
+ * the edit reads, a few KB whatever the image's size. */
+int  eu_hip_facet_alpha_rows(int width, int height, const eu_mask_polygon *polygons, int npolygons,
+                             int crop_kind, int crop_x0, int crop_x1, int crop_y0, int crop_y1,
+                             int32_t *keep, int32_t *row_start, int32_t *spans, int max_spans);
+/* The same edit, made on the device (eu_alpha.hip; bit for bit the host function's result). */
+typedef struct eu_facet_edit {
+  const eu_mask_polygon *polygons; int32_t npolygons;      /* PTO k-lines, variant 0          */
+  int32_t crop_kind, crop_x0, crop_x1, crop_y0, crop_y1;   /* as eu_hip_facet_alpha           */
+  int32_t pixel_channels;     /* channels of `pixels`: fct->nchannels or fct->nchannels - 1   */
+  int32_t pixels_on_device;   /* `pixels` is device memory of the library's device            */
+} eu_facet_edit;
+/* device twin of eu_hip_facet_alpha: pixels_dev (may be NULL; width x height x nchannels, dense,
+ * edit->pixel_channels == nchannels) edited in place, alpha_out_dev (may be NULL) receives the
+ * plane; asynchronous on `stream` (NULL: the library's). edit == NULL: nothing is cleared. */
+int  eu_hip_facet_alpha_dev(void *pixels_dev, int width, int height, int nchannels,
+                            const eu_facet_edit *edit, float *alpha_out_dev, void *stream);
 int  eu_hip_cubemap_metrics(int face_px, double face_fov, int support_min,
                             int tile_px, int64_t *section_px,
                             int64_t *left_frame_px, double *refc_md,
@@ -220,6 +241,17 @@ int  eu_hip_container_geometry(int degree, int bc0, int bc1, int64_t w,
 int  eu_hip_source_load(const eu_facet *fct, const float *pixels,
                         int spline_degree, int prefilter_degree,
                         int support_min, int tile_size, eu_source **out);
+/* eu_hip_source_load with source_t's alpha edit (environment.h:700-890) done on the device on the
+ * way into the container: a facet of a PTO project with exclude masks or a lens crop. `pixels` has
+ * edit->pixel_channels channels - where that is nchannels - 1 the facet gains its alpha channel
+ * here, set to 1 before the edit (environment.h:707-725) - and lies in host memory or, with
+ * edit->pixels_on_device, in memory of the library's device. Cubemaps: the plane is the stack of
+ * six faces. An edit needs nchannels 2 or 4. edit == NULL, or no polygons, crop_kind 0 and
+ * pixel_channels == nchannels: the same container as eu_hip_source_load. Argument errors are
+ * reported before a device is looked for. */
+int  eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit,
+                               int spline_degree, int prefilter_degree, int support_min,
+                               int tile_size, eu_source **out);
 /* Adopt an already prefiltered and braced container (host pointer, shape as
  * eu_hip_container_geometry reports; cubemaps: the IR image section_px x
  * 6*section_px). This is what a bound reference hands over when it keeps its

@@ -151,8 +151,9 @@ static int core(int argc, const char *const *argv)
                    f.window_width, cube ? 6 * f.window_width : f.window_height);
       return 2;
     }
-    // PTO masks and lens crops edit the loaded pixels (environment.h:700-890)
-    if (!prepare_facet_pixels(f, pixels[k], nch, err)) {
+    // PTO masks and lens crops edit the loaded pixels (environment.h:700-890): the dispatch does that on the
+    // device when it loads the facet, from the pixels at the file's own channel count
+    if (!check_facet_pixels(f, pixels[k].size(), nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
       return 2;
     }
