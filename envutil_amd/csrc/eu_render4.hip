@@ -116,11 +116,14 @@ struct eu4_plan {
   int l2_off[9];
   int l2_half;
   unsigned long long l2_magic;
-  // the first loop's list, the same way: {double row m, its column plan} pairs of XCD x at l1_rows[2 * l1_off[x] ...],
-  // walked with a fixed stride (equal tiles: no queue); l1_magic = floor(2^40 / tiles16) + 1
-  const int *l1_rows;
+  // the first loop's list: entries of EU_SHARE_ENTRY_INTS ints (eu_share_groups.h: a leader double row and the
+  // members rendered from its coordinates), those of XCD x at l1_ent[EU_SHARE_ENTRY_INTS * l1_off[x] ...]; an entry
+  // covers l1_ecols tile columns; walked with a fixed stride (no queue); l1_magic = floor(2^40 / l1_ecols) + 1
+  const int *l1_ent;
   int l1_off[9];
+  int l1_ecols;
   unsigned long long l1_magic;
+  const int *xtab;        // [plan][tiles16] { min, max } of the column entries' base position ix; min = INT_MAX: not fast
 #ifdef EU5_STAMPS
   unsigned long long *stamps;   // diagnostic build: 8 s_memtime stamps per tile of eu_render5_kernel
 #endif
@@ -128,8 +131,10 @@ struct eu4_plan {
 
 #ifdef EU5_STAMPS
 #define EU5_STAMP(k) do { asm volatile("" ::: "memory"); st_[k] = __builtin_amdgcn_s_memtime(); asm volatile("" ::: "memory"); } while (0)
+#define EU5_STAMP32(k) do { asm volatile("" ::: "memory"); st_[k] = (unsigned)__builtin_amdgcn_s_memtime(); asm volatile("" ::: "memory"); } while (0)
 #else
 #define EU5_STAMP(k) do { } while (0)
+#define EU5_STAMP32(k) do { } while (0)
 #endif
 
 // ---------------------------------------------------------------------------
@@ -361,6 +366,7 @@ __device__ __forceinline__ void eu4_direct_tile(const eu_render_params &p, const
   if (vb) eu_put<NCH>(orow, xb, pxb);
 }
 
+#include "eu_share_groups.h"
 #include "eu_render5.h"
 
 // ---------------------------------------------------------------------------
@@ -454,6 +460,10 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
   }
 }
 
+// follower tiles (eu_share_groups.h) of the plan about to be launched / of the last launch of eu_render5_kernel's FAST form
+static long long eu4_followers_plan = 0, eu4_followers_last = 0;
+extern "C" unsigned long long eu_hip_share_follower_tiles(void) { return (unsigned long long)eu4_followers_last; }
+
 #ifndef EU4_DIRECT_WGS
 #define EU4_DIRECT_WGS 2048
 #endif
@@ -487,6 +497,7 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
     }
     const int wgs = (cus / 8) * 8 * per_cu;
     if (wgs <= 0) return -1;
+    if (fast) eu4_followers_last = eu4_followers_plan;
     if (fast) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
     else hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, false>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
   } else {
@@ -550,8 +561,11 @@ struct plan_cache {
   int planned_rows = 0;      // tile rows with a column plan
   int *l2_rows = nullptr; size_t l2_cap = 0;
   int l2_off[9] = {};
-  int *l1_rows = nullptr; size_t l1_cap = 0;
+  int *l1_ent = nullptr; size_t l1_cap = 0;
   int l1_off[9] = {};
+  int l1_ecols = 1;
+  int *xtab = nullptr; size_t xtab_cap = 0;
+  long long follower_tiles = 0;
   hipStream_t last_stream = nullptr;   // where the plans were last read
 } g4s[EU_MAX_SLOTS];
 // one cache per device slot (eu_api.hip: eu_hip_init_devices)
@@ -584,6 +598,7 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
                                  unsigned long long plan_gen, int only_if_worth, void *stream)
 {
   eu_render_params p = *pp;
+  eu4_followers_last = 0;
   if (p.twine || p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return 1;
   if (p.norm_mode != EU_NORM_NONE && p.norm_mode != EU_NORM_DIV) return 1;
   if (p.src.prj != EU_SPHERICAL && p.src.prj != EU_CUBEMAP && p.src.prj != EU_BIATAN6) return 1;
@@ -602,13 +617,21 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
   w.atab_g = g4.atab;
 
   // ---- column plans (cached while nothing they depend on changes) ----------------------
-  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 8 * sizeof(int));
+  // EU_HIP_SHARE (read on every call, like the other A/B switches): 0: no tile is rendered from another tile's
+  // coordinates, m: column mirrors only, f: other faces only; anything else, or unset: both
+  int share_mode = EU_SHARE_FACES | EU_SHARE_MIRRORS;
+  if (const char *e = getenv("EU_HIP_SHARE")) {
+    if (e[0] == '0') share_mode = 0;
+    else if (e[0] == 'm') share_mode = EU_SHARE_MIRRORS;
+    else if (e[0] == 'f') share_mode = EU_SHARE_FACES;
+  }
+  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 9 * sizeof(int));
   {
     unsigned char *q = key.data();
     memcpy(q, &plan_gen, sizeof plan_gen); q += sizeof plan_gen;
     eu_src_dev sd = p.src; sd.base = nullptr;
     memcpy(q, &sd, sizeof sd); q += sizeof sd;
-    const int v[8] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode };
+    const int v[9] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, share_mode };
     memcpy(q, v, sizeof v);
   }
   // (cubemap / biatan6 sources never read the tile plan: no plans, no upload, no synchronisation for them)
@@ -678,23 +701,6 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
         g4.l2_cap = all.size() + 1;
       }
       if (!all.empty() && hipMemcpy(g4.l2_rows, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-      // the first loop's double rows per XCD (units of EU5_UNIT_ROWS / 2 double rows), with their plans
-      std::vector<int> prs[8];
-      for (int m = 0; 2 * m + 1 < p.tiles_y; m++)
-        if (tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1]) {
-          auto &v = prs[(m / (EU5_UNIT_ROWS / 2)) & 7];
-          v.push_back(m); v.push_back(tp[(size_t)2 * m]);
-        }
-      std::vector<int> all1;
-      for (int x = 0; x < 8; x++) { g4.l1_off[x] = (int)all1.size() / 2; all1.insert(all1.end(), prs[x].begin(), prs[x].end()); }
-      g4.l1_off[8] = (int)all1.size() / 2;
-      if (g4.l1_cap < all1.size() + 2) {
-        if (g4.l1_rows) (void)hipFree(g4.l1_rows);
-        g4.l1_rows = nullptr; g4.l1_cap = 0;
-        if (hipMalloc((void **)&g4.l1_rows, (all1.size() + 2) * sizeof(int)) != hipSuccess) return -1;
-        g4.l1_cap = all1.size() + 2;
-      }
-      if (!all1.empty() && hipMemcpy(g4.l1_rows, all1.data(), all1.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
     }
     for (size_t j = 0; j < plans.size() / 4; j++) {
       float *ct = g4.coltab + j * (size_t)p.width * EU4_COL_FLOATS;
@@ -704,6 +710,45 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
         default: launch_colplan<3>(p, ct, &plans[4 * j], st); break;
       }
       if (hipGetLastError() != hipSuccess) return -1;
+    }
+    {
+      // the first loop's entries per XCD and the boxes' x extents, from the bits of the tables the kernel reads
+      // (eu_share_groups.h): the column plans come back to the host once per plan build
+      const int nplans = (int)(plans.size() / 4);
+      std::vector<float> h_ct((size_t)nplans * p.width * EU4_COL_FLOATS);
+      if (nplans) {
+        if (hipStreamSynchronize(st) != hipSuccess) return -1;
+        if (hipMemcpy(h_ct.data(), g4.coltab, h_ct.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+      }
+      std::vector<int> cm, cp;
+      for (int m = 0; 2 * m + 1 < p.tiles_y; m++)
+        if (tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1]) { cm.push_back(m); cp.push_back(tp[(size_t)2 * m]); }
+      eu_share_input in;
+      in.width = p.width; in.tiles16 = w.tiles16; in.row_begin = p.row_begin; in.row_end = p.row_end;
+      in.band_mode = p.band_count > 1;
+      in.ncand = (int)cm.size(); in.cand_m = cm.data(); in.cand_plan = cp.data();
+      in.h_row = h_row; in.h_row_floats = h_row_floats; in.row_floats = EU_ROW_FLOATS;
+      in.coltab = nplans ? h_ct.data() : nullptr; in.col_floats = EU4_COL_FLOATS; in.nplans = nplans;
+      in.mode = share_mode; in.unit_drows = EU5_UNIT_ROWS / 2;
+      eu_share_result gr;
+      eu_share_build(in, gr);
+      if (g4.l1_cap < gr.entries.size() + 2) {
+        if (g4.l1_ent) (void)hipFree(g4.l1_ent);
+        g4.l1_ent = nullptr; g4.l1_cap = 0;
+        if (hipMalloc((void **)&g4.l1_ent, (gr.entries.size() + 2) * sizeof(int)) != hipSuccess) return -1;
+        g4.l1_cap = gr.entries.size() + 2;
+      }
+      if (!gr.entries.empty() && hipMemcpy(g4.l1_ent, gr.entries.data(), gr.entries.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
+      if (g4.xtab_cap < gr.xtab.size()) {
+        if (g4.xtab) (void)hipFree(g4.xtab);
+        g4.xtab = nullptr; g4.xtab_cap = 0;
+        if (hipMalloc((void **)&g4.xtab, gr.xtab.size() * sizeof(int)) != hipSuccess) return -1;
+        g4.xtab_cap = gr.xtab.size();
+      }
+      if (hipMemcpy(g4.xtab, gr.xtab.data(), gr.xtab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
+      for (int x = 0; x < 9; x++) g4.l1_off[x] = gr.off[x];
+      g4.l1_ecols = gr.ecols;
+      g4.follower_tiles = gr.follower_tiles;
     }
     g4.key.swap(key);
   }
@@ -716,9 +761,12 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
   for (int x = 0; x < 9; x++) w.l2_off[x] = g4.l2_off[x];
   w.l2_half = (w.tiles16 + 1) / 2;
   w.l2_magic = (1ull << 40) / (unsigned long long)w.l2_half + 1;
-  w.l1_rows = g4.l1_rows;
+  w.l1_ent = g4.l1_ent;
   for (int x = 0; x < 9; x++) w.l1_off[x] = g4.l1_off[x];
-  w.l1_magic = (1ull << 40) / (unsigned long long)w.tiles16 + 1;
+  w.l1_ecols = g4.l1_ecols;
+  w.l1_magic = (1ull << 40) / (unsigned long long)w.l1_ecols + 1;
+  w.xtab = g4.xtab;
+  eu4_followers_plan = g4.follower_tiles;
   g4.last_stream = st;
 #ifdef EU5_STAMPS
   // diagnostic build: stamps of every tile, averaged per pass count / plan kind after the launch

@@ -206,7 +206,7 @@ __device__ __forceinline__ void eu5_load8(const eu_render_params &p, int tile_y,
 }
 
 // PRE (with !HOIST, FAST): the tile's table values come in T, requested by the previous tile ahead of its
-// stores, and this tile requests the next one's (have_n, ty_n, x0_n -> Tn) ahead of its own - see eu5_tile16h
+// stores, and this tile requests the next one's (have_n, ty_n, x0_n -> Tn) ahead of its own - see eu5_group16
 template <int NCH, int DEG, int PRJ, bool HOIST, bool FAST, bool PRE = false>
 __device__ __forceinline__ void eu5_tile(const eu_render_params &p, const eu4_plan &w, const float *atab,
                                          float *wtile, const float *ct, int tile_y, int x0, int lane,
@@ -540,9 +540,9 @@ __device__ __forceinline__ void eu5_stage(const eu_src_dev &s, const eu5_box &bx
 // entry: base position, x weights, sqrt(rx^2 + rz^2)) and run two independent latitude chains, which is what a
 // wave needs to issue a packed operation every 4 cycles instead of every 8 (a dependent chain of packed
 // operations issues at half rate, and four waves per SIMD do not always have two of them in a vector phase);
-// the box reduction, the DMA issue and its round trip are paid once per 256 pixels. Headline: the box of a
-// 16x16 tile of an equatorial face is at most 24 x 24 texels - the slice. Returns false when the tile has to
-// be rendered as two 16x8 tiles (box too large, a lane off the fast path).
+// the DMA issue and its round trip are paid once per 256 pixels. Headline: the box of a 16x16 tile of an
+// equatorial face is at most 24 x 24 texels - the slice. A tile that cannot be rendered this way (box too
+// large, a lane off the fast path) goes to the work list as two 16x8 tiles. See eu5_group16.
 // what a 16x16 tile reads from the stepper tables and the column table (22 registers)
 struct eu5_tab16 {
   eu4_f4 a0, a1, b0, b1;      // the column entries of the lane's two columns
@@ -565,136 +565,228 @@ __device__ __forceinline__ void eu5_load16(const eu_render_params &p, const floa
   T.c0 = (eu_f2){ p.col[xac], p.col[xbc] };
 }
 
-// T: the tile's table values, requested by the PREVIOUS tile ahead of its stores; this tile does the same
-// for the next one (have_n, ct_n, ty_n, x0_n -> Tn). vmcnt counts in issue order: loads requested behind
-// a tile's stores cannot be waited for without waiting for the stores' acknowledgement too (1-2k cycles
-// at the head of every tile).
+typedef const __attribute__((address_space(4))) int *eu5_cint;   // read through the scalar cache
+
+// the column entries of the lane's two columns only: all a follower of a group reads from the tables
+__device__ __forceinline__ void eu5_load_cols(const float *ct, int xa, int xb, eu5_tab16 &T)
+{
+  const eu4_f4 *ea = (const eu4_f4 *)(ct + (size_t)xa * EU4_COL_FLOATS);
+  const eu4_f4 *eb = (const eu4_f4 *)(ct + (size_t)xb * EU4_COL_FLOATS);
+  T.a0 = ea[0]; T.a1 = ea[1]; T.b0 = eb[0]; T.b1 = eb[1];
+}
+
+// min and max over the wavefront, the two reductions interleaved (a DPP operand written by a VALU instruction
+// needs two wait states: the other reduction's instruction is one, s_nop 1 more than the other). Lanes without a
+// valid source keep their value. Results from lane 63. EXEC must be all ones.
+__device__ __forceinline__ void eu5_y_reduce(int &mn, int &mx)
+{
+#define EU5_RED2(ctrl)                                       \
+  "v_min_i32_dpp %0, %0, %0 " ctrl "\n\t"                    \
+  "v_max_i32_dpp %1, %1, %1 " ctrl "\n\t"                    \
+  "s_nop 1\n\t"
+  asm("s_nop 1\n\t"
+      EU5_RED2("row_shr:1 row_mask:0xf bank_mask:0xf")
+      EU5_RED2("row_shr:2 row_mask:0xf bank_mask:0xf")
+      EU5_RED2("row_shr:4 row_mask:0xf bank_mask:0xf")
+      EU5_RED2("row_shr:8 row_mask:0xf bank_mask:0xf")
+      EU5_RED2("row_bcast:15 row_mask:0xa bank_mask:0xf")
+      EU5_RED2("row_bcast:31 row_mask:0xc bank_mask:0xf")
+      : "+v"(mn), "+v"(mx));
+#undef EU5_RED2
+  mn = __builtin_amdgcn_readlane(mn, 63); mx = __builtin_amdgcn_readlane(mx, 63);
+}
+
+// One position of the first loop: a GROUP of 16x16 tiles (eu_share_groups.h) - the leader (double row m0, plan
+// plan0, tile column tcol) and the members the host found to have the leader's latitude per lane, bit for bit: the
+// same 16 rows of another cube face, the column mirror (tile column tiles16 - 1 - tcol, the lane's columns
+// W-1-xa and W-2-xa: the lane keeps its iy / ty, and takes the column entries from there).
+//   coordinate stage, once: ry, the two latitude chains, md_to_spline y, gate, split -> four iy, four ty, the lanes
+//     off the fast path, the box's y extent (one reduction of two values);
+//   member stage, per member: the column entries (ix, the x weights) of the member's plan, the box's x extent from
+//     the plan's table (w.xtab: no reduction), fit and gate tests, staging, y weights, taps, stores. A member
+//     that cannot be rendered this way goes to the work list ALONE (the +-180 degree seam is in one face only).
+// T: the leader's table values, requested by the PREVIOUS position ahead of its last stores. T is dead once a
+// member's sums are complete: the next member's column entries - behind the last member the next leader's values
+// (have_n, m_n, plan_n, tcol_n) - are requested into T itself ahead of the member's last stores. vmcnt counts in
+// issue order: loads requested behind stores cannot be waited for without waiting for the stores' acknowledgement
+// (1-2k cycles at the head of every tile).
 template <int NCH, int DEG>
-__device__ __forceinline__ bool eu5_tile16h(const eu_render_params &p, const eu4_plan &w, const float *atab,
-                                            float *wtile, const eu5_tab16 &T, int tile_y, int x0, int lane,
-                                            bool have_n, const float *ct_n, int ty_n, int x0_n, eu5_tab16 &Tn)
+__device__ __forceinline__ void eu5_group16(const eu_render_params &p, const eu4_plan &w, const float *atab, float *wtile,
+                                            eu5_tab16 &T, eu5_cint ent, int n, int m0, int plan0, int tcol, int lane0,
+                                            bool have_n, int m_n, int plan_n, int tcol_n)
 {
   constexpr int order = DEG + 1;
   const eu_src_dev &s = p.src;
 #ifdef EU5_STAMPS
-  unsigned long long st_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+  // (the low halves of the stamps, and none between a member's staging and its last stores: with more of them the
+  // member stage spills, and the stamps measure the spills)
+  unsigned st_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 #endif
-  EU5_STAMP(0);
-  const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
-  const int yA = p.row_begin + tile_y * EU4_TH + rw, yB = yA + EU4_TH;
-  const bool yinA = yA < p.row_end, yinB = yB < p.row_end;
-  const int ycA = yinA ? yA : p.row_end - 1, ycB = yinB ? yB : p.row_end - 1;
-  const int xa = x0 + 8 * hf + 2 * pr, xb = xa + 1;
-  const bool vxa = xa < p.width, vxb = xb < p.width;
-  const eu4_f4 a0 = T.a0, a1 = T.a1, b0 = T.b0, b1 = T.b1;
-  const eu_f2 c0 = T.c0;
-  const eu_f2 ryA = T.B1A * c0 + T.A1A, ryB = T.B1B * c0 + T.A1B;
-  const int ixa = __float_as_int(a0.x), ixb = __float_as_int(b0.x);
-  eu_f2 wx[order];
-  const eu_f2 tx = { a0.y, b0.y };
-  if constexpr (DEG >= 2) {
-    wx[0] = (eu_f2){ a0.z, b0.z }; wx[1] = (eu_f2){ a0.w, b0.w }; wx[2] = (eu_f2){ a1.x, b1.x };
-    if constexpr (DEG == 3) wx[3] = (eu_f2){ a1.y, b1.y };
-  }
-  const eu_f2 qs = { a1.z, b1.z };
-  eu_i2 bigA = { 0, 0 }, bigB = { 0, 0 };
-  // a lane is off the fast path when a column entry is, or an operand leaves the range of the FMA sequences
-  int bad = ((ixa != INT_MIN && ixb != INT_MIN) ? 0 : -1) |
-            eu5_out_of_range3(ryA.x, qs.x, ryB.x) | eu5_out_of_range3(ryA.y, qs.y, ryB.y);
-  const eu_f2 latA = eu_atan2f_2_lean(ryA, qs, atab, 1, bigA);
-  const eu_f2 latB = eu_atan2f_2_lean(ryB, qs, atab, 1, bigB);
-  bad |= bigA.x | bigA.y | bigB.x | bigB.y;
-  // source_t::md_to_spline, y (environment.h:988-1006)
-  const float rr = s.cdiv_ok ? 0.0f : eu_rcp_refined(s.ext_h);
-  eu_f2 iA = { (float)((double)latA.x - s.tex_y0), (float)((double)latA.y - s.tex_y0) };
-  eu_f2 iB = { (float)((double)latB.x - s.tex_y0), (float)((double)latB.y - s.tex_y0) };
-  if (s.cdiv_ok) { iA = eu_div2_const(iA, s.ext_h, s.rcp_ext_h); iB = eu_div2_const(iB, s.ext_h, s.rcp_ext_h); }
-  else { iA = eu_div2_rr(iA, s.ext_h, rr); iB = eu_div2_rr(iB, s.ext_h, rr); }
-  iA = iA * s.total_h; iA = iA - .5f; iB = iB * s.total_h; iB = iB - .5f;
-  const eu_f2 gyA = eu5_gate2(iA - s.win_y_off, s.gate1, s.lower1, s.upper1);
-  const eu_f2 gyB = eu5_gate2(iB - s.win_y_off, s.gate1, s.lower1, s.upper1);
-  eu_f2 fyA, fyB;
-  if constexpr (DEG & 1) { fyA = (eu_f2){ floorf(gyA.x), floorf(gyA.y) }; fyB = (eu_f2){ floorf(gyB.x), floorf(gyB.y) }; }
-  else { fyA = (eu_f2){ roundf(gyA.x), roundf(gyA.y) }; fyB = (eu_f2){ roundf(gyB.x), roundf(gyB.y) }; }
-  const eu_f2 tyA = gyA - fyA, tyB = gyB - fyB;
-  const int iyAa = (int)fyA.x, iyAb = (int)fyA.y, iyBa = (int)fyB.x, iyBb = (int)fyB.y;
-  // every ray hits (FAST): a pixel counts when it lies inside the frame
-  const bool hAa = yinA && vxa, hAb = yinA && vxb, hBa = yinB && vxa, hBb = yinB && vxb;
-
+  EU5_STAMP32(0);
+  // the leader's x extent (scalar cache; needed behind the coordinate stage)
+  const eu5_cint xt = (eu5_cint)w.xtab;
+  int xmn = xt[2 * (plan0 * w.tiles16 + tcol)], xmx = xt[2 * (plan0 * w.tiles16 + tcol) + 1];
+  // ---- coordinate stage ---------------------------------------------------------------------------------------
+  int iyAa, iyAb, iyBa, iyBb, bad, mny = INT_MAX, mxy = INT_MIN;
+  eu_f2 tyA, tyB;
+  bool off;
+  {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
+    const int yA = p.row_begin + 2 * m0 * EU4_TH + rw, yB = yA + EU4_TH;
+    const bool yinA = yA < p.row_end, yinB = yB < p.row_end;
+    const int xa = tcol * EU4_TW + 8 * hf + 2 * pr, xb = xa + 1;
+    const bool vxa = xa < p.width, vxb = xb < p.width;
+    const eu_f2 c0 = T.c0;
+    const eu_f2 ryA = T.B1A * c0 + T.A1A, ryB = T.B1B * c0 + T.A1B;
+    const eu_f2 qs = { T.a1.z, T.b1.z };
+    eu_i2 bigA = { 0, 0 }, bigB = { 0, 0 };
+    // a lane is off the fast path when an operand leaves the range of the FMA sequences (a column entry that is:
+    // the sentinel of w.xtab, per member)
+    bad = eu5_out_of_range3(ryA.x, qs.x, ryB.x) | eu5_out_of_range3(ryA.y, qs.y, ryB.y);
+    const eu_f2 latA = eu_atan2f_2_lean(ryA, qs, atab, 1, bigA);
+    const eu_f2 latB = eu_atan2f_2_lean(ryB, qs, atab, 1, bigB);
+    bad |= bigA.x | bigA.y | bigB.x | bigB.y;
+    // source_t::md_to_spline, y (environment.h:988-1006)
+    // (uniform values a vector instruction computes are handed on as scalars: kept in vector registers across the
+    // loops they are spilled to scratch memory, and every reload is a wait behind the stores)
+    const float rr = s.cdiv_ok ? 0.0f : __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eu_rcp_refined(s.ext_h))));
+    eu_f2 iA = { (float)((double)latA.x - s.tex_y0), (float)((double)latA.y - s.tex_y0) };
+    eu_f2 iB = { (float)((double)latB.x - s.tex_y0), (float)((double)latB.y - s.tex_y0) };
+    if (s.cdiv_ok) { iA = eu_div2_const(iA, s.ext_h, s.rcp_ext_h); iB = eu_div2_const(iB, s.ext_h, s.rcp_ext_h); }
+    else { iA = eu_div2_rr(iA, s.ext_h, rr); iB = eu_div2_rr(iB, s.ext_h, rr); }
+    iA = iA * s.total_h; iA = iA - .5f; iB = iB * s.total_h; iB = iB - .5f;
+    const eu_f2 gyA = eu5_gate2(iA - s.win_y_off, s.gate1, s.lower1, s.upper1);
+    const eu_f2 gyB = eu5_gate2(iB - s.win_y_off, s.gate1, s.lower1, s.upper1);
+    eu_f2 fyA, fyB;
+    if constexpr (DEG & 1) { fyA = (eu_f2){ floorf(gyA.x), floorf(gyA.y) }; fyB = (eu_f2){ floorf(gyB.x), floorf(gyB.y) }; }
+    else { fyA = (eu_f2){ roundf(gyA.x), roundf(gyA.y) }; fyB = (eu_f2){ roundf(gyB.x), roundf(gyB.y) }; }
+    tyA = gyA - fyA; tyB = gyB - fyB;
+    iyAa = (int)fyA.x; iyAb = (int)fyA.y; iyBa = (int)fyB.x; iyBb = (int)fyB.y;
 #ifdef EU5_STAMPS
-  asm volatile("" : : "v"(iyAa), "v"(iyAb), "v"(iyBa), "v"(iyBb));
+    asm volatile("" : : "v"(iyAa), "v"(iyAb), "v"(iyBa), "v"(iyBb));
 #endif
-  EU5_STAMP(2);
-  // the tile's box
-  int q0 = INT_MAX, q1 = INT_MAX, q2 = INT_MIN, q3 = INT_MIN, h0, h1, h2, h3;
-  if (hAa) { q0 = ixa; q2 = ixa; q1 = iyAa; q3 = iyAa; }
-  if (hAb) { q0 = min(q0, ixb); q2 = max(q2, ixb); q1 = min(q1, iyAb); q3 = max(q3, iyAb); }
-  if (hBa) { q0 = min(q0, ixa); q2 = max(q2, ixa); q1 = min(q1, iyBa); q3 = max(q3, iyBa); }
-  if (hBb) { q0 = min(q0, ixb); q2 = max(q2, ixb); q1 = min(q1, iyBb); q3 = max(q3, iyBb); }
-  eu5_box_reduce(q0, q1, q2, q3, h0, h1, h2, h3);
-  eu5_box bx = eu5_box_join(eu5_box_at(h0, h1, h2, h3, 31), eu5_box_at(h0, h1, h2, h3, 63));
-  bool fast = __ballot(bad != 0 && (hAa || hAb || hBa || hBb)) == 0ull;
-  if (bx.mnx != INT_MAX) {
-    const int cw = (int)(s.upper0 + 0.5f), ch = (int)(s.upper1 + 0.5f);
-    if (s.gate0 == 2 && bx.mnx < 0) fast = false;
-    if (s.gate0 != 0 && bx.mxx >= cw - 1) fast = false;
-    if (s.gate1 == 2 && bx.mny < 0) fast = false;
-    if (s.gate1 != 0 && bx.mxy >= ch - 1) fast = false;
-    if (eu5_box_fits<order>(bx) != 1) fast = false;
+    EU5_STAMP32(2);
+    // every ray hits (FAST): a pixel counts when it lies inside the frame. The y extent of those of the leader -
+    // a member with followers has all its rows inside the frame, and its followers have the same columns inside
+    const bool hAa = yinA && vxa, hAb = yinA && vxb, hBa = yinB && vxa, hBb = yinB && vxb;
+    int q1 = INT_MAX, q3 = INT_MIN;
+    if (hAa) { q1 = iyAa; q3 = iyAa; }
+    if (hAb) { q1 = min(q1, iyAb); q3 = max(q3, iyAb); }
+    if (hBa) { q1 = min(q1, iyBa); q3 = max(q3, iyBa); }
+    if (hBb) { q1 = min(q1, iyBb); q3 = max(q3, iyBb); }
+    eu5_y_reduce(q1, q3);
+    mny = q1; mxy = q3;
+    off = __ballot(bad != 0 && (hAa || hAb || hBa || hBb)) != 0ull;
   }
-  if (bx.mnx == INT_MAX || !fast) {
-    if (have_n) eu5_load16(p, ct_n, ty_n, x0_n, lane, Tn);
-    return bx.mnx == INT_MAX;                                // nothing inside the frame: done; else: not this way
-  }
-  bx.mnx = __builtin_amdgcn_readfirstlane(bx.mnx); bx.mny = __builtin_amdgcn_readfirstlane(bx.mny);
-  bx.mxx = __builtin_amdgcn_readfirstlane(bx.mxx); bx.mxy = __builtin_amdgcn_readfirstlane(bx.mxy);
-  const unsigned lds_tile = (unsigned)(unsigned long long)(eu4_lds_void)wtile;
-  EU5_STAMP(3);
-  eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
-  // the y weights of both pairs, behind the DMA issue
-  eu_f2 wyA[order], wyB[order];
-  if constexpr (DEG >= 2) { eu_weights2<DEG>(s.wm, tyA, wyA); eu_weights2<DEG>(s.wm, tyB, wyB); }
-  const int ibw = bx.mxx - bx.mnx + order;
-  const int oAa = hAa ? ((iyAa - bx.mny) * ibw + (ixa - bx.mnx)) * 4 : 0, oAb = hAb ? ((iyAb - bx.mny) * ibw + (ixb - bx.mnx)) * 4 : 0;
-  const int oBa = hBa ? ((iyBa - bx.mny) * ibw + (ixa - bx.mnx)) * 4 : 0, oBb = hBb ? ((iyBb - bx.mny) * ibw + (ixb - bx.mnx)) * 4 : 0;
-  EU5_STAMP(4);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  EU5_STAMP(5);
-  __builtin_amdgcn_sched_barrier(0);
-  eu_f2 rga, bxa, rgb, bxb;
-  eu5_taps<NCH, DEG>((eu_lptr)wtile, oAa, oAb, ibw * 4, wx, wyA, tx, tyA, rga, bxa, rgb, bxb);
-  // (the sums are complete here, whatever the stores' conditions: keeps the evaluation out of the
-  // conditional blocks and the window reads 16 bytes wide)
-  asm volatile("" : "+v"(rga), "+v"(bxa), "+v"(rgb), "+v"(bxb));
-  {
-    float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
-    float *const orow = p.out + (long long)(ycA - p.row_begin) * p.out_stride;
-    if (hAa) eu_put<NCH>(orow, xa, qa);
-    if (hAb) eu_put<NCH>(orow, xb, qb);
-  }
-  // one pair after the other: interleaved, the two sets of windows do not fit the registers
-  EU5_STAMP(6);
-  __builtin_amdgcn_sched_barrier(0);
-  eu5_taps<NCH, DEG>((eu_lptr)wtile, oBa, oBb, ibw * 4, wx, wyB, tx, tyB, rga, bxa, rgb, bxb);
-  asm volatile("" : "+v"(rga), "+v"(bxa), "+v"(rgb), "+v"(bxb));
-  if (have_n) eu5_load16(p, ct_n, ty_n, x0_n, lane, Tn);
-  __builtin_amdgcn_sched_barrier(0);
-  {
-    float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
-    float *const orow = p.out + (long long)(ycB - p.row_begin) * p.out_stride;
-    if (hBa) eu_put<NCH>(orow, xa, qa);
-    if (hBb) eu_put<NCH>(orow, xb, qb);
-  }
-  EU5_STAMP(7);
+  EU5_STAMP32(3);
+  // ---- member stage -------------------------------------------------------------------------------------------
+  int mk = m0, pk = plan0;
+#pragma unroll 1
+  for (int k = 0; k < n; k++) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
+    const bool mir = (pk & EU_SHARE_MIRROR) != 0;
+    const int tc = mir ? w.tiles16 - 1 - tcol : tcol;
+    // the next member's record (scalar cache), requested a member ahead
+    int mk_n = 0, pk_n = 0;
+    if (k + 1 < n) { mk_n = ent[2 * k + 4]; pk_n = ent[2 * k + 5]; }
 #ifdef EU5_STAMPS
-  if (lane == 0 && w.stamps) {
-    unsigned long long *o = w.stamps + ((size_t)tile_y * w.tiles16 + x0 / EU4_TW) * 8;
-    st_[1] = 6ull | 16ull;      // class: hoist 1, "npass 5" = a 16x16 tile (taps column: pair A only, store column: pair B + stores)
+    if (k > 0) { EU5_STAMP32(0); st_[2] = st_[0]; st_[3] = st_[0]; }
+#endif
+    eu5_box bx = { xmn, mny, xmx, mxy };
+    bool fast = !off && xmn != INT_MAX && mny != INT_MAX;
+    if (fast) {
+      const int cw = __builtin_amdgcn_readfirstlane((int)(s.upper0 + 0.5f)), ch = __builtin_amdgcn_readfirstlane((int)(s.upper1 + 0.5f));
+      if (s.gate0 == 2 && bx.mnx < 0) fast = false;
+      if (s.gate0 != 0 && bx.mxx >= cw - 1) fast = false;
+      if (s.gate1 == 2 && bx.mny < 0) fast = false;
+      if (s.gate1 != 0 && bx.mxy >= ch - 1) fast = false;
+      if (eu5_box_fits<order>(bx) != 1) fast = false;
+    }
+    const int xl = 8 * hf + 2 * pr;
+    const int xa = mir ? p.width - 1 - (tcol * EU4_TW + xl) : tc * EU4_TW + xl, xb = mir ? xa - 1 : xa + 1;
+    const int yA = p.row_begin + 2 * mk * EU4_TH + rw, yB = yA + EU4_TH;
+    const bool yinA = yA < p.row_end, yinB = yB < p.row_end;
+    const int ycA = yinA ? yA : p.row_end - 1, ycB = yinB ? yB : p.row_end - 1;
+    const bool vxa = xa < p.width, vxb = xb < p.width;
+    const bool hAa = yinA && vxa, hAb = yinA && vxb, hBa = yinB && vxa, hBb = yinB && vxb;
+    eu_f2 rga = { 0.0f, 0.0f }, bxa = { 0.0f, 0.0f }, rgb = { 0.0f, 0.0f }, bxb = { 0.0f, 0.0f };
+    if (fast) eu5_stage<NCH, DEG>(s, bx, (unsigned)(unsigned long long)(eu4_lds_void)wtile, lane);
+    // the next member's x extent, requested under this member's staging (its record has arrived by now)
+    const bool mir_n = (pk_n & EU_SHARE_MIRROR) != 0;
+    const int plan_k = pk_n & (EU_SHARE_MIRROR - 1);
+    const int tc_k = mir_n ? w.tiles16 - 1 - tcol : tcol;
+    int xmn_n = INT_MAX, xmx_n = INT_MIN;
+    if (k + 1 < n) { xmn_n = xt[2 * (plan_k * w.tiles16 + tc_k)]; xmx_n = xt[2 * (plan_k * w.tiles16 + tc_k) + 1]; }
+    if (fast) {
+      // the y weights of both pairs, behind the DMA issue (per member: kept across the members they cost 16 registers)
+      eu_f2 wx[order], wyA[order], wyB[order];
+      const int ixa = __float_as_int(T.a0.x), ixb = __float_as_int(T.b0.x);
+      const eu_f2 tx = { T.a0.y, T.b0.y };
+      if constexpr (DEG >= 2) {
+        wx[0] = (eu_f2){ T.a0.z, T.b0.z }; wx[1] = (eu_f2){ T.a0.w, T.b0.w }; wx[2] = (eu_f2){ T.a1.x, T.b1.x };
+        if constexpr (DEG == 3) wx[3] = (eu_f2){ T.a1.y, T.b1.y };
+        eu_weights2<DEG>(s.wm, tyA, wyA); eu_weights2<DEG>(s.wm, tyB, wyB);
+      }
+      const int ibw = bx.mxx - bx.mnx + order;
+      const int oAa = hAa ? ((iyAa - bx.mny) * ibw + (ixa - bx.mnx)) * 4 : 0, oAb = hAb ? ((iyAb - bx.mny) * ibw + (ixb - bx.mnx)) * 4 : 0;
+      const int oBa = hBa ? ((iyBa - bx.mny) * ibw + (ixa - bx.mnx)) * 4 : 0, oBb = hBb ? ((iyBb - bx.mny) * ibw + (ixb - bx.mnx)) * 4 : 0;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      eu5_taps<NCH, DEG>((eu_lptr)wtile, oAa, oAb, ibw * 4, wx, wyA, tx, tyA, rga, bxa, rgb, bxb);
+      // (the sums are complete here, whatever the stores' conditions: keeps the evaluation out of the
+      // conditional blocks and the window reads 16 bytes wide)
+      asm volatile("" : "+v"(rga), "+v"(bxa), "+v"(rgb), "+v"(bxb));
+      {
+        float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
+        float *const orow = p.out + (long long)(ycA - p.row_begin) * p.out_stride;
+        if (hAa) eu_put<NCH>(orow, xa, qa);
+        if (hAb) eu_put<NCH>(orow, xb, qb);
+      }
+      // one pair after the other: interleaved, the two sets of windows do not fit the registers
+      __builtin_amdgcn_sched_barrier(0);
+      eu5_taps<NCH, DEG>((eu_lptr)wtile, oBa, oBb, ibw * 4, wx, wyB, tx, tyB, rga, bxa, rgb, bxb);
+      asm volatile("" : "+v"(rga), "+v"(bxa), "+v"(rgb), "+v"(bxb));
+    } else if (mny != INT_MAX) {
+      // both 16x8 tiles to the direct-gather kernel (a rare event: the +-180 degree seam, a box beyond the slice)
+      if (lane < 2) {
+        const int id = (2 * mk + lane) * w.tiles16 + tc;
+        const int sh = eu4_shard_of(id);
+        const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
+        p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
+      }
+    }
+    // what comes next, ahead of the stores
+    if (k + 1 < n) {
+      const int xa_n = mir_n ? p.width - 1 - (tcol * EU4_TW + xl) : tcol * EU4_TW + xl, xb_n = mir_n ? xa_n - 1 : xa_n + 1;
+      // (a group has followers only where every column lies inside the frame or the mirror is off: clamp as eu5_load16 does)
+      const int xac = xa_n < p.width ? xa_n : p.width - 1, xbc = xb_n < p.width ? xb_n : p.width - 1;
+      eu5_load_cols(w.coltab + (size_t)plan_k * p.width * EU4_COL_FLOATS, xac, xbc, T);
+    } else if (have_n) {
+      eu5_load16(p, w.coltab + (size_t)plan_n * p.width * EU4_COL_FLOATS, 2 * m_n, tcol_n * EU4_TW, lane, T);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (fast) {
+      float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
+      float *const orow = p.out + (long long)(ycB - p.row_begin) * p.out_stride;
+      if (hBa) eu_put<NCH>(orow, xa, qa);
+      if (hBb) eu_put<NCH>(orow, xb, qb);
+    }
+    EU5_STAMP32(7);
+#ifdef EU5_STAMPS
+    if (fast && lane == 0 && w.stamps) {
+      unsigned long long *o = w.stamps + ((size_t)(2 * mk) * w.tiles16 + tc) * 8;
+      // class: hoist 1, "npass 5" = the leader of a group, "npass 6" = a follower (no coordinate stage, no box)
+      st_[1] = (k == 0 ? 6ull : 7ull) | 16ull;
 #pragma unroll
-    for (int k = 0; k < 8; k++) o[k] = st_[k];
-  }
+      for (int q = 0; q < 8; q++) o[q] = q == 1 ? st_[1] : (q == 4 || q == 5) ? 0ull : (unsigned long long)st_[q == 6 ? 7 : q] | (1ull << 32);
+    }
 #endif
-  return true;
+    mk = mk_n; pk = pk_n; xmn = xmn_n; xmx = xmx_n;
+  }
 }
 
 // the tiles of one wave: XCD x owns the units x, x + 8, ... of UNIT tile rows (of RPT 16x8 tile rows each);
@@ -737,7 +829,6 @@ struct eu5_iter {
 // tile rows 2m and 2m + 1 form a 16x16 row of the first loop when both have the same column plan
 // (the plan table is read through the scalar cache: as a vector load its wait - vmcnt counts in issue order -
 // is also a wait for the stores of the tile just finished, 1-2k cycles per iteration)
-typedef const __attribute__((address_space(4))) int *eu5_cint;
 __device__ __forceinline__ int eu5_pair_plan(const int *tileplan, int tiles_y, int m)
 {
   if (2 * m + 1 >= tiles_y) return -1;
@@ -778,57 +869,34 @@ __global__ __launch_bounds__(64 * EU5_WAVES, EU5_OCC) void eu_render5_kernel(con
   // waits for the plan of the tile it is about to start (measured: 1.6-2.3k cycles per iteration outside
   // the tiles, a quarter of a wave's life).
   if constexpr (PAIRS) {
-    // first the pairs of tile rows with a common column plan, as 16x16 tiles: position i of the XCD's list
-    // (w.l1_rows: built on the host with the plans, so that no position is looked at only to be skipped) is
-    // column i % tiles16 - rotated by the row, see eu5_iter::col - of double row l1_rows[i / tiles16]
-    const int n1 = (w.l1_off[xcd + 1] - w.l1_off[xcd]) * w.tiles16;
-    const eu5_cint rows1 = (eu5_cint)w.l1_rows + 2 * w.l1_off[xcd];
+    // first the pairs of tile rows with a common column plan, as 16x16 tiles: position i of the XCD's list of
+    // groups (w.l1_ent: built on the host with the plans, eu_share_groups.h) is column i % l1_ecols - rotated by
+    // the row, see eu5_iter::col - of entry i / l1_ecols; a position renders every member of its group
+    const int n1 = (w.l1_off[xcd + 1] - w.l1_off[xcd]) * w.l1_ecols;
+    const eu5_cint ents = (eu5_cint)w.l1_ent + EU_SHARE_ENTRY_INTS * w.l1_off[xcd];
     int pos1 = t0;
-    auto seek = [&](int &m, int &tcol, int &plan) -> bool {
+    auto seek = [&](eu5_cint &e, int &n, int &m, int &plan, int &tcol) -> bool {
       if (pos1 >= n1) return false;
-      const int r = (int)(((unsigned long long)(unsigned)pos1 * w.l1_magic) >> 40);     // pos1 / tiles16
-      m = rows1[2 * r]; plan = rows1[2 * r + 1];
+      const int r = (int)(((unsigned long long)(unsigned)pos1 * w.l1_magic) >> 40);     // pos1 / l1_ecols
+      e = ents + EU_SHARE_ENTRY_INTS * r;
+      n = e[0]; m = e[2]; plan = e[3];
       const unsigned h = ((unsigned)m * 0x9E3779B1u) >> 16;
-      int c = pos1 - r * w.tiles16 + (int)((h * (unsigned)w.tiles16) >> 16);
-      if (c >= w.tiles16) c -= w.tiles16;
-      tcol = c;
+      int c = pos1 - r * w.l1_ecols + (int)((h * (unsigned)w.l1_ecols) >> 16);
+      if (c >= w.l1_ecols) c -= w.l1_ecols;
+      tcol = e[1] + c;
       pos1 += K;
       return true;
     };
-    // two copies of the body, the table values alternating between Ta and Tb: handing them from "next" to
-    // "current" by assignment is a use, and a use is a wait for the loads that have just been requested
-    int m_a = 0, col_a = 0, plan_a = -1, m_b = 0, col_b = 0, plan_b = -1;
-    bool have_a = seek(m_a, col_a, plan_a), have_b = false;
-    eu5_tab16 Ta, Tb;
-    if (have_a) eu5_load16(p, w.coltab + (size_t)plan_a * p.width * EU4_COL_FLOATS, 2 * m_a, col_a * EU4_TW, lane0, Ta);
-    auto fallback = [&](int m, int tcol, int lane) {
-      // both 16x8 tiles to the direct-gather kernel (a rare event: the +-180 degree seam, a box beyond the slice)
-      if (lane < 2) {
-        const int id = (2 * m + lane) * w.tiles16 + tcol;
-        const int sh = eu4_shard_of(id);
-        const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
-        p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
-      }
-    };
+    eu5_cint e_a = ents, e_n = ents;
+    int n_a = 0, m_a = 0, col_a = 0, plan_a = 0, n_n = 0, m_n = 0, col_n = 0, plan_n = 0;
+    bool have_a = seek(e_a, n_a, m_a, plan_a, col_a);
+    eu5_tab16 T;
+    if (have_a) eu5_load16(p, w.coltab + (size_t)plan_a * p.width * EU4_COL_FLOATS, 2 * m_a, col_a * EU4_TW, lane0, T);
 #pragma unroll 1
     while (have_a) {
-      {
-        have_b = seek(m_b, col_b, plan_b);
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        const float *ct_n = w.coltab + (size_t)(have_b ? plan_b : 0) * p.width * EU4_COL_FLOATS;
-        if (!eu5_tile16h<NCH, DEG>(p, w, atab, tile, Ta, 2 * m_a, col_a * EU4_TW, lane, have_b, ct_n, 2 * m_b, col_b * EU4_TW, Tb))
-          fallback(m_a, col_a, lane);
-      }
-      if (!have_b) break;
-      {
-        have_a = seek(m_a, col_a, plan_a);
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        const float *ct_n = w.coltab + (size_t)(have_a ? plan_a : 0) * p.width * EU4_COL_FLOATS;
-        if (!eu5_tile16h<NCH, DEG>(p, w, atab, tile, Tb, 2 * m_b, col_b * EU4_TW, lane, have_a, ct_n, 2 * m_a, col_a * EU4_TW, Ta))
-          fallback(m_b, col_b, lane);
-      }
+      const bool have_n = seek(e_n, n_n, m_n, plan_n, col_n);
+      eu5_group16<NCH, DEG>(p, w, atab, tile, T, e_a, n_a, m_a, plan_a, col_a, lane0, have_n, m_n, have_n ? plan_n : 0, col_n);
+      e_a = e_n; n_a = n_n; m_a = m_n; plan_a = plan_n; col_a = col_n; have_a = have_n;
     }
   }
 #ifdef EU5_STAMPS

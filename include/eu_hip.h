@@ -156,6 +156,11 @@ int  eu_hip_layout_segments(const eu_target *trg, eu_source *const *srcs, int ns
 /* render kernel launches issued so far by this process (single-facet path) */
 unsigned long long eu_hip_launch_count(void);
 
+/* 16x16 tiles that the last staged launch (eu_render5_kernel's first loop) rendered from the
+ * coordinates of another tile - the column mirror, the same rows of another cube face; 0 where
+ * the tables the kernel reads do not agree bit for bit, and under EU_HIP_SHARE=0 */
+unsigned long long eu_hip_share_follower_tiles(void);
+
 /* number of local rows of part band_index (see eu_target.band_*) in a frame of
  * `height` rows; height itself when band_count <= 1 */
 int  eu_hip_band_rows(int height, int band_rows, int band_count, int band_index);

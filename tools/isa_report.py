@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""profiles/r03_headline_isa.txt: what the shipped headline kernel is made of. Compiles eu_render4.hip (which
+"""profiles/shared_rows_headline_isa.txt (r03_headline_isa.txt: the kernel before the first loop rendered groups): what the
+shipped headline kernel is made of. Compiles eu_render4.hip (which
 includes eu_render5.h) with -save-temps, takes eu_render5_kernel<3,3,SPHERICAL,FAST> out of the ISA listing and
-reports the code-object metadata, the instruction mix (whole kernel and per stage of the 16x16 tile, cut at the
-stage's first characteristic instruction), and - from the PMC record in profiles/ - the executed counts per tile.
-usage: python tools/isa_report.py > profiles/r03_headline_isa.txt"""
+reports the code-object metadata, the instruction mix (whole kernel and per stage of the first loop's group of 16x16
+tiles - the coordinate stage, once per group, and the member stage - cut at the stage's first characteristic instruction), and - from the PMC record in profiles/ - the executed counts per tile.
+usage: python tools/isa_report.py > profiles/shared_rows_headline_isa.txt"""
 import collections, os, re, subprocess, sys, tempfile, json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,33 +44,38 @@ print("## code-object metadata")
 for m in meta + occ: print("  ", m)
 print("   waves per SIMD by registers: 512 / 128 = 4 (launch bounds 256 x 4); workgroups per CU by LDS: 163840 / 39936 = 4 -> 16 waves per CU")
 tot = collections.Counter(cls(op) for _, op in ins)
-print(f"## static instruction mix of the whole kernel ({len(ins)} instructions: two loops, two copies of each tile body)")
+print(f"## static instruction mix of the whole kernel ({len(ins)} instructions: two loops, one copy of the first loop's body, two of the second's)")
 for k, v in tot.most_common(): print(f"   {v:6d}  {k}")
-# the first copy of the 16x16 tile: from the loop head's column-table use to its last store
+# the first loop's body: the coordinate stage of a group (up to the y reduction, the only DPP block of that loop),
+# then the member stage (a loop over the group's members) from its head to its last store
 first_dpp = next(i for i, (_, op) in enumerate(ins) if "_dpp" in op)
+last_dpp = first_dpp
+while "_dpp" in ins[last_dpp + 1][1] or ins[last_dpp + 1][1].startswith("s_nop"): last_dpp += 1
 stores = [i for i, (_, op) in enumerate(ins) if op.startswith("global_store")]
 dmas = [i for i, (_, op) in enumerate(ins) if op.startswith("global_load_lds")]
 dsr = [i for i, (_, op) in enumerate(ins) if op.startswith("ds_read_b128")]
 end16 = next(i for i in stores if i > first_dpp and sum(1 for j in stores if first_dpp < j <= i) == 4)
 tile_dma = [i for i in dmas if i > first_dpp][:2]
 taps0 = next(i for i in dsr if i > tile_dma[-1])
-# head of the tile body: walk back from the DPP block to the previous store / loop label
-prev_store = max([i for i in stores if i < first_dpp] + [0])
-stages = [("coordinates (table values -> ray y, two latitude chains, md_to_spline, gate, split)", prev_store, first_dpp),
-          ("box (DPP reduction, lane reads, scalar fit / gate tests)", first_dpp, tile_dma[0]),
-          ("LDS-DMA issue + y weights of both pairs + window addresses", tile_dma[0], taps0),
-          ("taps of both pairs (32 + 32 ds_read_b128, 2 x 140 packed operations), next tile's table loads, stores", taps0, end16 + 1)]
-print("## first copy of the 16x16 tile body (256 pixels per wave), instructions between stage markers [static; the rare branches")
-print("##   (work-list exit, unaligned tails of the DMA loop) are inside the ranges, the DMA loop body counts once]")
+# head of the loop body: walk back from the DPP block to the loop's first table-value use (behind the kernel's prologue)
+head = max([i for i, (_, op) in enumerate(ins) if op.startswith("global_load_dword") and i < first_dpp] + [0])
+stages = [("coordinate stage, ONCE PER GROUP (table values -> ray y, two latitude chains, md_to_spline, gate, split, y extent: one DPP reduction of two values)", head, last_dpp + 1),
+          ("member stage: the group's ballot and lane reads, then per member the x extent from the plan's table, scalar fit / gate tests", last_dpp + 1, tile_dma[0]),
+          ("member stage: LDS-DMA issue + y weights of both pairs + window addresses", tile_dma[0], taps0),
+          ("member stage: taps of both pairs (32 + 32 ds_read_b128, 2 x 140 packed operations), the next member's column entries / the next leader's table values, stores", taps0, end16 + 1)]
+print("## the first loop's body (a group of 16x16 tiles, 256 pixels per wave each), instructions between stage markers [static; the rare")
+print("##   branches (work-list exit, unaligned tails of the DMA loop) are inside the ranges, the DMA loop body counts once]")
 tsum = collections.Counter()
+per_stage = []
 for name, a, b in stages:
     c = collections.Counter(cls(op) for _, op in ins[a:b])
     valu = sum(v for k, v in c.items() if k.startswith("VALU"))
     tsum.update(c)
+    per_stage.append(valu)
     print(f"   {name}\n      VALU {valu} (packed {c['VALU packed fp32 (v_pk_*)']}, moves {c['VALU moves']}, lane<->scalar {c['VALU lane<->scalar (incl. SGPR spills)']}, DPP {c['VALU DPP']}, f64/cvt {c['VALU f64 / conversions']}, trans {c['VALU transcendental']}), "
           f"SALU {c['SALU other']}, LDS {c['LDS']}, LDS-DMA {c['LDS-DMA']}, vmem {c['vector memory']}, waitcnt {c['s_waitcnt']}, nop {c['s_nop']}, branches {c['branches']}")
-valu_tile = sum(v for k, v in tsum.items() if k.startswith("VALU"))
-print(f"   total VALU of the tile body: {valu_tile} per 256 pixels = {valu_tile / 2:.0f} per 128 pixels")
+coord, member = per_stage[0], sum(per_stage[1:])
+print(f"   VALU per tile: a single {coord + member}, in a group of 2 {coord / 2 + member:.0f}, of 4 {coord / 4 + member:.0f}, of 8 {coord / 8 + member:.0f} (880 before the groups)")
 # longest dependent chain: the latitude chain (atan2f with x > 0) between the table values and the base position
 print("## longest dependent chain per pixel (operations that each need the previous one's result; eu_math2.h):")
 print("   ray y 2 | range test 3 | division y/x: rcp + 7 = 8 | table index 3 + LDS round trip | num/den 3 | division 8 | z, w 2 |")
@@ -78,8 +84,9 @@ print("   FMA division by the extent 5 | * total, - .5, - offset 3 | gate 2 | fl
 print("   ~50 of them packed (8 cycles each from one wave): ~450 cycles; a 16x16 tile runs two such chains side by side (pairs A, B)")
 try:
     t = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))["workloads"]["headline"]
-    print("## executed counts (profiles/r03_headline_kernel_stats_pmc.txt, per launch of eu_render5_kernel; 786 432 16x8-tile equivalents):")
-    for l in open(os.path.join(ROOT, "profiles", "r03_headline_kernel_stats_pmc.txt")):
+    print("## executed counts (profiles/shared_rows_headline_kernel_stats_pmc.txt, per launch of eu_render5_kernel; 786 432 16x8-tile equivalents):")
+    for l in open(os.path.join(ROOT, "profiles", "shared_rows_headline_kernel_stats_pmc.txt")):
+        if not l.startswith("new_"): continue
         if "eu_render5_kernel" in l and any(k in l for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_VALU", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "GRBM_GUI_ACTIVE", "TCP_TOTAL", "SQ_LDS_BANK", "SQ_LDS_IDX")):
             m = re.search(r"(\S+)\s+n=\s*\d+ mean=(\S+)", l)
             v = float(m.group(2))
