@@ -18,6 +18,4 @@ struct eu_alpha_params {
   const int32_t *spans;      // pairs [x0, x1) the polygons clear
 };
 
-extern "C" int eu_launch_facet_alpha(const eu_alpha_params *p, void *stream);
-
 #endif

@@ -20,6 +20,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "eu_alpha.h"
+#include "eu_launch.h"
 
 namespace {
 

@@ -16,31 +16,7 @@
 #include "eu_imageprep.h"
 #include "eu_alpha.h"
 #include "eu_math2.h"
-
-extern "C" int eu_launch_render(const eu_render_params *p, void *stream);
-extern "C" int eu_launch_diag(const eu_render_params *p, unsigned long long *stamps_dev, void *stream);
-extern "C" int eu_launch_render_multi(const void *p, int degree, void *stream);
-extern "C" int eu_launch_render2(const eu_render_params *p, void *stream);
-extern "C" int eu_launch_diag_coords(const eu_src_dev *s, const float *rays_dev, long n, int variant,
-                                     float *out_dev, void *stream);
-extern "C" int eu_launch_render4(const eu_render_params *p, const float *h_row, size_t h_row_floats,
-                                 unsigned long long plan_gen, int only_if_worth, void *stream);
-extern "C" size_t eu_render4_worklist_ints(size_t ntiles);
-extern "C" size_t eu_render4_worklist_header_ints(void);
-extern "C" int eu_launch_to_screen(const float *in, long long in_stride, unsigned *out,
-                                   long long out_stride, int w, int rows, int nch, const float *lut,
-                                   void *stream);
-
-extern "C" int eu_verify_const_div(float c, float limit, void *stream);
-extern "C" int eu_launch_selftest(unsigned long long seed, int blocks, int iters,
-                                  unsigned long long *bad_dev, void *stream);
-extern "C" int eu_launch_prefilter(float *container, const eu_container *g, int nch,
-                                   int bc0, int bc1, int prefilter_degree, int spherical,
-                                   void *stream);
-extern "C" int eu_launch_cubemap_build(const float *faces_dev, float *ir_dev, int nch,
-                                       long face_px, long section_px, long left_frame,
-                                       long right_frame, double refc_md, double model_to_px,
-                                       int prefilter_degree, void *stream);
+#include "eu_launch.h"
 
 struct eu_source {
   eu_facet fct;
@@ -66,42 +42,40 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 struct context {
   int device = -1;
   hipStream_t stream = nullptr;
-  float *col = nullptr, *row = nullptr, *taps = nullptr;
-  size_t col_cap = 0, row_cap = 0, taps_cap = 0;
+  eu_dev_buf<float> col, row, taps;
   float *lut = nullptr;        // to_screen_t's sRGB LUT, 257 floats
-  float *scr = nullptr; size_t scr_cap = 0;       // float frame of a tethered job
+  eu_dev_buf<float> scr;                          // float frame of a tethered job
   // host copies of the plan's stepper tables and, from them, the layout the packed
   // kernel should use per segment of EU_SEG_ROWS frame rows (launch-level hybrid)
   std::vector<float> h_col, h_row;
   std::vector<unsigned char> seg_flags;
-  bool seg_valid = false, seg_mixed = false;
+  bool seg_valid = false;
   unsigned long long plan_gen = 0;                // bumped whenever the stepper tables change
   int tab_finite = 0;                             // every entry of the plan's stepper tables is finite
   unsigned long long launches = 0;                // render kernel launches so far
   eu_src_dev seg_sd;
-  float *stage = nullptr; size_t stage_cap = 0;   // host-output staging
+  eu_dev_buf<float> stage;                        // host-output staging
   hipStream_t last_user = nullptr;                // caller's stream of the last render (eu_hip_sync waits on it too)
-  eu_generic *mgen = nullptr; size_t mgen_cap = 0; // multi-facet jobs: the translated facets' transformations
+  eu_dev_buf<eu_generic> mgen;                    // multi-facet jobs: the translated facets' transformations
   float *inv_coef = nullptr;                      // --single: the inverse lens model's coefficients (eu_inv_planar)
   hipEvent_t wl_done = nullptr;                   // behind the last staged launch pair (its work list is free again)
   hipStream_t wl_stream = nullptr; bool wl_stream_set = false;
   hipStream_t copy = nullptr;                     // D2H of a host-output frame, chunk by chunk
   hipEvent_t chunk_done[4] = { nullptr, nullptr, nullptr, nullptr };
-  int *wl = nullptr; size_t wl_cap = 0;           // eu_render4.hip work list (count, done, tile ids)
+  eu_dev_buf<int> wl;                             // eu_render4.hip work list (count, done, tile ids)
   // the tables of the last target stay valid while (target geometry,
   // orientation, taps) repeat: streaming / tethered jobs re-render the same
   // target many times (envutil_main.cc:1948-1982)
   std::vector<unsigned char> plan_key;
   int plan_form = 0, plan_norm = 0;
   // multi-facet jobs keep their own tables
-  float *mcol = nullptr, *mrow = nullptr, *mtaps = nullptr;
-  size_t mcol_cap = 0, mrow_cap = 0, mtaps_cap = 0;
-  eu_src_dev *msrc = nullptr; size_t msrc_cap = 0;
-  float *mrej = nullptr; size_t mrej_cap = 0;      // early-miss tables of a multi-facet job
+  eu_dev_buf<float> mcol, mrow, mtaps;
+  eu_dev_buf<eu_src_dev> msrc;
+  eu_dev_buf<float> mrej;                         // early-miss tables of a multi-facet job
   std::vector<unsigned char> mplan_key;
   int mplan_form = 0, mplan_norm = 0;
-  float *strip = nullptr; size_t strip_cap = 0;   // eu_hip_render_devices: this slot's rows before they are gathered
-  float *aplan = nullptr; size_t aplan_cap = 0;   // row plan of the last device alpha edit (int32 words)
+  eu_dev_buf<float> strip;                        // eu_hip_render_devices: this slot's rows before they are gathered
+  eu_dev_buf<int32_t> aplan;                      // row plan of the last device alpha edit
   hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
 // One context per device SLOT. A process that never calls eu_hip_init_devices has one slot (one process per
@@ -154,18 +128,6 @@ int ensure_init()
   return init_device(dev);
 }
 
-int grow(float **p, size_t *cap, size_t need)
-{
-  if (*cap >= need) return EU_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIPCHK(hipMalloc((void **)p, need * sizeof(float)));
-  *cap = need;
-  return EU_OK;
-}
-
-bool is_cube(int prj) { return prj == EU_CUBEMAP || prj == EU_BIATAN6; }
-
 // evaluator + mount parameters (eval.h:2039-2164, environment.h:594-633)
 void fill_src_dev(eu_source *s)
 {
@@ -191,9 +153,9 @@ void fill_src_dev(eu_source *s)
   d.brighten = (float)f.brighten;
   d.mask_paint = f.mask_paint;
   d.recip_step = (float)(1.0 / f.step);
-  d.mask_all = is_cube(f.projection) || (f.projection == EU_FISHEYE && f.hfov >= M_PI * 2.0);
+  d.mask_all = eu_cube_source(f.projection) || (f.projection == EU_FISHEYE && f.hfov >= M_PI * 2.0);
   eu::weight_matrix(s->degree, d.wm);
-  if (is_cube(f.projection)) return;
+  if (eu_cube_source(f.projection)) return;
   double te[4], we[4];
   eu::get_extent(f.projection, f.width, f.height, f.hfov, te);
   double wx = te[1] - te[0], wy = te[3] - te[2];
@@ -281,7 +243,7 @@ int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int sup
   s->fct = *fct;
   s->degree = spline_degree;
   s->nch = fct->nchannels;
-  if (is_cube(fct->projection)) {
+  if (eu_cube_source(fct->projection)) {
     // IR image: container == core, REFLECT x REFLECT (cubemap.h:576-583)
     eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
     // The support frame is all the margin the IR has: a ray at a face's edge picks up at left_frame - 0.5, and a
@@ -311,7 +273,7 @@ int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int sup
   if (e == hipSuccess) e = hipMemset(s->dev + s->nfloats, 0, slack * sizeof(float));
   if (e != hipSuccess) { delete s; return fail(EU_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
   fill_src_dev(s);
-  if (is_cube(fct->projection)) {
+  if (eu_cube_source(fct->projection)) {
     eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
     s->sd.refc_md = (float)m.refc_md;
     s->sd.model_to_px = (float)m.model_to_px;
@@ -416,7 +378,7 @@ int build_inv_planar(const eu_target *t, eu_inv_planar *q)
 }
 
 int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *out_dev,
-                 size_t row_stride_bytes, eu_render_params *p)
+                 size_t row_stride_bytes, const eu_switches &sw, eu_render_params *p)
 {
   if (!t || !srcs || !out_dev) return fail(EU_ERR_ARGUMENT, "null argument");
   if (nsrc != 1)
@@ -451,7 +413,6 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
     memcpy(q, fo, sizeof fo); q += sizeof fo;
     if (twine) memcpy(q, t->taps, 3 * sizeof(float) * (size_t)t->ntaps);
   }
-  int rc;
   int form = g.plan_form, norm_mode = g.plan_norm;
   if (key != g.plan_key) {
     eu::stepper_tables tb;
@@ -459,17 +420,17 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
       return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
     // a kernel of the previous job may still read the tables on the caller's stream
     if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
-    if ((rc = grow(&g.col, &g.col_cap, tb.col.size()))) return rc;
-    if ((rc = grow(&g.row, &g.row_cap, tb.row.size()))) return rc;
-    HIPCHK(hipMemcpyAsync(g.col, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(g.row, tb.row.data(), tb.row.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(g.col.reserve(tb.col.size()));
+    HIPCHK(g.row.reserve(tb.row.size()));
+    HIPCHK(hipMemcpyAsync(g.col.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(g.row.p, tb.row.data(), tb.row.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     std::vector<float> taps;
     if (twine) {
       // twine_t ctor: x, y pre-multiplied by the bias 4.0 (twining.h:106-121)
       taps.assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
       for (int k = 0; k < t->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
-      if ((rc = grow(&g.taps, &g.taps_cap, taps.size()))) return rc;
-      HIPCHK(hipMemcpyAsync(g.taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+      HIPCHK(g.taps.reserve(taps.size()));
+      HIPCHK(hipMemcpyAsync(g.taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     }
     // the host vectors die at the end of this block: the copies must have left them
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -500,37 +461,18 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
   }
   p->twine = twine; p->ntaps = t->ntaps; p->stage = t->stage; p->nch = s->nch;
   p->nch_out = t->nchannels;
-  p->col = g.col; p->row = g.row; p->taps = g.taps;
+  p->col = g.col.p; p->row = g.row.p; p->taps = g.taps.p;
   p->out = out_dev;
   p->out_stride = (long long)(row_stride_bytes / sizeof(float));
   p->src = s->sd;
-  { const char *e = getenv("EU_HIP_DIRECT"); p->direct = (e && e[0] == '1') ? 1 : 0; }
+  p->direct = sw.direct;
   return EU_OK;
 }
-
-// mirror of eu_multi_params (eu_render_multi.hip)
-struct multi_params {
-  int width, height, row_begin, row_end;
-  int form, norm_mode, twine, ntaps, nch, nfct, plus;
-  const float *col, *row, *taps;
-  const eu_src_dev *srcs;
-  float *out;
-  long long out_stride;
-  int tiles_x, tiles_y;
-  int band_shift, band_count, band_index;
-  int hdr, hdr_low, hdr_high;
-  const eu_generic *gen;
-  eu_inv_planar inv;
-  const float *rej;
-};
 
 // The multi-facet kernels' second early-miss stage (eu_render_multi.hip: eu_multi_maybe): for a fisheye facet
 // (no shear) a table over u = cos(angle to the facet's axis), u in [rej_cos, 1], of a lower bound of the
 // radius R(theta) = theta * lens polynomial(theta / s) a ray of that angle maps to (environment.h:254-284,
-// geometry.h:513-531), and the window's edges moved out by 0.1 %. tab: EU_REJ_STRIDE floats; false: no table.
-#define EU_REJ_N 1024
-#define EU_REJ_HDR 16
-#define EU_REJ_STRIDE (EU_REJ_HDR + EU_REJ_N)
+// geometry.h:513-531), and the window's edges moved out by 0.1 %. tab: EU_REJ_STRIDE floats (eu_launch.h); false: no table.
 static bool build_reject_table(const eu_src_dev &d, float *tab, bool analytic)
 {
   for (int i = 0; i < EU_REJ_STRIDE; i++) tab[i] = 0.0f;
@@ -592,7 +534,7 @@ static bool build_reject_table(const eu_src_dev &d, float *tab, bool analytic)
 // fuse() for several facets (envutil_payload.cc:2139-2180, :2240-2281): one
 // stepper per facet, all with normalize = true, synopsis by channel count
 int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out_dev,
-                size_t row_stride_bytes, multi_params *p, int *degree)
+                size_t row_stride_bytes, const eu_switches &sw, eu_multi_params *p, int *degree)
 {
   { int rc0 = check_target(t); if (rc0) return rc0; }
   const eu_source *s0 = srcs[0];
@@ -616,7 +558,6 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     }
     if (twine) memcpy(q, t->taps, 3 * sizeof(float) * (size_t)t->ntaps);
   }
-  int rc;
   if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));   // g.msrc and the tables are rewritten below
   if (key != g.mplan_key) {
     eu::mat3 r_cam = eu::make_r3(t->roll, t->pitch, t->yaw, false);
@@ -629,16 +570,16 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
         return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
       rows.insert(rows.end(), tb.row.begin(), tb.row.end());
     }
-    if ((rc = grow(&g.mcol, &g.mcol_cap, tb.col.size()))) return rc;
-    if ((rc = grow(&g.mrow, &g.mrow_cap, rows.size()))) return rc;
-    HIPCHK(hipMemcpyAsync(g.mcol, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemcpyAsync(g.mrow, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(g.mcol.reserve(tb.col.size()));
+    HIPCHK(g.mrow.reserve(rows.size()));
+    HIPCHK(hipMemcpyAsync(g.mcol.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(g.mrow.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     std::vector<float> taps;
     if (twine) {
       taps.assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
       for (int k = 0; k < t->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
-      if ((rc = grow(&g.mtaps, &g.mtaps_cap, taps.size()))) return rc;
-      HIPCHK(hipMemcpyAsync(g.mtaps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
+      HIPCHK(g.mtaps.reserve(taps.size()));
+      HIPCHK(hipMemcpyAsync(g.mtaps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     }
     HIPCHK(hipStreamSynchronize(g.stream));
     g.mplan_form = tb.form; g.mplan_norm = tb.norm_mode;
@@ -647,28 +588,20 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
   // the facets' evaluator parameters (they can change between jobs: always refreshed)
   std::vector<eu_src_dev> sd((size_t)nsrc);
   for (int f = 0; f < nsrc; f++) sd[f] = srcs[f]->sd;
-  if (g.msrc_cap < (size_t)nsrc) {
-    if (g.msrc) (void)hipFree(g.msrc);
-    HIPCHK(hipMalloc((void **)&g.msrc, sizeof(eu_src_dev) * (size_t)nsrc));
-    g.msrc_cap = (size_t)nsrc;
-  }
-  HIPCHK(hipMemcpyAsync(g.msrc, sd.data(), sizeof(eu_src_dev) * (size_t)nsrc, hipMemcpyHostToDevice, g.stream));
+  HIPCHK(g.msrc.reserve((size_t)nsrc));
+  HIPCHK(hipMemcpyAsync(g.msrc.p, sd.data(), sizeof(eu_src_dev) * (size_t)nsrc, hipMemcpyHostToDevice, g.stream));
   // the early-miss tables of the fisheye facets - OFF unless EU_HIP_REJ=1: measured on config 5 the second
   // stage drops a third of the exact hit tests and the step takes 7.67 instead of 7.30 ms (the table read is
   // one more round trip on a path that waits for memory already)
   bool any_rej = false;
   std::vector<float> rej;
-  {
-    const char *rje = getenv("EU_HIP_REJ");                  // read on every job
-    const bool rej_on = rje && (rje[0] == '1' || rje[0] == '2');       // 2: the table-free form where it applies
-    if (rej_on) {
-      rej.resize((size_t)nsrc * EU_REJ_STRIDE);
-      for (int f = 0; f < nsrc; f++) any_rej |= build_reject_table(sd[f], rej.data() + (size_t)f * EU_REJ_STRIDE, rje[0] == '2');
-    }
-    if (any_rej) {
-      if ((rc = grow(&g.mrej, &g.mrej_cap, rej.size()))) return rc;
-      HIPCHK(hipMemcpyAsync(g.mrej, rej.data(), rej.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    }
+  if (sw.rej) {                          // 2: the table-free form where it applies
+    rej.resize((size_t)nsrc * EU_REJ_STRIDE);
+    for (int f = 0; f < nsrc; f++) any_rej |= build_reject_table(sd[f], rej.data() + (size_t)f * EU_REJ_STRIDE, sw.rej == 2);
+  }
+  if (any_rej) {
+    HIPCHK(g.mrej.reserve(rej.size()));
+    HIPCHK(hipMemcpyAsync(g.mrej.p, rej.data(), rej.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
   }
   // facets with translation parameters step through generic_stepper (envutil_payload.cc:2145-2158,
   // :2246-2258); like the evaluator parameters these are refreshed on every job
@@ -682,20 +615,15 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     any_generic = true;
   }
   if (any_generic) {
-    if (g.mgen_cap < (size_t)nsrc) {
-      if (g.mgen) (void)hipFree(g.mgen);
-      g.mgen = nullptr; g.mgen_cap = 0;
-      HIPCHK(hipMalloc((void **)&g.mgen, sizeof(eu_generic) * (size_t)nsrc));
-      g.mgen_cap = (size_t)nsrc;
-    }
-    HIPCHK(hipMemcpyAsync(g.mgen, gv.data(), sizeof(eu_generic) * (size_t)nsrc, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(g.mgen.reserve((size_t)nsrc));
+    HIPCHK(hipMemcpyAsync(g.mgen.p, gv.data(), sizeof(eu_generic) * (size_t)nsrc, hipMemcpyHostToDevice, g.stream));
   }
   HIPCHK(hipStreamSynchronize(g.stream));
   eu_inv_planar inv;
   { int rci = build_inv_planar(t, &inv); if (rci) return rci; }
   memset(p, 0, sizeof *p);
-  p->gen = any_generic ? g.mgen : nullptr;
-  p->rej = any_rej ? g.mrej : nullptr;
+  p->gen = any_generic ? g.mgen.p : nullptr;
+  p->rej = any_rej ? g.mrej.p : nullptr;
   p->inv = inv;
   p->width = frame_w(t); p->height = frame_h(t); p->row_begin = t->row_begin; p->row_end = t->row_end;
   if (t->band_count > 1) {
@@ -714,7 +642,7 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
       if (b > highest) { highest = b; p->hdr_high = f; }
     }
   }
-  p->col = g.mcol; p->row = g.mrow; p->taps = g.mtaps; p->srcs = g.msrc;
+  p->col = g.mcol.p; p->row = g.mrow.p; p->taps = g.mtaps.p; p->srcs = g.msrc.p;
   p->out = out_dev; p->out_stride = (long long)(row_stride_bytes / sizeof(float));
   *degree = s0->degree;
   return EU_OK;
@@ -724,16 +652,19 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
 // ACROSS target rows (the inner half of the polar faces of a cubemap made from a lat/lon
 // image: 0.098 -> 0.071 ms per 1024 rows) 32x16 tiles beat the 128x4 row strips; everywhere
 // else the strips win (0.045 vs 0.055 ms). The frame is cut into segments of EU_SEG_ROWS
-// rows; 16 probe pixels per segment, evaluated on the host from the plan's stepper
+// rows (eu_select.h: eu_split_runs); 16 probe pixels per segment, evaluated on the host from the plan's stepper
 // tables, say how the source rows run there. Lat/lon sources only.
-#define EU_SEG_ROWS 512
-
-void compute_seg_flags(const eu_render_params *p)
+// (kept while the plan's tables and the source's parameters stay the same)
+void refresh_seg_flags(const eu_render_params *p)
 {
+  eu_src_dev cmp = p->src;
+  cmp.base = nullptr;
+  if (g.seg_valid && !memcmp(&cmp, &g.seg_sd, sizeof cmp)) return;
+  g.seg_sd = cmp;
+  g.seg_valid = true;
   const int W = p->width, H = p->height;
   const int nseg = (H + EU_SEG_ROWS - 1) / EU_SEG_ROWS;
   g.seg_flags.assign((size_t)nseg, 0);
-  g.seg_mixed = false;
   const eu_src_dev &s = p->src;
   if (s.prj != EU_SPHERICAL || W < 64 || g.h_col.size() < (size_t)2 * W || g.h_row.size() < (size_t)H * EU_ROW_FLOATS)
     return;
@@ -745,7 +676,6 @@ void compute_seg_flags(const eu_render_params *p)
       r[i] = p->form == EU_FORM_BCA ? (double)rt[3 + i] * c0 + (double)rt[6 + i] * c1 + rt[i]
                                     : (double)rt[3 + i] * c0 + rt[i];
   };
-  int any = 0;
   for (int k = 0; k < nseg; k++) {
     const int yc = std::min(k * EU_SEG_ROWS + EU_SEG_ROWS / 2, H - 1);
     int across = 0;
@@ -761,128 +691,74 @@ void compute_seg_flags(const eu_render_params *p)
       if (std::fabs(lat1 - lat0) * ky > 0.5 * dlon * kx) across++;
     }
     g.seg_flags[(size_t)k] = across > 8;
-    any += across > 8;
   }
-  g.seg_mixed = any > 0;
 }
 
-// the packed two-pixel kernel where it applies, the general kernel otherwise
-// (EU_HIP_KERNEL=1 forces the general kernel: A/B switch)
-int launch_render(const eu_render_params *p, void *st)
+// the staged kernels: their work list (eu_render4.hip: chunk counters of the persistent kernel, lists of the
+// tiles left to the direct-gather kernel that follows it on the same stream) and its order between streams
+int launch_staged(const eu_render_params *p, const eu_switches &sw, hipStream_t st, int *launches)
 {
-  static const int force_v1 = [] { const char *e = getenv("EU_HIP_KERNEL"); return e && e[0] == '1'; }();
-  static const bool hybrid = [] { const char *e = getenv("EU_HIP_HYBRID"); return !(e && e[0] == '0'); }();
-  // The LDS-staging kernel (eu_render4.hip). Measured: it wins where the taps
-  // dominate and the tile boxes are small - cubic / quadratic jobs on cubemap sources (config 3:
-  // 1.13 -> 0.99 ms) - and loses to the direct-gather kernels on lat/lon sources (headline 1.22
-  // vs 1.57 ms: the polar faces' boxes do not fit, the equatorial faces tie) and on bilinear
-  // jobs. EU_HIP_R4: 0 never, 1 wherever it applies (tests, A/B runs); read on every call.
-  const char *r4env = getenv("EU_HIP_R4");
-  const int r4mode = r4env ? atoi(r4env) : -1;
-  // round 3: also cubic / quadratic lat/lon jobs whose target has column plans (the headline: an upright cubemap),
-  // with the persistent form of the staged kernel (eu_render5_kernel) - eu_launch_render4 declines the others
-  const bool fast5 = p->src.prj == EU_SPHERICAL && p->src.degree >= 2 && p->form == EU_FORM_BA && p->norm_mode == EU_NORM_NONE &&
-                     p->band_count <= 1 && p->src.brighten == 1.0f && p->src.always_hit && !p->twine;
-  const bool use_r4 = r4mode == 1 || (r4mode != 0 && p->src.degree >= 2 && (is_cube(p->src.prj) || fast5));
-  // a --mask_for job paints the facet at the inner evaluation: only the general kernels do that
-  if (p->src.mask_paint) {
+  const size_t ntiles = (size_t)((p->width + 15) / 16) * (size_t)((p->row_end - p->row_begin + 7) / 8);
+  const size_t need = eu_render4_worklist_ints(ntiles);
+  if (g.wl.cap < need) {
+    if (g.wl.reserve(need) != hipSuccess) return -1;
+    if (hipMemsetAsync(g.wl.p, 0, eu_render4_worklist_header_ints() * sizeof(int), st) != hipSuccess) { g.wl.cap = 0; return -1; }
+  }
+  eu_render_params q = *p;
+  q.wl = g.wl.p;
+  // the work list and the persistent kernel's queues belong to ONE launch pair at a time: a job on another
+  // stream than the last staged job's waits for that job's event (same stream: stream order does it)
+  if (g.wl_stream_set && g.wl_stream != st && g.wl_done)
+    if (hipStreamWaitEvent(st, g.wl_done, 0) != hipSuccess) return -1;
+  const int rc = eu_launch_render4(&q, &sw, g.h_row.data(), g.h_row.size(), g.plan_gen, st, launches);
+  if (rc || !*launches) return rc;
+  if (!g.wl_done && hipEventCreateWithFlags(&g.wl_done, hipEventDisableTiming) != hipSuccess) return -1;
+  if (hipEventRecord(g.wl_done, st) != hipSuccess) return -1;
+  g.wl_stream = st; g.wl_stream_set = true;
+  return 0;
+}
+
+// the packed kernel, one launch per run of rows that want the same work layout (eu_select.h: eu_split_runs)
+int launch_packed_runs(const eu_render_params *p, const eu_switches &sw, hipStream_t st, int *launches)
+{
+  refresh_seg_flags(p);
+  const std::vector<eu_run> runs = eu_split_runs(g.seg_flags.data(), (int)g.seg_flags.size(), *p, sw.hybrid == 2);
+  if (runs.empty()) { *launches = 1; return eu_launch_render2(p, &sw, st); }
+  for (const eu_run &r : runs) {
     eu_render_params q = *p;
-    q.direct = 1;                       // not the LDS-staged variant: it evaluates inline
-    g.launches++;
-    return eu_launch_render(&q, st);
+    q.row_begin = r.row_begin; q.row_end = r.row_end;
+    q.out = p->out + (long long)(r.row_begin - p->row_begin) * p->out_stride;
+    q.layout = r.layout;
+    ++*launches;
+    const int rc = eu_launch_render2(&q, &sw, st);
+    if (rc) return rc;
   }
-  if (!force_v1 && use_r4) {
-    // work list of the staged kernel (eu_render4.hip: chunk counters of the persistent kernel,
-    // lists of the tiles left to the direct-gather kernel that follows it on the same stream)
-    const size_t ntiles = (size_t)((p->width + 15) / 16) * (size_t)((p->row_end - p->row_begin + 7) / 8);
-    const size_t need = eu_render4_worklist_ints(ntiles);
-    if (g.wl_cap < need) {
-      if (g.wl) (void)hipFree(g.wl);
-      g.wl = nullptr; g.wl_cap = 0;
-      if (hipMalloc((void **)&g.wl, need * sizeof(int)) != hipSuccess) return -1;
-      if (hipMemsetAsync(g.wl, 0, eu_render4_worklist_header_ints() * sizeof(int), (hipStream_t)st) != hipSuccess) return -1;
-      g.wl_cap = need;
-    }
-    eu_render_params q = *p;
-    q.wl = g.wl;
-    // the work list and the persistent kernel's queues belong to ONE launch pair at a time: a job on another
-    // stream than the last staged job's waits for that job's event (same stream: stream order does it)
-    if (g.wl_stream_set && g.wl_stream != (hipStream_t)st && g.wl_done)
-      if (hipStreamWaitEvent((hipStream_t)st, g.wl_done, 0) != hipSuccess) return -1;
-    g.launches += 2;
-    const int rc = eu_launch_render4(&q, g.h_row.data(), g.h_row.size(), g.plan_gen, r4mode != 1, st);
-    if (rc == 0) {
-      if (!g.wl_done && hipEventCreateWithFlags(&g.wl_done, hipEventDisableTiming) != hipSuccess) return -1;
-      if (hipEventRecord(g.wl_done, (hipStream_t)st) != hipSuccess) return -1;
-      g.wl_stream = (hipStream_t)st; g.wl_stream_set = true;
-    }
-    if (rc <= 0) return rc;
-    g.launches -= 2;
+  return 0;
+}
+
+// the kernel eu_select_path() names for the job
+int launch_render(const eu_render_params *p, const eu_switches &sw, hipStream_t st)
+{
+  eu_path path = eu_select_path(*p, sw);
+  int rc = 0, n = 0;
+  if (path == EU_PATH_STAGED) {
+    rc = launch_staged(p, sw, st, &n);
+    if (!rc && !n) path = eu_select_path(*p, sw, false);       // the plan says no (eu_staged_worth)
   }
-  if (!force_v1) {
-    // worth it for cubic / quadratic jobs whose rows fall into a few long runs: every run
-    // is a launch of its own (a rank's share of a band-interleaved split has many short
-    // runs, a 0.2 ms bilinear job little to gain: both lose more to the extra launches
-    // than the layout gains); EU_HIP_HYBRID=2 lifts the limits (tests)
-    static const bool hybrid_any = [] { const char *e = getenv("EU_HIP_HYBRID"); return e && e[0] == '2'; }();
-    const bool worth = hybrid_any || p->src.degree >= 2;
-    if (hybrid && worth && !p->twine && p->stage == 0 && p->norm_mode == EU_NORM_NONE && p->src.prj == EU_SPHERICAL) {
-      eu_src_dev cmp = p->src;
-      cmp.base = nullptr;
-      if (!g.seg_valid || memcmp(&cmp, &g.seg_sd, sizeof cmp)) {
-        compute_seg_flags(p);
-        g.seg_sd = cmp;
-        g.seg_valid = true;
-      }
-      // runs of local rows whose segments want the same layout, in chunks of 64 rows
-      auto flag_of = [&](int r) {
-        const int fy = eu_frame_row(std::min(r, p->row_end - 1), p->band_shift, p->band_count, p->band_index);
-        return (int)g.seg_flags[(size_t)std::min(fy / EU_SEG_ROWS, (int)g.seg_flags.size() - 1)];
-      };
-      auto run_end = [&](int a, int fl) {
-        int b = std::min((a / 64 + 1) * 64, p->row_end);
-        while (b < p->row_end && flag_of(b) == fl) b = std::min(b + 64, p->row_end);
-        return b;
-      };
-      int nruns = 0, tiled = 0, shortest = INT_MAX;
-      if (g.seg_mixed)
-        for (int a = p->row_begin; a < p->row_end; nruns++) {
-          const int fl = flag_of(a);
-          tiled += fl;
-          const int b = run_end(a, fl);
-          shortest = std::min(shortest, b - a);
-          a = b;
-        }
-      // a few long runs (the whole frame: 5; a contiguous strip of a split: 1-3), not the
-      // many short ones of a band-interleaved share (0.18 -> 0.21 ms when split up)
-      if (tiled > 0 && (hybrid_any || nruns <= 3 || (nruns <= 5 && shortest >= EU_SEG_ROWS))) {
-        int a = p->row_begin;
-        while (a < p->row_end) {
-          const int fl = flag_of(a);
-          const int b = run_end(a, fl);
-          eu_render_params q = *p;
-          q.row_begin = a; q.row_end = b;
-          q.out = p->out + (long long)(a - p->row_begin) * p->out_stride;
-          q.layout = fl ? 2 : 1;
-          g.launches++;
-          const int rc = eu_launch_render2(&q, st);
-          if (rc > 0) {                 // not a packed-kernel job after all: one ordinary launch
-            if (a != p->row_begin) return -1;
-            return eu_launch_render(p, st);
-          }
-          if (rc < 0) return rc;
-          a = b;
-        }
-        return 0;
-      }
+  switch (path) {
+    case EU_PATH_STAGED: break;
+    case EU_PATH_PACKED_RUNS: rc = launch_packed_runs(p, sw, st, &n); break;
+    case EU_PATH_PACKED: n = 1; rc = eu_launch_render2(p, &sw, st); break;
+    case EU_PATH_GENERAL: n = 1; rc = eu_launch_render(p, st); break;
+    case EU_PATH_GENERAL_DIRECT: {
+      eu_render_params q = *p;
+      q.direct = 1;                       // not the LDS-staged variant: it evaluates inline
+      n = 1;
+      rc = eu_launch_render(&q, st);
     }
-    g.launches++;
-    int rc = eu_launch_render2(p, st);
-    if (rc <= 0) return rc;
-    g.launches--;
   }
-  g.launches++;
-  return eu_launch_render(p, st);
+  g.launches += n;
+  return rc;
 }
 
 
@@ -922,10 +798,9 @@ int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
   // an earlier edit on a caller's stream may still read the buffer
   if (g.aplan_user) { HIPCHK(hipStreamSynchronize(g.aplan_user)); g.aplan_user = nullptr; }
   HIPCHK(hipStreamSynchronize(g.stream));
-  int rc;
-  if ((rc = grow(&g.aplan, &g.aplan_cap, plan.size() + 2))) return rc;
-  HIPCHK(hipMemcpy(g.aplan, plan.data(), plan.size() * sizeof(int), hipMemcpyHostToDevice));
-  p->keep = reinterpret_cast<const int32_t *>(g.aplan);
+  HIPCHK(g.aplan.reserve(plan.size() + 2));
+  HIPCHK(hipMemcpy(g.aplan.p, plan.data(), plan.size() * sizeof(int), hipMemcpyHostToDevice));
+  p->keep = g.aplan.p;
   p->row_start = p->keep + size_t(h) * 2;
   p->spans = p->row_start + size_t(h) + 1;
   return EU_OK;
@@ -1053,9 +928,9 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
   // (a core narrower than the spline's frame on an axis is braced slice by slice in zimt's order,
   // eu_setup.hip: brace_seq_kernel)
-  const int nch = s->nch;
+  const int nch = s->nch, iir_stream = eu_read_switches().iir_stream;
   hipError_t e = hipSuccess;
-  if (is_cube(fct->projection)) {
+  if (eu_cube_source(fct->projection)) {
     eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
     size_t nface = (size_t)6 * m.face_px * m.face_px * nch;
     float *faces = nullptr;
@@ -1064,7 +939,7 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
     if (e == hipSuccess) {
       rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px,
                                    m.right_frame_px, m.refc_md, m.model_to_px, prefilter_degree,
-                                   g.stream);
+                                   iir_stream, g.stream);
       e = hipStreamSynchronize(g.stream);
     }
     if (faces) (void)hipFree(faces);
@@ -1085,7 +960,7 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
                       && fct->width == 2 * fct->height;
       // (a full-sphere image smaller than its frame - 2 x 1, 4 x 2, 6 x 3 for degree 3 - takes the sequential forms of
       // the pole rows and of the horizontal bracing: eu_setup.hip, pole_rows_seq_kernel / brace_seq_kernel)
-      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, g.stream);
+      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
       e = hipStreamSynchronize(g.stream);
     }
   }
@@ -1170,8 +1045,8 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
   source_bcs(fct, &bc0, &bc1);
   eu_source *s = nullptr;
   if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
-  const int nch = s->nch, src_ch = edit->pixel_channels;
-  const bool cube = is_cube(fct->projection);
+  const int nch = s->nch, src_ch = edit->pixel_channels, iir_stream = eu_read_switches().iir_stream;
+  const bool cube = eu_cube_source(fct->projection);
   eu::metrics m {};
   if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
   // the plane of the edit: the facet's window; cubemaps: the stack of six faces
@@ -1208,12 +1083,12 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
   if (e == hipSuccess && !prc) {
     if (cube) {
       rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
-                                   m.refc_md, m.model_to_px, prefilter_degree, g.stream);
+                                   m.refc_md, m.model_to_px, prefilter_degree, iir_stream, g.stream);
     } else {
       // as eu_hip_source_load: full spherical images get the two-axis periodic scheme
       int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
                       && fct->width == 2 * fct->height;
-      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, g.stream);
+      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
     }
   }
   const hipError_t e2 = hipStreamSynchronize(g.stream);
@@ -1253,12 +1128,12 @@ int eu_hip_source_update_facet(eu_source *src, const eu_facet *fct)
   if (fct->projection != o.projection || fct->nchannels != o.nchannels || fct->width != o.width ||
       fct->height != o.height || fct->window_width != o.window_width || fct->window_height != o.window_height)
     return fail(EU_ERR_ARGUMENT, "the facet's image (projection, size, channels) differs from the resident one");
-  if (is_cube(o.projection) && fct->hfov != o.hfov)
+  if (eu_cube_source(o.projection) && fct->hfov != o.hfov)
     return fail(EU_ERR_ARGUMENT, "a cubemap's field of view is part of its resident image");
   const eu_src_dev keep = src->sd;
   src->fct = *fct;
   fill_src_dev(src);
-  if (is_cube(o.projection)) {
+  if (eu_cube_source(o.projection)) {
     src->sd.refc_md = keep.refc_md; src->sd.model_to_px = keep.model_to_px; src->sd.section_px = keep.section_px;
   }
   return EU_OK;
@@ -1305,7 +1180,7 @@ int eu_hip_source_release(eu_source *src)
 // tethered - float pixels into the library's frame buffer followed by the
 // to_screen_t pass that writes the packed words to out_dev
 static int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev,
-                            size_t stride_bytes, hipStream_t st)
+                            size_t stride_bytes, const eu_switches &sw, hipStream_t st)
 {
   int rc;
   const bool multi = nsrc > 1;
@@ -1318,18 +1193,18 @@ static int render_on_device(const eu_target *trg, eu_source *const *srcs, int ns
     if (!g.lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
     tf.out_format = EU_OUT_FLOAT;
     fstride = (size_t)frame_w(trg) * trg->nchannels * sizeof(float);
-    if ((rc = grow(&g.scr, &g.scr_cap, rows * frame_w(trg) * trg->nchannels))) return rc;
-    fout = g.scr;
+    HIPCHK(g.scr.reserve(rows * frame_w(trg) * trg->nchannels));
+    fout = g.scr.p;
   }
   if (multi) {
-    multi_params mp;
+    eu_multi_params mp;
     int mdeg = 0;
-    if ((rc = build_multi(&tf, srcs, nsrc, fout, fstride, &mp, &mdeg))) return rc;
+    if ((rc = build_multi(&tf, srcs, nsrc, fout, fstride, sw, &mp, &mdeg))) return rc;
     if (eu_launch_render_multi(&mp, mdeg, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
   } else {
     eu_render_params p;
-    if ((rc = build_params(&tf, srcs, nsrc, fout, fstride, &p))) return rc;
-    if (launch_render(&p, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    if ((rc = build_params(&tf, srcs, nsrc, fout, fstride, sw, &p))) return rc;
+    if (launch_render(&p, sw, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
   }
   if (screen &&
       eu_launch_to_screen(fout, (long long)(fstride / sizeof(float)), (unsigned *)out_dev,
@@ -1365,10 +1240,11 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
   // for it before they rewrite tables that job may be reading (it used to be overwritten here, so a job on another
   // stream rewrote the tables under the previous one: tests/test_gpu_round3_switches.py)
   struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
-  if (out_on_device) return render_on_device(trg, srcs, nsrc, out, out_row_stride_bytes, st);
+  const eu_switches sw = eu_read_switches();
+  if (out_on_device) return render_on_device(trg, srcs, nsrc, out, out_row_stride_bytes, sw, st);
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (!rows) return EU_OK;
-  if ((rc = grow(&g.stage, &g.stage_cap, rows * frame_w(trg) * och))) return rc;
+  HIPCHK(g.stage.reserve(rows * frame_w(trg) * och));
   // The frame goes to the host in up to four row chunks: every chunk is a launch of its own
   // on `st`, and its copy (second stream, behind the chunk's event) runs while the later
   // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
@@ -1378,7 +1254,7 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
   for (size_t c = 0; c < 4; c++)
     if (!g.chunk_done[c]) HIPCHK(hipEventCreateWithFlags(&g.chunk_done[c], hipEventDisableTiming));
   const size_t per = ((rows + nchunk - 1) / nchunk + 7) / 8 * 8;
-  // whatever happens below, nothing of this call may still write into `out` or read g.stage when it returns
+  // whatever happens below, nothing of this call may still write into `out` or read g.stage.p when it returns
   struct drain { hipStream_t a, b; ~drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain_on_exit{ g.copy, st };
   for (size_t c = 0; c < nchunk; c++) {
     const size_t a = std::min(rows, c * per), b = std::min(rows, (c + 1) * per);
@@ -1386,8 +1262,8 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
     eu_target tc = *trg;
     tc.row_begin = trg->row_begin + (int)a;
     tc.row_end = trg->row_begin + (int)b;
-    float *dst = g.stage + a * frame_w(trg) * och;
-    if ((rc = render_on_device(&tc, srcs, nsrc, dst, min_stride, st))) return rc;
+    float *dst = g.stage.p + a * frame_w(trg) * och;
+    if ((rc = render_on_device(&tc, srcs, nsrc, dst, min_stride, sw, st))) return rc;
     HIPCHK(hipEventRecord(g.chunk_done[c], st));
     HIPCHK(hipStreamWaitEvent(g.copy, g.chunk_done[c], 0));
     HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, min_stride,
@@ -1532,6 +1408,7 @@ int eu_hip_render_devices(const eu_target *trg, eu_source *const *srcs, int nsrc
     return fail(EU_ERR_ARGUMENT, "row stride smaller than a row / not a multiple of 4 bytes");
   int begin[EU_MAX_SLOTS], end[EU_MAX_SLOTS];
   cost_strips(trg, srcs, nsrc, nslots_, begin, end);
+  const eu_switches sw = eu_read_switches();
   // every slot: its replicas, its strip into its own buffer, the strip's way to `out` behind it on the
   // slot's stream; the slots run concurrently, one host thread feeds them
   struct guard { ~guard() { for (int k = 0; k < nslots_; k++) { cur_slot_ = k; if (ctx_[k].device >= 0 && hipSetDevice(ctx_[k].device) == hipSuccess && ctx_[k].stream) (void)hipStreamSynchronize(ctx_[k].stream); } cur_slot_ = 0; if (ctx_[0].device >= 0) (void)hipSetDevice(ctx_[0].device); } } sync_all_on_exit;
@@ -1550,10 +1427,10 @@ int eu_hip_render_devices(const eu_target *trg, eu_source *const *srcs, int nsrc
     float *dst = nullptr;
     if (direct) dst = out + (size_t)begin[k] * (min_stride / sizeof(float));
     else {
-      if ((rc = grow(&g.strip, &g.strip_cap, rows * (min_stride / sizeof(float))))) return rc;
-      dst = g.strip;
+      HIPCHK(g.strip.reserve(rows * (min_stride / sizeof(float))));
+      dst = g.strip.p;
     }
-    if ((rc = render_on_device(&t, reps, nsrc, dst, min_stride, g.stream))) return rc;
+    if ((rc = render_on_device(&t, reps, nsrc, dst, min_stride, sw, g.stream))) return rc;
     if (!direct) {
       char *o = (char *)out + (size_t)begin[k] * out_row_stride_bytes;
       if (!out_on_device)
@@ -1584,16 +1461,10 @@ int eu_hip_layout_segments(const eu_target *trg, eu_source *const *srcs, int nsr
   t.band_rows = 0; t.band_count = 0; t.band_index = 0;
   t.row_begin = 0; t.row_end = frame_h(trg);
   float dummy;
-  if ((rc = build_params(&t, srcs, 1, &dummy, (size_t)frame_w(trg) * t.nchannels * sizeof(float), &p))) return rc;
+  if ((rc = build_params(&t, srcs, 1, &dummy, (size_t)frame_w(trg) * t.nchannels * sizeof(float), eu_read_switches(), &p))) return rc;
   if (seg_rows) *seg_rows = EU_SEG_ROWS;
   if (p.twine || p.norm_mode != EU_NORM_NONE || p.src.prj != EU_SPHERICAL) return 0;
-  eu_src_dev cmp = p.src;
-  cmp.base = nullptr;
-  if (!g.seg_valid || memcmp(&cmp, &g.seg_sd, sizeof cmp)) {
-    compute_seg_flags(&p);
-    g.seg_sd = cmp;
-    g.seg_valid = true;
-  }
+  refresh_seg_flags(&p);
   const int n = (int)g.seg_flags.size();
   if (n > max_flags) return fail(EU_ERR_ARGUMENT, "flags buffer too small");
   memcpy(flags, g.seg_flags.data(), (size_t)n);
@@ -1626,8 +1497,9 @@ int eu_hip_render_timed(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   if (iters <= 0 || !mean_ms) return fail(EU_ERR_ARGUMENT, "bad iteration count");
   if (!srcs || nsrc < 1 || !trg || !out_dev) return fail(EU_ERR_ARGUMENT, "no source / no output");
   if ((rc = check_target(trg))) return rc;
+  const eu_switches sw = eu_read_switches();
   // one untimed launch builds the plan (stepper tables, derived copies)
-  if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, g.stream))) return rc;
+  if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, sw, g.stream))) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   struct guard {
     hipEvent_t &a, &b;
@@ -1637,7 +1509,7 @@ int eu_hip_render_timed(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   HIPCHK(hipEventCreate(&e1));
   HIPCHK(hipEventRecord(e0, g.stream));
   for (int i = 0; i < iters; i++)
-    if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, g.stream))) return rc;
+    if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, sw, g.stream))) return rc;
   HIPCHK(hipEventRecord(e1, g.stream));
   HIPCHK(hipEventSynchronize(e1));
   float ms = 0.0f;
@@ -1655,7 +1527,7 @@ int eu_hip_diag_stamps(const eu_target *trg, eu_source *const *srcs, int nsrc, f
   int rc;
   if ((rc = ensure_init())) return rc;
   eu_render_params p;
-  if ((rc = build_params(trg, srcs, nsrc, out_dev, out_row_stride_bytes, &p))) return rc;
+  if ((rc = build_params(trg, srcs, nsrc, out_dev, out_row_stride_bytes, eu_read_switches(), &p))) return rc;
   if (p.nch != 3 || p.src.degree != 3 || p.twine) return fail(EU_ERR_ARGUMENT, "diag: NCH 3, degree 3, no twining");
   unsigned long long *d = nullptr;
   struct guard { unsigned long long *&q; ~guard() { if (q) (void)hipFree(q); } } buf { d };

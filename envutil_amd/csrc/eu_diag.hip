@@ -3,6 +3,7 @@
 // timings are read as SHARES of a wave's lifetime, not as kernel time.
 #include "eu_render_dev.h"
 #include "eu_packed_dev.h"
+#include "eu_launch.h"
 
 __device__ __forceinline__ unsigned long long eu_stamp()
 {

@@ -1,0 +1,85 @@
+// The boundary between the C ABI's host glue (eu_api.hip) and the kernel files, declared once: the
+// launchers, the argument structure of the multi-facet kernels and a typed device buffer.
+#ifndef EU_LAUNCH_H
+#define EU_LAUNCH_H
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include "eu_device.h"
+#include "eu_select.h"
+
+// early-miss tables of a multi-facet job (eu_render_multi.hip: eu_multi_maybe): per facet a header and
+// EU_REJ_N bins over u = cos(angle to the facet's axis)
+#define EU_REJ_N 1024
+#define EU_REJ_HDR 16
+#define EU_REJ_STRIDE (EU_REJ_HDR + EU_REJ_N)
+
+struct eu_multi_params {
+  int width, height, row_begin, row_end;
+  int form, norm_mode, twine, ntaps, nch, nfct, plus;
+  const float *col;          // [4][width], shared by all facets
+  const float *row;          // [nfct][height][EU_ROW_FLOATS]
+  const float *taps;         // [ntaps][3], x/y scaled by 4
+  const eu_src_dev *srcs;    // [nfct]
+  float *out;
+  long long out_stride;
+  int tiles_x, tiles_y;
+  int band_shift, band_count, band_index;   // eu_frame_row
+  int hdr, hdr_low, hdr_high;               // _hdr_merge_syn: the facets that rule the shadows / the highlights
+  const eu_generic *gen;                    // [nfct] or nullptr: facets stepped by generic_stepper (translation)
+  eu_inv_planar inv;                        // tf22 of a --single job
+  const float *rej;                         // [nfct][EU_REJ_STRIDE] or nullptr: early-miss tables (eu_multi_maybe)
+};
+
+struct eu_alpha_params;      // eu_alpha.h
+
+// Device memory that only ever grows. reserve() frees and allocates: the old contents are gone, and the
+// capacity stays 0 when the allocation fails.
+template <class T> struct eu_dev_buf {
+  T *p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t n)
+  {
+    if (cap >= n) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n; else p = nullptr;
+    return e;
+  }
+};
+
+// The render launchers return 0, or a negative value: -1 a HIP error, -2 a job outside the kernel's
+// coverage (eu_select.h decides before the call, so that is a bug of the caller).
+extern "C" {
+int eu_launch_render(const eu_render_params *p, void *stream);
+int eu_launch_render2(const eu_render_params *p, const eu_switches *sw, void *stream);
+// h_row: the host copy of the plan's row table (whole frame), plan_gen: changes whenever the stepper tables
+// change. *launches: kernels launched for the job - 0 where the plan of a lat/lon job says that the
+// direct-gather kernels are faster (eu_staged_worth; the plan stays cached)
+int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const float *h_row, size_t h_row_floats,
+                      unsigned long long plan_gen, void *stream, int *launches);
+size_t eu_render4_worklist_ints(size_t ntiles);
+size_t eu_render4_worklist_header_ints(void);
+int eu_launch_render_multi(const eu_multi_params *p, int degree, void *stream);
+int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stream);
+int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);
+int eu_launch_render_multi_nch3(const eu_multi_params *p, int degree, void *stream);
+int eu_launch_render_multi_nch4(const eu_multi_params *p, int degree, void *stream);
+int eu_launch_to_screen(const float *in, long long in_stride, unsigned *out, long long out_stride, int w, int rows,
+                        int nch, const float *lut, void *stream);
+// iir_stream: eu_switches::iir_stream
+int eu_launch_prefilter(float *container, const eu_container *g, int nch, int bc0, int bc1, int prefilter_degree,
+                        int spherical, int iir_stream, void *stream);
+int eu_launch_cubemap_build(const float *faces_dev, float *ir_dev, int nch, long face_px, long section_px,
+                            long left_frame, long right_frame, double refc_md, double model_to_px,
+                            int prefilter_degree, int iir_stream, void *stream);
+int eu_launch_facet_alpha(const eu_alpha_params *p, void *stream);
+int eu_launch_diag(const eu_render_params *p, unsigned long long *stamps_dev, void *stream);
+int eu_launch_diag_coords(const eu_src_dev *s, const float *rays_dev, long n, int variant, float *out_dev,
+                          void *stream);
+int eu_launch_selftest(unsigned long long seed, int blocks, int iters, unsigned long long *bad_dev, void *stream);
+int eu_verify_const_div(float c, float limit, void *stream);   // 1: the three-operation division is exact
+int eu_current_slot(void);                                     // the device slot the entry points work on
+}
+
+#endif

@@ -28,6 +28,7 @@
 #include "eu_math.h"
 
 #include "eu_render_dev.h"
+#include "eu_launch.h"
 
 // ---------------------------------------------------------------------------
 // the kernel

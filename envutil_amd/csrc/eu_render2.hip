@@ -5,8 +5,8 @@
 // Same operations, same order, same bits as eu_render_kernel - only how they
 // are issued changes. Covers the jobs without twining whose source is a
 // lat/lon image; everything else stays on eu_render_kernel.
-#include <cstdlib>
 #include "eu_packed_dev.h"
+#include "eu_launch.h"
 
 #define EU2_TILE_W 128   // pixels of one row per wave and pass (2 per lane)
 #define EU2_TILE_H 4   // default waves (rows) per workgroup
@@ -221,7 +221,7 @@ static int launch2_nd(const eu_render_params &p, hipStream_t st)
     case EU_CUBEMAP: return launch2_ndp<NCH, DEG, EU_CUBEMAP>(p, st);
     case EU_BIATAN6: return launch2_ndp<NCH, DEG, EU_BIATAN6>(p, st);
   }
-  return 1;
+  return -2;
 }
 
 template <int NCH>
@@ -232,26 +232,18 @@ static int launch2_n(const eu_render_params &p, hipStream_t st)
     case 2: return launch2_nd<NCH, 2>(p, st);
     case 3: return launch2_nd<NCH, 3>(p, st);
   }
-  return 1;
+  return -2;
 }
 
-// returns 1 when the job is outside this kernel's coverage (caller falls back
-// to eu_render_kernel)
-extern "C" int eu_launch_render2(const eu_render_params *pp, void *stream)
+extern "C" int eu_launch_render2(const eu_render_params *pp, const eu_switches *sw, void *stream)
 {
   eu_render_params p = *pp;
-  if (p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return 1;
-  if (p.src.prj != EU_SPHERICAL && p.src.prj != EU_CUBEMAP && p.src.prj != EU_BIATAN6) return 1;
-  if (p.src.degree < 1 || p.src.degree > 3 || p.src.es0 != p.nch) return 1;
+  if (!eu_packed_covers(p)) return -2;
   p.unit_rows = EU2_UNIT_ROWS;
   // rotated targets and twined jobs walk their units column by column (eu_xcd_tile): their source lines are
   // shared between vertically neighbouring tiles. EU_HIP_COLMAJOR=0 / 1 forces one walk (A/B runs).
-  {
-    const char *cme = getenv("EU_HIP_COLMAJOR");          // read on every launch, like the other A/B switches
-    const int cm_env = cme && cme[0] ? atoi(cme) : -1;
-    const bool cm = cm_env >= 0 ? cm_env != 0 : (p.form != EU_FORM_BA || p.twine);
-    if (cm) p.unit_rows = -p.unit_rows;
-  }
+  const bool cm = sw->colmajor >= 0 ? sw->colmajor != 0 : (p.form != EU_FORM_BA || p.twine);
+  if (cm) p.unit_rows = -p.unit_rows;
   p.tiles_x = (p.width + EU2_TILE_W - 1) / EU2_TILE_W;
   p.tiles_y = (p.row_end - p.row_begin + EU2_TILE_H - 1) / EU2_TILE_H;
   if (p.tiles_x <= 0 || p.tiles_y <= 0) return 0;
@@ -262,5 +254,5 @@ extern "C" int eu_launch_render2(const eu_render_params *pp, void *stream)
     case 3: return launch2_n<3>(p, st);
     case 4: return launch2_n<4>(p, st);
   }
-  return 1;
+  return -2;
 }

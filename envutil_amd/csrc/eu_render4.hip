@@ -32,12 +32,12 @@
 //
 // Stands in for: zimt::process' get/act/put loop (wielding.h:151-463) with the
 // evaluator's gathers (zimt/eval.h:838-889) replaced by LDS reads.
-#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 #include <algorithm>
 #include "eu_packed_dev.h"
+#include "eu_launch.h"
 
 #define EU4_TW 16          // wave tile, pixels
 #define EU4_TH 8
@@ -481,12 +481,7 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
       if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
       return n;
     }();
-    // eu_div2_rr's range: the divisor in [2^-20, 2^20], the extent's origin 0 or in that range (so that a
-    // non-zero difference 'angle - origin' is at least 2^-73)
-    auto mag_ok = [](double v) { const double a = v < 0 ? -v : v; return a == 0.0 || (a >= 0x1p-20 && a <= 0x1p20); };
-    const bool fast = p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && p.band_count <= 1 && p.src.brighten == 1.0f &&
-                      p.src.always_hit && mag_ok(p.src.tex_x0) && mag_ok(p.src.tex_y0) && p.src.ext_w >= 0x1p-20f &&
-                      p.src.ext_w <= 0x1p20f && p.src.ext_h >= 0x1p-20f && p.src.ext_h <= 0x1p20f && p.tab_finite;
+    const bool fast = eu_staged_fast_profile(p);
     int per_cu = 0;
     if (fast) {
       static const int occ = [] { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, eu_render5_kernel<NCH, DEG, PRJ, true>, 64 * EU5_WAVES, 0) == hipSuccess ? n : 0; }();
@@ -523,7 +518,7 @@ static int launch4_nd(const eu_render_params &p, const eu4_plan &w, hipStream_t 
     case EU_CUBEMAP: return launch4_ndp<NCH, DEG, EU_CUBEMAP>(p, w, st);
     case EU_BIATAN6: return launch4_ndp<NCH, DEG, EU_BIATAN6>(p, w, st);
   }
-  return 1;
+  return -2;
 }
 
 template <int NCH>
@@ -534,7 +529,7 @@ static int launch4_n(const eu_render_params &p, const eu4_plan &w, hipStream_t s
     case 2: return launch4_nd<NCH, 2>(p, w, st);
     case 3: return launch4_nd<NCH, 3>(p, w, st);
   }
-  return 1;
+  return -2;
 }
 
 // ints the work list buffer needs for a launch of `ntiles` wave tiles
@@ -551,20 +546,17 @@ extern "C" size_t eu_render4_worklist_header_ints(void) { return EU4_WL_ENTRIES;
 // rx, rz and everything derived from them alone are functions of the column). Tile rows
 // with the same four constants share a table.
 // ---------------------------------------------------------------------------
-extern "C" int eu_current_slot(void);
+static_assert(EU_STAGED_TILE_ROWS == EU4_TH && EU_STAGED_MAX_TILES_Y == 65535 * 8 * EU4_UNIT_ROWS, "eu_select.h: eu_staged_covers");
 namespace {
 struct plan_cache {
   std::vector<unsigned char> key;
-  int *tileplan = nullptr; size_t tileplan_cap = 0;
-  float *coltab = nullptr; size_t coltab_cap = 0;
+  eu_dev_buf<int> tileplan, l2_rows, l1_ent, xtab;
+  eu_dev_buf<float> coltab;
   float *atab = nullptr;
   int planned_rows = 0;      // tile rows with a column plan
-  int *l2_rows = nullptr; size_t l2_cap = 0;
   int l2_off[9] = {};
-  int *l1_ent = nullptr; size_t l1_cap = 0;
   int l1_off[9] = {};
   int l1_ecols = 1;
-  int *xtab = nullptr; size_t xtab_cap = 0;
   long long follower_tiles = 0;
   hipStream_t last_stream = nullptr;   // where the plans were last read
 } g4s[EU_MAX_SLOTS];
@@ -586,197 +578,150 @@ void launch_colplan(const eu_render_params &p, float *ct, const float *k, hipStr
   hipLaunchKernelGGL((eu_colplan_kernel<DEG>), dim3((unsigned)((p.width + 511) / 512)), dim3(256), 0, st, p, ct,
                      k[0], k[1], k[2], k[3]);
 }
-}  // namespace
 
-// h_row: the host copy of the plan's row table (whole frame), plan_gen: changes whenever the
-// stepper tables change. Returns 1 when the job is outside this kernel's coverage (the caller
-// goes on to eu_launch_render2 / eu_launch_render).
-// only_if_worth: take a lat/lon job only where the staged kernels measured faster than the direct-gather ones
-// (cubic / quadratic, the FAST profile, column plans on at least half of the tile rows: an upright cubemap or
-// rectilinear target); 0: every job they cover (EU_HIP_R4=1: tests, A/B runs)
-extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row, size_t h_row_floats,
-                                 unsigned long long plan_gen, int only_if_worth, void *stream)
+// everything the cached plans depend on
+std::vector<unsigned char> eu4_plan_key(const eu_render_params &p, unsigned long long plan_gen, int share_mode)
 {
-  eu_render_params p = *pp;
-  eu4_followers_last = 0;
-  if (p.twine || p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return 1;
-  if (p.norm_mode != EU_NORM_NONE && p.norm_mode != EU_NORM_DIV) return 1;
-  if (p.src.prj != EU_SPHERICAL && p.src.prj != EU_CUBEMAP && p.src.prj != EU_BIATAN6) return 1;
-  if (p.src.degree < 1 || p.src.degree > 3 || p.src.es0 != p.nch) return 1;
-  if (p.nch != 3 && p.nch != 4) return 1;
-  if (!p.wl) return 1;
-  // the staging offsets are 32-bit
-  if (p.src.es1 * 4 >= (1ll << 31)) return 1;
-  p.tiles_y = (p.row_end - p.row_begin + EU4_TH - 1) / EU4_TH;
-  eu4_plan w;
-  w.tiles16 = (p.width + EU4_TW - 1) / EU4_TW;
-  if (w.tiles16 <= 0 || p.tiles_y <= 0) return 0;
-  if (p.tiles_y > 65535 * 8 * EU4_UNIT_ROWS) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (!ensure_atab()) return -1;
-  w.atab_g = g4.atab;
-
-  // ---- column plans (cached while nothing they depend on changes) ----------------------
-  // EU_HIP_SHARE (read on every call, like the other A/B switches): 0: no tile is rendered from another tile's
-  // coordinates, m: column mirrors only, f: other faces only; anything else, or unset: both
-  int share_mode = EU_SHARE_FACES | EU_SHARE_MIRRORS;
-  if (const char *e = getenv("EU_HIP_SHARE")) {
-    if (e[0] == '0') share_mode = 0;
-    else if (e[0] == 'm') share_mode = EU_SHARE_MIRRORS;
-    else if (e[0] == 'f') share_mode = EU_SHARE_FACES;
-  }
   std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 9 * sizeof(int));
+  unsigned char *q = key.data();
+  memcpy(q, &plan_gen, sizeof plan_gen); q += sizeof plan_gen;
+  eu_src_dev sd = p.src; sd.base = nullptr;
+  memcpy(q, &sd, sizeof sd); q += sizeof sd;
+  const int v[9] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, share_mode };
+  memcpy(q, v, sizeof v);
+  return key;
+}
+
+bool upload(eu_dev_buf<int> &buf, const std::vector<int> &v, size_t spare)
+{
+  if (buf.reserve(v.size() + spare) != hipSuccess) return false;
+  return v.empty() || hipMemcpy(buf.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// the plans of a lat/lon job into the slot's cache: the tile rows' plan ids, the second loop's rows, the column
+// tables (one kernel launch per plan) and, from their bits, the first loop's entries (eu_share_groups.h)
+int eu4_build_plans(const eu_render_params &p, int tiles16, const eu_switches &sw, const float *h_row,
+                    size_t h_row_floats, hipStream_t st)
+{
+  std::vector<int> tp((size_t)p.tiles_y, -1);
+  std::vector<float> plans;          // 4 floats per plan: A0, A2, B0, B2
+  const bool can = p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && h_row;
+  if (can && sw.colplan) {
+    for (int ty = 0; ty < p.tiles_y; ty++) {
+      float k[4] = { 0, 0, 0, 0 };
+      bool same = true;
+      for (int ly = 0; ly < EU4_TH && same; ly++) {
+        const int y = std::min(p.row_begin + ty * EU4_TH + ly, p.row_end - 1);
+        const size_t fr = (size_t)eu_frame_row(y, p.band_shift, p.band_count, p.band_index) * EU_ROW_FLOATS;
+        if (fr + 6 > h_row_floats) { same = false; break; }
+        const float c[4] = { h_row[fr + 0], h_row[fr + 2], h_row[fr + 3], h_row[fr + 5] };
+        if (ly == 0) memcpy(k, c, sizeof k);
+        else same = memcmp(k, c, sizeof k) == 0;
+      }
+      if (!same) continue;
+      int id = -1;
+      for (size_t j = 0; j < plans.size() / 4 && id < 0; j++)
+        if (memcmp(&plans[4 * j], k, sizeof k) == 0) id = (int)j;
+      if (id < 0 && plans.size() / 4 < EU4_MAX_PLANS) {
+        id = (int)(plans.size() / 4);
+        plans.insert(plans.end(), k, k + 4);
+      }
+      tp[(size_t)ty] = id;
+    }
+  }
+  const int nplans = (int)(plans.size() / 4);
+  if (g4.tileplan.reserve(tp.size()) != hipSuccess) return -1;
+  if (g4.coltab.reserve(std::max<size_t>(1, nplans) * (size_t)p.width * EU4_COL_FLOATS) != hipSuccess) return -1;
+  // the previous launch may still read the old plans - on this stream or on the one the plans were last
+  // used on (the library's own stream and a caller's stream alternate)
+  if (hipStreamSynchronize(st) != hipSuccess) return -1;
+  if (g4.last_stream && g4.last_stream != st && hipStreamSynchronize(g4.last_stream) != hipSuccess) return -1;
+  if (hipMemcpy(g4.tileplan.p, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
+  g4.planned_rows = 0;
+  for (int v : tp) g4.planned_rows += v >= 0;
+  auto paired = [&](int m) { return 2 * m + 1 < p.tiles_y && tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1]; };
   {
-    unsigned char *q = key.data();
-    memcpy(q, &plan_gen, sizeof plan_gen); q += sizeof plan_gen;
-    eu_src_dev sd = p.src; sd.base = nullptr;
-    memcpy(q, &sd, sizeof sd); q += sizeof sd;
-    const int v[9] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, share_mode };
-    memcpy(q, v, sizeof v);
+    // the second loop's rows per XCD: units of EU5_UNIT_ROWS tile rows dealt round-robin, as in the first loop
+    std::vector<int> rows[8], all;
+    for (int r = 0; r < p.tiles_y; r++)
+      if (!paired(r >> 1)) rows[(r / EU5_UNIT_ROWS) & 7].push_back(r);
+    for (int x = 0; x < 8; x++) { g4.l2_off[x] = (int)all.size(); all.insert(all.end(), rows[x].begin(), rows[x].end()); }
+    g4.l2_off[8] = (int)all.size();
+    if (!upload(g4.l2_rows, all, 1)) return -1;
   }
-  // (cubemap / biatan6 sources never read the tile plan: no plans, no upload, no synchronisation for them)
-  if (p.src.prj == EU_SPHERICAL && key != g4.key) {
-    std::vector<int> tp((size_t)p.tiles_y, -1);
-    std::vector<float> plans;          // 4 floats per plan: A0, A2, B0, B2
-    const bool can = p.src.prj == EU_SPHERICAL && p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && h_row;
-    static const bool off = [] { const char *e = getenv("EU_HIP_COLPLAN"); return e && e[0] == '0'; }();
-    if (can && !off) {
-      for (int ty = 0; ty < p.tiles_y; ty++) {
-        float k[4] = { 0, 0, 0, 0 };
-        bool same = true;
-        for (int ly = 0; ly < EU4_TH && same; ly++) {
-          const int y = std::min(p.row_begin + ty * EU4_TH + ly, p.row_end - 1);
-          const size_t fr = (size_t)eu_frame_row(y, p.band_shift, p.band_count, p.band_index) * EU_ROW_FLOATS;
-          if (fr + 6 > h_row_floats) { same = false; break; }
-          const float c[4] = { h_row[fr + 0], h_row[fr + 2], h_row[fr + 3], h_row[fr + 5] };
-          if (ly == 0) memcpy(k, c, sizeof k);
-          else same = memcmp(k, c, sizeof k) == 0;
-        }
-        if (!same) continue;
-        int id = -1;
-        for (size_t j = 0; j < plans.size() / 4 && id < 0; j++)
-          if (memcmp(&plans[4 * j], k, sizeof k) == 0) id = (int)j;
-        if (id < 0 && plans.size() / 4 < EU4_MAX_PLANS) {
-          id = (int)(plans.size() / 4);
-          plans.insert(plans.end(), k, k + 4);
-        }
-        tp[(size_t)ty] = id;
-      }
+  for (int j = 0; j < nplans; j++) {
+    float *ct = g4.coltab.p + j * (size_t)p.width * EU4_COL_FLOATS;
+    switch (p.src.degree) {
+      case 1: launch_colplan<1>(p, ct, &plans[4 * j], st); break;
+      case 2: launch_colplan<2>(p, ct, &plans[4 * j], st); break;
+      default: launch_colplan<3>(p, ct, &plans[4 * j], st); break;
     }
-    if (g4.tileplan_cap < tp.size()) {
-      if (g4.tileplan) (void)hipFree(g4.tileplan);
-      g4.tileplan = nullptr; g4.tileplan_cap = 0;
-      if (hipMalloc((void **)&g4.tileplan, tp.size() * sizeof(int)) != hipSuccess) return -1;
-      g4.tileplan_cap = tp.size();
-    }
-    const size_t need = std::max<size_t>(1, plans.size() / 4) * (size_t)p.width * EU4_COL_FLOATS;
-    if (g4.coltab_cap < need) {
-      if (g4.coltab) (void)hipFree(g4.coltab);
-      g4.coltab = nullptr; g4.coltab_cap = 0;
-      if (hipMalloc((void **)&g4.coltab, need * sizeof(float)) != hipSuccess) return -1;
-      g4.coltab_cap = need;
-    }
-    // the previous launch may still read the old plans - on this stream or on the one the plans were last
-    // used on (the library's own stream and a caller's stream alternate)
+    if (hipGetLastError() != hipSuccess) return -1;
+  }
+  // the first loop's entries per XCD and the boxes' x extents, from the bits of the tables the kernel reads
+  // (eu_share_groups.h): the column plans come back to the host once per plan build
+  std::vector<float> h_ct((size_t)nplans * p.width * EU4_COL_FLOATS);
+  if (nplans) {
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
-    if (g4.last_stream && g4.last_stream != st && hipStreamSynchronize(g4.last_stream) != hipSuccess) return -1;
-    if (hipMemcpy(g4.tileplan, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    g4.planned_rows = 0;
-    for (int v : tp) g4.planned_rows += v >= 0;
-    {
-      // the second loop's rows per XCD: units of EU5_UNIT_ROWS tile rows dealt round-robin, as in the first loop
-      std::vector<int> rows[8];
-      for (int r = 0; r < p.tiles_y; r++) {
-        const int m = r >> 1;
-        const bool paired = 2 * m + 1 < p.tiles_y && tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1];
-        if (!paired) rows[(r / EU5_UNIT_ROWS) & 7].push_back(r);
-      }
-      std::vector<int> all;
-      for (int x = 0; x < 8; x++) { g4.l2_off[x] = (int)all.size(); all.insert(all.end(), rows[x].begin(), rows[x].end()); }
-      g4.l2_off[8] = (int)all.size();
-      if (g4.l2_cap < all.size() + 1) {
-        if (g4.l2_rows) (void)hipFree(g4.l2_rows);
-        g4.l2_rows = nullptr; g4.l2_cap = 0;
-        if (hipMalloc((void **)&g4.l2_rows, (all.size() + 1) * sizeof(int)) != hipSuccess) return -1;
-        g4.l2_cap = all.size() + 1;
-      }
-      if (!all.empty() && hipMemcpy(g4.l2_rows, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-    }
-    for (size_t j = 0; j < plans.size() / 4; j++) {
-      float *ct = g4.coltab + j * (size_t)p.width * EU4_COL_FLOATS;
-      switch (p.src.degree) {
-        case 1: launch_colplan<1>(p, ct, &plans[4 * j], st); break;
-        case 2: launch_colplan<2>(p, ct, &plans[4 * j], st); break;
-        default: launch_colplan<3>(p, ct, &plans[4 * j], st); break;
-      }
-      if (hipGetLastError() != hipSuccess) return -1;
-    }
-    {
-      // the first loop's entries per XCD and the boxes' x extents, from the bits of the tables the kernel reads
-      // (eu_share_groups.h): the column plans come back to the host once per plan build
-      const int nplans = (int)(plans.size() / 4);
-      std::vector<float> h_ct((size_t)nplans * p.width * EU4_COL_FLOATS);
-      if (nplans) {
-        if (hipStreamSynchronize(st) != hipSuccess) return -1;
-        if (hipMemcpy(h_ct.data(), g4.coltab, h_ct.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-      }
-      std::vector<int> cm, cp;
-      for (int m = 0; 2 * m + 1 < p.tiles_y; m++)
-        if (tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1]) { cm.push_back(m); cp.push_back(tp[(size_t)2 * m]); }
-      eu_share_input in;
-      in.width = p.width; in.tiles16 = w.tiles16; in.row_begin = p.row_begin; in.row_end = p.row_end;
-      in.band_mode = p.band_count > 1;
-      in.ncand = (int)cm.size(); in.cand_m = cm.data(); in.cand_plan = cp.data();
-      in.h_row = h_row; in.h_row_floats = h_row_floats; in.row_floats = EU_ROW_FLOATS;
-      in.coltab = nplans ? h_ct.data() : nullptr; in.col_floats = EU4_COL_FLOATS; in.nplans = nplans;
-      in.mode = share_mode; in.unit_drows = EU5_UNIT_ROWS / 2;
-      eu_share_result gr;
-      eu_share_build(in, gr);
-      if (g4.l1_cap < gr.entries.size() + 2) {
-        if (g4.l1_ent) (void)hipFree(g4.l1_ent);
-        g4.l1_ent = nullptr; g4.l1_cap = 0;
-        if (hipMalloc((void **)&g4.l1_ent, (gr.entries.size() + 2) * sizeof(int)) != hipSuccess) return -1;
-        g4.l1_cap = gr.entries.size() + 2;
-      }
-      if (!gr.entries.empty() && hipMemcpy(g4.l1_ent, gr.entries.data(), gr.entries.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-      if (g4.xtab_cap < gr.xtab.size()) {
-        if (g4.xtab) (void)hipFree(g4.xtab);
-        g4.xtab = nullptr; g4.xtab_cap = 0;
-        if (hipMalloc((void **)&g4.xtab, gr.xtab.size() * sizeof(int)) != hipSuccess) return -1;
-        g4.xtab_cap = gr.xtab.size();
-      }
-      if (hipMemcpy(g4.xtab, gr.xtab.data(), gr.xtab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
-      for (int x = 0; x < 9; x++) g4.l1_off[x] = gr.off[x];
-      g4.l1_ecols = gr.ecols;
-      g4.follower_tiles = gr.follower_tiles;
-    }
-    g4.key.swap(key);
+    if (hipMemcpy(h_ct.data(), g4.coltab.p, h_ct.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   }
-  if (only_if_worth && p.src.prj == EU_SPHERICAL) {
-    if (p.src.degree < 2 || g4.planned_rows * 2 < p.tiles_y) return 1;
-  }
-  w.tileplan = g4.tileplan;
-  w.coltab = g4.coltab;
-  w.l2_rows = g4.l2_rows;
+  std::vector<int> cm, cp;
+  for (int m = 0; 2 * m + 1 < p.tiles_y; m++)
+    if (paired(m)) { cm.push_back(m); cp.push_back(tp[(size_t)2 * m]); }
+  eu_share_input in;
+  in.width = p.width; in.tiles16 = tiles16; in.row_begin = p.row_begin; in.row_end = p.row_end;
+  in.band_mode = p.band_count > 1;
+  in.ncand = (int)cm.size(); in.cand_m = cm.data(); in.cand_plan = cp.data();
+  in.h_row = h_row; in.h_row_floats = h_row_floats; in.row_floats = EU_ROW_FLOATS;
+  in.coltab = nplans ? h_ct.data() : nullptr; in.col_floats = EU4_COL_FLOATS; in.nplans = nplans;
+  in.mode = sw.share; in.unit_drows = EU5_UNIT_ROWS / 2;
+  eu_share_result gr;
+  eu_share_build(in, gr);
+  if (!upload(g4.l1_ent, gr.entries, 2)) return -1;
+  if (g4.xtab.reserve(gr.xtab.size()) != hipSuccess) return -1;
+  if (hipMemcpy(g4.xtab.p, gr.xtab.data(), gr.xtab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
+  for (int x = 0; x < 9; x++) g4.l1_off[x] = gr.off[x];
+  g4.l1_ecols = gr.ecols;
+  g4.follower_tiles = gr.follower_tiles;
+  return 0;
+}
+
+// the launch's view of the slot's cache (w.tiles16 and w.atab_g are set)
+void eu4_fill_plan(eu4_plan &w)
+{
+  w.tileplan = g4.tileplan.p;
+  w.coltab = g4.coltab.p;
+  w.l2_rows = g4.l2_rows.p;
   for (int x = 0; x < 9; x++) w.l2_off[x] = g4.l2_off[x];
   w.l2_half = (w.tiles16 + 1) / 2;
   w.l2_magic = (1ull << 40) / (unsigned long long)w.l2_half + 1;
-  w.l1_ent = g4.l1_ent;
+  w.l1_ent = g4.l1_ent.p;
   for (int x = 0; x < 9; x++) w.l1_off[x] = g4.l1_off[x];
   w.l1_ecols = g4.l1_ecols;
   w.l1_magic = (1ull << 40) / (unsigned long long)w.l1_ecols + 1;
-  w.xtab = g4.xtab;
-  eu4_followers_plan = g4.follower_tiles;
-  g4.last_stream = st;
+  w.xtab = g4.xtab.p;
+}
+
+int launch4(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
+{
+  switch (p.nch) {
+    case 3: return launch4_n<3>(p, w, st);
+    case 4: return launch4_n<4>(p, w, st);
+  }
+  return -2;
+}
+
 #ifdef EU5_STAMPS
-  // diagnostic build: stamps of every tile, averaged per pass count / plan kind after the launch
+// diagnostic build: stamps of every tile, averaged per pass count / plan kind after the launch
+int launch4_stamped(const eu_render_params &p, eu4_plan &w, hipStream_t st)
+{
   static unsigned long long *d_st = nullptr; static size_t st_cap = 0; static int dumps = 0;
   const size_t ntile_st = (size_t)w.tiles16 * p.tiles_y * 8;
   const size_t nst = ntile_st + 8192 * 4;      // + per-wave totals (eu_render5_kernel)
   if (st_cap < nst) { if (d_st) (void)hipFree(d_st); if (hipMalloc((void **)&d_st, nst * 8) != hipSuccess) return -1; st_cap = nst; }
   (void)hipMemsetAsync(d_st, 0, nst * 8, st);
   w.stamps = d_st;
-  int rc_ = p.nch == 3 ? launch4_n<3>(p, w, st) : p.nch == 4 ? launch4_n<4>(p, w, st) : 1;
+  const int rc_ = launch4(p, w, st);
   if (rc_ == 0 && dumps < 2 && nst >= 8 * 4096) {
     dumps++;
     std::vector<unsigned long long> h(nst);
@@ -809,11 +754,40 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const float *h_row,
               c >> 4, (c & 15) - 1, cnt[c], acc[c][0] / cnt[c], acc[c][1] / cnt[c], acc[c][2] / cnt[c], acc[c][3] / cnt[c], acc[c][4] / cnt[c], acc[c][5] / cnt[c], acc[c][6] / cnt[c]);
   }
   return rc_;
-#else
-  switch (p.nch) {
-    case 3: return launch4_n<3>(p, w, st);
-    case 4: return launch4_n<4>(p, w, st);
+}
+#endif
+}  // namespace
+
+extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *sw, const float *h_row, size_t h_row_floats,
+                                 unsigned long long plan_gen, void *stream, int *launches)
+{
+  eu_render_params p = *pp;
+  eu4_followers_last = 0;
+  *launches = 2;
+  if (!eu_staged_covers(p) || !p.wl) return -2;
+  p.tiles_y = (p.row_end - p.row_begin + EU4_TH - 1) / EU4_TH;
+  eu4_plan w;
+  w.tiles16 = (p.width + EU4_TW - 1) / EU4_TW;
+  if (w.tiles16 <= 0 || p.tiles_y <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (!ensure_atab()) return -1;
+  w.atab_g = g4.atab;
+  // the plans are cached while nothing they depend on changes (cubemap / biatan6 sources never read the
+  // tile plan: no plans, no upload, no synchronisation for them)
+  if (p.src.prj == EU_SPHERICAL) {
+    std::vector<unsigned char> key = eu4_plan_key(p, plan_gen, sw->share);
+    if (key != g4.key) {
+      if (eu4_build_plans(p, w.tiles16, *sw, h_row, h_row_floats, st)) return -1;
+      g4.key.swap(key);
+    }
+    if (sw->r4 != 1 && !eu_staged_worth(p.src.degree, g4.planned_rows, p.tiles_y)) { *launches = 0; return 0; }
   }
-  return 1;
+  eu4_fill_plan(w);
+  eu4_followers_plan = g4.follower_tiles;
+  g4.last_stream = st;
+#ifdef EU5_STAMPS
+  return launch4_stamped(p, w, st);
+#else
+  return launch4(p, w, st);
 #endif
 }

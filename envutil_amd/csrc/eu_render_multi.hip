@@ -23,26 +23,10 @@
 // loop (readlane makes the index uniform, the lanes that want it go together).
 #include <cstring>
 #include "eu_render_dev.h"
+#include "eu_launch.h"
 
 #define EU_MULTI_MAXF 64     // facets per job the mask-based alpha compositing takes (one bit each); beyond: eu_synopsis_big
 #define EU_MULTI_KEEP 16     // facets whose coordinates are kept in LDS (3 KB each per workgroup)
-
-struct eu_multi_params {
-  int width, height, row_begin, row_end;
-  int form, norm_mode, twine, ntaps, nch, nfct, plus;
-  const float *col;          // [4][width], shared by all facets
-  const float *row;          // [nfct][height][EU_ROW_FLOATS]
-  const float *taps;         // [ntaps][3], x/y scaled by 4
-  const eu_src_dev *srcs;    // [nfct]
-  float *out;
-  long long out_stride;
-  int tiles_x, tiles_y;
-  int band_shift, band_count, band_index;   // eu_frame_row
-  int hdr, hdr_low, hdr_high;               // _hdr_merge_syn: the facets that rule the shadows / the highlights
-  const eu_generic *gen;                    // [nfct] or nullptr: facets stepped by generic_stepper (translation)
-  eu_inv_planar inv;                        // tf22 of a --single job
-  const float *rej;                         // [nfct][EU_REJ_STRIDE] or nullptr: early-miss tables (eu_multi_maybe)
-};
 
 // Early miss, second stage (round 3). The exact hit test of a facet costs ~300 vector instructions (two atan2f,
 // sincosf in double, the lens polynomial, md_to_spline) and config 5 ran it 3.1 times per pixel: for every
@@ -54,9 +38,6 @@ struct eu_multi_params {
 // dropped only when its coordinate lies beyond an edge moved OUT by 0.1 % of the window, far more than float
 // rounding moves it; everything else takes the exact test as before. Header of a facet's table:
 // [0] u0, [1] bins per unit of u, [2] 0 = no table, [4] [5] shift, [6]..[9] the edges x0 x1 y0 y1 moved out.
-#define EU_REJ_N 1024
-#define EU_REJ_HDR 16
-#define EU_REJ_STRIDE (EU_REJ_HDR + EU_REJ_N)
 __device__ __forceinline__ bool eu_multi_maybe(const eu_multi_params &p, int f, const eu_src_dev &s, float rx, float ry, float rz)
 {
   const float n2 = rx * rx + ry * ry, n3 = n2 + rz * rz;
@@ -665,14 +646,9 @@ extern "C" int EU_CAT(eu_launch_render_multi_nch, EU_MULTI_NCH)(const eu_multi_p
   return launch_multi_n<EU_MULTI_NCH, plus>(*p, degree, (hipStream_t)stream);
 }
 #else
-extern "C" int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stream);
-extern "C" int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);
-extern "C" int eu_launch_render_multi_nch3(const eu_multi_params *p, int degree, void *stream);
-extern "C" int eu_launch_render_multi_nch4(const eu_multi_params *p, int degree, void *stream);
-
-extern "C" int eu_launch_render_multi(const void *pp, int degree, void *stream)
+extern "C" int eu_launch_render_multi(const eu_multi_params *pp, int degree, void *stream)
 {
-  eu_multi_params p = *(const eu_multi_params *)pp;
+  eu_multi_params p = *pp;
   // voronoi_syn and hdr_merge keep no per-facet state; alpha compositing beyond 64 facets: eu_synopsis_big
   p.tiles_x = (p.width + EU_TILE_W - 1) / EU_TILE_W;
   p.tiles_y = (p.row_end - p.row_begin + EU_TILE_H - 1) / EU_TILE_H;

@@ -1,0 +1,175 @@
+// How a single-facet job finds its kernel, and the EU_HIP_* switches that can change the answer.
+// Plain C++ (no HIP): eu_api.hip and the launchers include it, and so does a host test program
+// (tests/csrc/select_demo.cc).
+//
+//   general          eu_render.hip    one pixel per lane, every job
+//   general, direct  the same with the inline evaluation: --mask_for jobs paint the facet there
+//   packed           eu_render2.hip   two pixels per lane, direct gathers (eu_packed_covers)
+//   packed in runs   the same, one launch per run of rows that want the same work layout
+//   staged           eu_render4.hip   LDS-staged tiles plus the direct-gather kernel behind them
+//                                     (eu_staged_covers), two launches
+#ifndef EU_SELECT_H
+#define EU_SELECT_H
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
+#include <vector>
+#include "eu_device.h"
+#include "eu_share_groups.h"
+
+// ---- the switches ------------------------------------------------------------------------------
+// One field per EU_HIP_* variable the library reads. eu_read_switches() is the only reader: every
+// entry point calls it once and hands the result down, so all of them are read on every call.
+struct eu_switches {
+  int force_general;   // EU_HIP_KERNEL=1: the general kernel for every job (A/B switch)
+  int hybrid;          // EU_HIP_HYBRID: 0 never split a frame into runs, 2 split wherever the layouts differ (tests); else 1
+  int r4;              // EU_HIP_R4: 0 never the staged kernels, 1 wherever they apply (tests, A/B runs); unset: -1
+  int colmajor;        // EU_HIP_COLMAJOR: 0 / non-zero forces the packed kernel's walk; unset or empty: -1
+  int rej;             // EU_HIP_REJ: 1 the early-miss tables of a multi-facet job, 2 their table-free form; else 0
+  int colplan;         // EU_HIP_COLPLAN=0: no column plans (0); else 1
+  int share;           // EU_HIP_SHARE: EU_SHARE_* bits - 0: none, m: mirrors, f: faces; else both
+  int direct;          // EU_HIP_DIRECT=1: the general kernel never stages through LDS
+  int iir_stream;      // EU_HIP_IIR_STREAM: bit 0 rows, bit 1 columns, bit 2 checkpoints; unset: 7
+};
+
+inline eu_switches eu_read_switches()
+{
+  auto first = [](const char *name) { const char *e = getenv(name); return e ? e[0] : '\0'; };
+  eu_switches s;
+  s.force_general = first("EU_HIP_KERNEL") == '1';
+  const char hy = first("EU_HIP_HYBRID");
+  s.hybrid = hy == '0' ? 0 : hy == '2' ? 2 : 1;
+  const char *r4 = getenv("EU_HIP_R4");
+  s.r4 = r4 ? atoi(r4) : -1;
+  const char *cm = getenv("EU_HIP_COLMAJOR");
+  s.colmajor = cm && cm[0] ? atoi(cm) : -1;
+  const char rj = first("EU_HIP_REJ");
+  s.rej = rj == '1' ? 1 : rj == '2' ? 2 : 0;
+  s.colplan = first("EU_HIP_COLPLAN") != '0';
+  const char sh = first("EU_HIP_SHARE");
+  s.share = sh == '0' ? 0 : sh == 'm' ? EU_SHARE_MIRRORS : sh == 'f' ? EU_SHARE_FACES : EU_SHARE_FACES | EU_SHARE_MIRRORS;
+  s.direct = first("EU_HIP_DIRECT") == '1';
+  const char *iir = getenv("EU_HIP_IIR_STREAM");
+  s.iir_stream = iir ? atoi(iir) : 7;
+  return s;
+}
+
+// ---- coverage ----------------------------------------------------------------------------------
+inline bool eu_cube_source(int prj) { return prj == EU_CUBEMAP || prj == EU_BIATAN6; }
+
+// the packed two-pixel kernels (eu_render2.hip): table-driven forms on lat/lon and cube sources
+inline bool eu_packed_covers(const eu_render_params &p)
+{
+  if (p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return false;
+  if (p.src.prj != EU_SPHERICAL && !eu_cube_source(p.src.prj)) return false;
+  if (p.src.degree < 1 || p.src.degree > 3 || p.src.es0 != p.nch) return false;
+  return p.nch >= 1 && p.nch <= 4;
+}
+
+// the staged kernels (eu_render4.hip): 16x8 wave tiles, at most 65535 * 8 units of 4 tile rows
+#define EU_STAGED_TILE_ROWS 8
+#define EU_STAGED_MAX_TILES_Y (65535 * 8 * 4)
+inline bool eu_staged_covers(const eu_render_params &p)
+{
+  if (!eu_packed_covers(p) || p.twine) return false;
+  if (p.norm_mode != EU_NORM_NONE && p.norm_mode != EU_NORM_DIV) return false;
+  if (p.nch != 3 && p.nch != 4) return false;
+  if (p.src.es1 * 4 >= (1ll << 31)) return false;            // the staging offsets are 32-bit
+  return (p.row_end - p.row_begin + EU_STAGED_TILE_ROWS - 1) / EU_STAGED_TILE_ROWS <= EU_STAGED_MAX_TILES_Y;
+}
+
+// 'ray = B * c0 + A' without normalisation over the whole frame, on a source every finite ray hits
+inline bool eu_plain_ba(const eu_render_params &p)
+{
+  return p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && p.band_count <= 1 && p.src.brighten == 1.0f &&
+         p.src.always_hit;
+}
+
+// lat/lon jobs that go to the staged kernels without being asked to: cubic / quadratic jobs whose target
+// can have column plans (an upright cubemap or rectilinear target)
+inline bool eu_staged_default(const eu_render_params &p)
+{
+  return p.src.prj == EU_SPHERICAL && p.src.degree >= 2 && !p.twine && eu_plain_ba(p);
+}
+
+// the FAST form of the persistent staged kernel (eu_render5.h), for a lat/lon job eu_staged_covers():
+// eu_div2_rr's range - the divisor in [2^-20, 2^20], the extent's origin 0 or in that range (so that a
+// non-zero difference 'angle - origin' is at least 2^-73) - and finite stepper tables
+inline bool eu_staged_fast_profile(const eu_render_params &p)
+{
+  auto mag_ok = [](double v) { const double a = v < 0 ? -v : v; return a == 0.0 || (a >= 0x1p-20 && a <= 0x1p20); };
+  return eu_plain_ba(p) && mag_ok(p.src.tex_x0) && mag_ok(p.src.tex_y0) && p.src.ext_w >= 0x1p-20f &&
+         p.src.ext_w <= 0x1p20f && p.src.ext_h >= 0x1p-20f && p.src.ext_h <= 0x1p20f && p.tab_finite;
+}
+
+// Known only once the column plans of a lat/lon job exist: the staged kernels measured faster than the
+// direct-gather ones for cubic / quadratic jobs with column plans on at least half of the tile rows
+// (DESIGN.md 5). Not asked under EU_HIP_R4=1, nor for cube sources.
+inline bool eu_staged_worth(int degree, int planned_rows, int tiles_y)
+{
+  return degree >= 2 && planned_rows * 2 >= tiles_y;
+}
+
+// ---- the decision ------------------------------------------------------------------------------
+enum eu_path { EU_PATH_GENERAL, EU_PATH_GENERAL_DIRECT, EU_PATH_PACKED, EU_PATH_PACKED_RUNS, EU_PATH_STAGED };
+
+// staged_allowed = false: the answer for a job whose plan said no to eu_staged_worth().
+// EU_PATH_PACKED_RUNS: the job is split where eu_split_runs() finds runs, and is one packed launch otherwise.
+inline eu_path eu_select_path(const eu_render_params &p, const eu_switches &sw, bool staged_allowed = true)
+{
+  // a --mask_for job paints the facet at the inner evaluation: only the general kernel does that
+  if (p.src.mask_paint) return EU_PATH_GENERAL_DIRECT;
+  if (sw.force_general) return EU_PATH_GENERAL;
+  // Measured: the staged kernels win where the taps dominate and the tile boxes are small - cubic /
+  // quadratic jobs on cube sources (config 3: 1.13 -> 0.99 ms) and, in their persistent form, on lat/lon sources
+  // whose target has column plans (the headline) - and lose to the direct-gather kernels on bilinear jobs
+  const bool want_staged = sw.r4 == 1 || (sw.r4 != 0 && p.src.degree >= 2 && (eu_cube_source(p.src.prj) || eu_staged_default(p)));
+  if (staged_allowed && want_staged && eu_staged_covers(p)) return EU_PATH_STAGED;
+  if (!eu_packed_covers(p)) return EU_PATH_GENERAL;
+  // the two work layouts of the packed kernel differ on lat/lon sources only, and a 0.2 ms bilinear job
+  // has little to gain from more launches; EU_HIP_HYBRID=2 lifts that limit (tests)
+  const bool worth = sw.hybrid == 2 || p.src.degree >= 2;
+  if (sw.hybrid && worth && !p.twine && p.norm_mode == EU_NORM_NONE && p.src.prj == EU_SPHERICAL) return EU_PATH_PACKED_RUNS;
+  return EU_PATH_PACKED;
+}
+
+// ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------
+// The frame is cut into segments of EU_SEG_ROWS rows; flags[k] != 0 where segment k renders faster with
+// 32x16 tiles than with 128x4 row strips (eu_api.hip: refresh_seg_flags).
+#define EU_SEG_ROWS 512
+
+struct eu_run { int row_begin, row_end, layout; };     // local rows; layout 1 row strips, 2 tiles
+
+// Runs of local rows whose segments want the same layout, in chunks of 64 rows. Empty: one launch for
+// the whole job. Every run is a launch of its own, so only a few long runs are worth it (the whole
+// frame: 5; a contiguous strip of a split: 1-3), not the many short ones of a band-interleaved share
+// (0.18 -> 0.21 ms when split up); any = true (EU_HIP_HYBRID=2) lifts the limits.
+inline std::vector<eu_run> eu_split_runs(const unsigned char *flags, int nflags, const eu_render_params &p, bool any)
+{
+  std::vector<eu_run> runs;
+  bool mixed = false;
+  for (int k = 0; k < nflags; k++) mixed = mixed || flags[k];
+  if (!mixed) return runs;
+  auto flag_of = [&](int r) {
+    const int fy = eu_frame_row(std::min(r, p.row_end - 1), p.band_shift, p.band_count, p.band_index);
+    return (int)flags[std::min(fy / EU_SEG_ROWS, nflags - 1)];
+  };
+  auto run_end = [&](int a, int fl) {
+    int b = std::min((a / 64 + 1) * 64, p.row_end);
+    while (b < p.row_end && flag_of(b) == fl) b = std::min(b + 64, p.row_end);
+    return b;
+  };
+  int tiled = 0, shortest = INT_MAX;
+  for (int a = p.row_begin; a < p.row_end;) {
+    const int fl = flag_of(a), b = run_end(a, fl);
+    tiled += fl;
+    shortest = std::min(shortest, b - a);
+    runs.push_back({ a, b, fl ? 2 : 1 });
+    a = b;
+  }
+  const int nruns = (int)runs.size();
+  if (!(tiled > 0 && (any || nruns <= 3 || (nruns <= 5 && shortest >= EU_SEG_ROWS)))) runs.clear();
+  return runs;
+}
+
+#endif

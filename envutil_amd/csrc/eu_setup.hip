@@ -15,6 +15,7 @@
 #include "eu_device.h"
 #include "eu_setup_math.h"
 #include "eu_math.h"
+#include "eu_launch.h"
 
 namespace {
 
@@ -967,13 +968,9 @@ void launch_brace(float *container, long long SX, long long SY, int nch, int axi
                      SX, SY, nch, axis, bc, lsz, rsz);
 }
 
-// EU_HIP_IIR_STREAM=0: the one-thread-per-line kernels only (the form the streamed ones are
-// checked against on the device, tests/test_gpu_prefilter_stream.py)
-int iir_stream_on()   // bit 0: rows, bit 1: columns, bit 2: checkpoints + recomputation (3 passes per axis)
-{
-  const char *e = getenv("EU_HIP_IIR_STREAM");
-  return e ? atoi(e) : 7;
-}
+// `iir` below is eu_switches::iir_stream (EU_HIP_IIR_STREAM) - bit 0: rows, bit 1: columns, bit 2: checkpoints +
+// recomputation (3 passes per axis); 0: the one-thread-per-line kernels only (the form the streamed ones
+// are checked against on the device, tests/test_gpu_prefilter_stream.py)
 
 // lines per wavefront: few, so that the lines of a large image make more wavefronts than the
 // chip has SIMDs (1024) and a SIMD has two recursions to alternate between
@@ -983,9 +980,9 @@ constexpr int IIR_COLS = 32;   // adjacent floats of the column sweeps
 // Scratch for the checkpoints of the streamed sweeps (stream_causal): groups x blocks x 64 floats,
 // stream-ordered allocation. Only when every pole's horizon lies inside the first block (iacc
 // reads the causal result of that many samples) and EU_HIP_IIR_STREAM has bit 2 set.
-float *iir_ckpt_alloc(const iir_dev &f, long long groups, int len, hipStream_t st)
+float *iir_ckpt_alloc(const iir_dev &f, long long groups, int len, int iir, hipStream_t st)
 {
-  if (!(iir_stream_on() & 4) || len / 64 < 3) return nullptr;
+  if (!(iir & 4) || len / 64 < 3) return nullptr;
   for (int k = 0; k < f.npoles; k++) if (f.horizon[k] >= 64) return nullptr;
   void *p = nullptr;
   if (hipMallocAsync(&p, (size_t)groups * (size_t)(len / 64) * 64 * sizeof(float), st) != hipSuccess) {
@@ -1007,10 +1004,10 @@ void launch_stream(K kernel, unsigned groups, size_t wave_lds, hipStream_t st, A
 }
 
 template <int NCH>
-unsigned launch_rows_nch(const iir_dev &f, float *base, long long nl, long long line_stride, int len, hipStream_t st)
+unsigned launch_rows_nch(const iir_dev &f, float *base, long long nl, long long line_stride, int len, int iir, hipStream_t st)
 {
   const unsigned groups = (unsigned)(nl / IIR_ROWS);
-  float *ck = iir_ckpt_alloc(f, groups, len, st);
+  float *ck = iir_ckpt_alloc(f, groups, len, iir, st);
   launch_stream(filter_rows_stream_kernel<NCH, IIR_ROWS>, groups,
                 sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_rows<NCH, IIR_ROWS>>::BUF, st, f, base, line_stride, len, ck);
   iir_ckpt_free(ck, st);
@@ -1019,16 +1016,16 @@ unsigned launch_rows_nch(const iir_dev &f, float *base, long long nl, long long 
 
 // nl rows of len samples x nch channels (es = nch), rows line_stride floats apart
 void launch_filter_rows(const iir_dev &f, float *base, long long nl, int nch, long long line_stride,
-                        int len, hipStream_t st)
+                        int len, int iir, hipStream_t st)
 {
   long long done = 0;
-  if ((iir_stream_on() & 1) && len >= 64 && nch >= 1 && nch <= 4 && nl >= IIR_ROWS) {
+  if ((iir & 1) && len >= 64 && nch >= 1 && nch <= 4 && nl >= IIR_ROWS) {
     unsigned groups;
     switch (nch) {
-      case 1: groups = launch_rows_nch<1>(f, base, nl, line_stride, len, st); break;
-      case 2: groups = launch_rows_nch<2>(f, base, nl, line_stride, len, st); break;
-      case 3: groups = launch_rows_nch<3>(f, base, nl, line_stride, len, st); break;
-      default: groups = launch_rows_nch<4>(f, base, nl, line_stride, len, st);
+      case 1: groups = launch_rows_nch<1>(f, base, nl, line_stride, len, iir, st); break;
+      case 2: groups = launch_rows_nch<2>(f, base, nl, line_stride, len, iir, st); break;
+      case 3: groups = launch_rows_nch<3>(f, base, nl, line_stride, len, iir, st); break;
+      default: groups = launch_rows_nch<4>(f, base, nl, line_stride, len, iir, st);
     }
     done = (long long)groups * IIR_ROWS;
   }
@@ -1038,12 +1035,12 @@ void launch_filter_rows(const iir_dev &f, float *base, long long nl, int nch, lo
 }
 
 // nfloats adjacent columns (every float of a row is a line of its own), rows es floats apart
-void launch_filter_cols(const iir_dev &f, float *base, long long nfloats, long long es, int len, hipStream_t st)
+void launch_filter_cols(const iir_dev &f, float *base, long long nfloats, long long es, int len, int iir, hipStream_t st)
 {
   long long done = 0;
-  if ((iir_stream_on() & 2) && len >= 64 && nfloats >= IIR_COLS) {
+  if ((iir & 2) && len >= 64 && nfloats >= IIR_COLS) {
     const unsigned groups = (unsigned)(nfloats / IIR_COLS);
-    float *ck = iir_ckpt_alloc(f, groups, len, st);
+    float *ck = iir_ckpt_alloc(f, groups, len, iir, st);
     launch_stream(filter_cols_stream_kernel<IIR_COLS>, groups,
                   sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<IIR_COLS, false>>::BUF, st, f, base, es, len, ck);
     iir_ckpt_free(ck, st);
@@ -1055,12 +1052,12 @@ void launch_filter_cols(const iir_dev &f, float *base, long long nfloats, long l
 }
 
 // environment.h:395-447: column t top -> bottom, then column t + down_off bottom -> top
-void launch_filter_stacked(const iir_dev &f, float *core, long long nfloats, long long row_es, int H, hipStream_t st)
+void launch_filter_stacked(const iir_dev &f, float *core, long long nfloats, long long row_es, int H, int iir, hipStream_t st)
 {
   long long done = 0;
-  if ((iir_stream_on() & 2) && 2 * H >= 64 && nfloats >= IIR_COLS) {
+  if ((iir & 2) && 2 * H >= 64 && nfloats >= IIR_COLS) {
     const unsigned groups = (unsigned)(nfloats / IIR_COLS);
-    float *ck = iir_ckpt_alloc(f, groups, 2 * H, st);
+    float *ck = iir_ckpt_alloc(f, groups, 2 * H, iir, st);
     launch_stream(filter_stacked_stream_kernel<IIR_COLS>, groups,
                   sizeof(float) * EU_IIR_BUFS * iir_bufs<tile_cols<IIR_COLS, true>>::BUF, st, f, core, nfloats, row_es, H, ck);
     iir_ckpt_free(ck, st);
@@ -1074,7 +1071,7 @@ void launch_filter_stacked(const iir_dev &f, float *core, long long nfloats, lon
 }  // namespace
 
 extern "C" int eu_launch_prefilter(float *container, const eu_container *g, int nch, int bc0,
-                                   int bc1, int degree, int spherical, void *stream)
+                                   int bc1, int degree, int spherical, int iir, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
   const long long W = g->core[0], H = g->core[1], SX = g->shape[0], SY = g->shape[1];
@@ -1083,9 +1080,9 @@ extern "C" int eu_launch_prefilter(float *container, const eu_container *g, int 
     // environment.h:356-522
     if (degree > 1) {
       iir_dev f = make_iir(EU_BC_PERIODIC, degree, 0.0001L, W);
-      launch_filter_rows(f, core, H, nch, SX * nch, (int)W, st);
+      launch_filter_rows(f, core, H, nch, SX * nch, (int)W, iir, st);
       iir_dev f2 = make_iir(EU_BC_PERIODIC, degree, 0.0001L, 2 * H);
-      launch_filter_stacked(f2, core, (W / 2) * nch, SX * nch, (int)H, st);
+      launch_filter_stacked(f2, core, (W / 2) * nch, SX * nch, (int)H, iir, st);
     }
     long long n = (g->left[1] + g->right[1]) * W * nch;
     const long long vfr = g->left[1] > g->right[1] ? g->left[1] : g->right[1];
@@ -1102,9 +1099,9 @@ extern "C" int eu_launch_prefilter(float *container, const eu_container *g, int 
   // bspline::prefilter, zimt/bspline.h:1017-1041 + prefilter.h:133-190
   if (degree > 1) {
     iir_dev f0 = make_iir(bc0, degree, (long double)FLT_EPSILON, W);
-    launch_filter_rows(f0, core, H, nch, SX * nch, (int)W, st);
+    launch_filter_rows(f0, core, H, nch, SX * nch, (int)W, iir, st);
     iir_dev f1 = make_iir(bc1, degree, (long double)FLT_EPSILON, H);
-    launch_filter_cols(f1, core, W * nch, SX * nch, (int)H, st);
+    launch_filter_cols(f1, core, W * nch, SX * nch, (int)H, iir, st);
   }
   launch_brace(container, SX, SY, nch, 0, bc0, (long long)g->left[0], (long long)g->right[0], st);
   launch_brace(container, SX, SY, nch, 1, bc1, (long long)g->left[1], (long long)g->right[1], st);
@@ -1113,7 +1110,7 @@ extern "C" int eu_launch_prefilter(float *container, const eu_container *g, int 
 
 extern "C" int eu_launch_cubemap_build(const float *faces, float *ir, int nch, long F, long S,
                                        long lf, long rf, double refc_md, double model_to_px,
-                                       int prefilter_degree, void *stream)
+                                       int prefilter_degree, int iir, void *stream)
 {
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(place_faces_kernel, dim3(blocks_for(6LL * F * F * nch, 256)), dim3(256), 0,
@@ -1140,9 +1137,9 @@ extern "C" int eu_launch_cubemap_build(const float *faces, float *ir, int nch, l
   if (prefilter_degree > 1) {
     // cubemap.h:921-946: per section, NATURAL x NATURAL, default tolerance
     iir_dev f = make_iir(EU_BC_NATURAL, prefilter_degree, (long double)FLT_EPSILON, S);
-    launch_filter_rows(f, ir, 6LL * S, nch, (long long)S * nch, (int)S, st);
+    launch_filter_rows(f, ir, 6LL * S, nch, (long long)S * nch, (int)S, iir, st);
     for (int face = 0; face < 6; face++)
-      launch_filter_cols(f, ir + (long long)face * S * S * nch, (long long)S * nch, (long long)S * nch, (int)S, st);
+      launch_filter_cols(f, ir + (long long)face * S * S * nch, (long long)S * nch, (long long)S * nch, (int)S, iir, st);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

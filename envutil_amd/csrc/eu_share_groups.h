@@ -20,7 +20,7 @@
 #define EU_SHARE_ENTRY_INTS (2 + 2 * EU_SHARE_MAX_MEMBERS)
 #define EU_SHARE_MIRROR (1 << 30)
 #define EU_SHARE_FACES 1        // mode bits: double rows of other faces may follow a leader
-#define EU_SHARE_MIRRORS 2      //            the column mirror of a double row may
+#define EU_SHARE_MIRRORS 2      //            a double row mirrored column for column may
 
 struct eu_share_input {
   int width, tiles16;           // frame width, 16-pixel tile columns
