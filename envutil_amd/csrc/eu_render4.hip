@@ -124,6 +124,7 @@ struct eu4_plan {
   int l1_ecols;
   unsigned long long l1_magic;
   const int *xtab;        // [plan][tiles16] { min, max } of the column entries' base position ix; min = INT_MAX: not fast
+  const int *boxtab;      // the second loop's tile boxes (eu_render5.h: EU5_BT_RECS records per tile of the rows in l2_rows); null: none
 #ifdef EU5_STAMPS
   unsigned long long *stamps;   // diagnostic build: 8 s_memtime stamps per tile of eu_render5_kernel
 #endif
@@ -463,6 +464,12 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
 // follower tiles (eu_share_groups.h) of the plan about to be launched / of the last launch of eu_render5_kernel's FAST form
 static long long eu4_followers_plan = 0, eu4_followers_last = 0;
 extern "C" unsigned long long eu_hip_share_follower_tiles(void) { return (unsigned long long)eu4_followers_last; }
+// whether the last launch of eu_render5_kernel's FAST form read a box table (1, also for one of zero tiles) or not (0),
+// and the tiles that table holds
+static int eu4_boxtab_last = 0;
+static long long eu4_boxtab_tiles_last = 0;
+extern "C" int eu_hip_boxtab_used(void) { return eu4_boxtab_last; }
+extern "C" unsigned long long eu_hip_boxtab_tiles(void) { return (unsigned long long)eu4_boxtab_tiles_last; }
 
 #ifndef EU4_DIRECT_WGS
 #define EU4_DIRECT_WGS 2048
@@ -482,8 +489,13 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
       return n;
     }();
     const bool fast = eu_staged_fast_profile(p);
+    // (eu5_tile_bt stores through 32-bit buffer offsets: eight rows of the output below 2^31 bytes)
+    const bool bt = fast && w.boxtab != nullptr && p.out_stride < (1ll << 25);
     int per_cu = 0;
-    if (fast) {
+    if (bt) {
+      static const int occ = [] { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, eu_render5_kernel<NCH, DEG, PRJ, true, true>, 64 * EU5_WAVES, 0) == hipSuccess ? n : 0; }();
+      per_cu = occ;
+    } else if (fast) {
       static const int occ = [] { int n = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, eu_render5_kernel<NCH, DEG, PRJ, true>, 64 * EU5_WAVES, 0) == hipSuccess ? n : 0; }();
       per_cu = occ;
     } else {
@@ -493,7 +505,9 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
     const int wgs = (cus / 8) * 8 * per_cu;
     if (wgs <= 0) return -1;
     if (fast) eu4_followers_last = eu4_followers_plan;
-    if (fast) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
+    eu4_boxtab_last = bt;
+    if (bt) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
+    else if (fast) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
     else hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, false>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
   } else {
     const int units = (p.tiles_y + EU4_UNIT_ROWS - 1) / EU4_UNIT_ROWS;
@@ -550,7 +564,9 @@ static_assert(EU_STAGED_TILE_ROWS == EU4_TH && EU_STAGED_MAX_TILES_Y == 65535 * 
 namespace {
 struct plan_cache {
   std::vector<unsigned char> key;
-  eu_dev_buf<int> tileplan, l2_rows, l1_ent, xtab;
+  eu_dev_buf<int> tileplan, l2_rows, l1_ent, xtab, boxtab;
+  bool has_boxtab = false;   // the second loop's box table exists (it may hold no tile)
+  long long boxtab_tiles = 0;
   eu_dev_buf<float> coltab;
   float *atab = nullptr;
   int planned_rows = 0;      // tile rows with a column plan
@@ -580,14 +596,15 @@ void launch_colplan(const eu_render_params &p, float *ct, const float *k, hipStr
 }
 
 // everything the cached plans depend on
-std::vector<unsigned char> eu4_plan_key(const eu_render_params &p, unsigned long long plan_gen, int share_mode)
+std::vector<unsigned char> eu4_plan_key(const eu_render_params &p, unsigned long long plan_gen, const eu_switches &sw)
 {
-  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 9 * sizeof(int));
+  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 11 * sizeof(int));
   unsigned char *q = key.data();
   memcpy(q, &plan_gen, sizeof plan_gen); q += sizeof plan_gen;
   eu_src_dev sd = p.src; sd.base = nullptr;
   memcpy(q, &sd, sizeof sd); q += sizeof sd;
-  const int v[9] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, share_mode };
+  const int v[11] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, sw.share,
+                      sw.boxtab, sw.boxtab_max_kb };
   memcpy(q, v, sizeof v);
   return key;
 }
@@ -596,6 +613,13 @@ bool upload(eu_dev_buf<int> &buf, const std::vector<int> &v, size_t spare)
 {
   if (buf.reserve(v.size() + spare) != hipSuccess) return false;
   return v.empty() || hipMemcpy(buf.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+template <int DEG>
+void launch_boxplan(const eu_render_params &p, const float *atab_g, const int *l2_rows, int tiles16, int ntiles, int *tab, hipStream_t st)
+{
+  hipLaunchKernelGGL((eu5_boxplan_kernel<DEG>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, atab_g, l2_rows, tiles16,
+                     ntiles, tab);
 }
 
 // the plans of a lat/lon job into the slot's cache: the tile rows' plan ids, the second loop's rows, the column
@@ -649,6 +673,26 @@ int eu4_build_plans(const eu_render_params &p, int tiles16, const eu_switches &s
     g4.l2_off[8] = (int)all.size();
     if (!upload(g4.l2_rows, all, 1)) return -1;
   }
+  // the second loop's box table (eu_render5.h), for the FAST form - the only reader: one wave per tile of those rows,
+  // on the stream the plans are built on. A table beyond sw.boxtab_max_kb is not built: the job takes the loop that
+  // reduces its boxes per frame.
+  g4.has_boxtab = false; g4.boxtab_tiles = 0;
+  if (sw.boxtab && eu_staged_fast_profile(p)) {
+    const long long ntiles = (long long)g4.l2_off[8] * tiles16;
+    const long long bytes = ntiles * (EU5_BT_RECS * 16);
+    if (bytes <= (long long)sw.boxtab_max_kb * 1024) {
+      if (g4.boxtab.reserve((size_t)std::max<long long>(1, ntiles) * (EU5_BT_RECS * 4)) != hipSuccess) return -1;
+      if (ntiles > 0) {
+        switch (p.src.degree) {
+          case 1: launch_boxplan<1>(p, g4.atab, g4.l2_rows.p, tiles16, (int)ntiles, g4.boxtab.p, st); break;
+          case 2: launch_boxplan<2>(p, g4.atab, g4.l2_rows.p, tiles16, (int)ntiles, g4.boxtab.p, st); break;
+          default: launch_boxplan<3>(p, g4.atab, g4.l2_rows.p, tiles16, (int)ntiles, g4.boxtab.p, st); break;
+        }
+        if (hipGetLastError() != hipSuccess) return -1;
+      }
+      g4.has_boxtab = true; g4.boxtab_tiles = ntiles;
+    }
+  }
   for (int j = 0; j < nplans; j++) {
     float *ct = g4.coltab.p + j * (size_t)p.width * EU4_COL_FLOATS;
     switch (p.src.degree) {
@@ -700,6 +744,7 @@ void eu4_fill_plan(eu4_plan &w)
   w.l1_ecols = g4.l1_ecols;
   w.l1_magic = (1ull << 40) / (unsigned long long)w.l1_ecols + 1;
   w.xtab = g4.xtab.p;
+  w.boxtab = g4.has_boxtab ? g4.boxtab.p : nullptr;
 }
 
 int launch4(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
@@ -763,6 +808,7 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
 {
   eu_render_params p = *pp;
   eu4_followers_last = 0;
+  eu4_boxtab_last = 0; eu4_boxtab_tiles_last = 0;
   *launches = 2;
   if (!eu_staged_covers(p) || !p.wl) return -2;
   p.tiles_y = (p.row_end - p.row_begin + EU4_TH - 1) / EU4_TH;
@@ -775,7 +821,7 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
   // the plans are cached while nothing they depend on changes (cubemap / biatan6 sources never read the
   // tile plan: no plans, no upload, no synchronisation for them)
   if (p.src.prj == EU_SPHERICAL) {
-    std::vector<unsigned char> key = eu4_plan_key(p, plan_gen, sw->share);
+    std::vector<unsigned char> key = eu4_plan_key(p, plan_gen, *sw);
     if (key != g4.key) {
       if (eu4_build_plans(p, w.tiles16, *sw, h_row, h_row_floats, st)) return -1;
       g4.key.swap(key);
@@ -784,6 +830,7 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
   }
   eu4_fill_plan(w);
   eu4_followers_plan = g4.follower_tiles;
+  eu4_boxtab_tiles_last = w.boxtab ? g4.boxtab_tiles : 0;
   g4.last_stream = st;
 #ifdef EU5_STAMPS
   return launch4_stamped(p, w, st);

@@ -205,6 +205,117 @@ __device__ __forceinline__ void eu5_load8(const eu_render_params &p, int tile_y,
   T.c0 = (eu_f2){ p.col[xac], p.col[xbc] };
 }
 
+// ---------------------------------------------------------------------------
+// The geometry of a 16x8 tile without a column plan (FAST profile, lat/lon source) as functions: what eu5_tile's
+// !HOIST FAST form does in line, operation for operation in the same order, no contraction - the same bits.
+// eu5_boxplan_kernel (which fills the second loop's box table) and eu5_tile_bt (which renders from it) compile
+// THIS source, so the table's boxes are the boxes of the coordinates the render computes; eu5_tile itself keeps
+// its text: rewritten on these functions its allocation gains 48 bytes of scratch (60 / 68 against 12 / 20 for
+// <3,3> / <4,3>: kernel arguments the allocator parks in a stack slot and reloads in the coordinate stage), and
+// it is the form EU_HIP_BOXTAB=0 measures the table against. tests/test_gpu_boxtab.py holds the three to one frame.
+// ---------------------------------------------------------------------------
+struct eu5_co8 {
+  eu_f2 tx, ty;               // the fractions of both pixels (ty: the gated y coordinate until eu5_split_y)
+  int ixa, ixb, iya, iyb;     // their base positions
+  eu_i2 ok;                   // 0 for a pixel that left the fast path of the coordinate arithmetic
+};
+
+// the reference's operations in the reference's order (stepper.h ray, geometry.h:278-301,
+// environment.h:988-1006, map.h gates) in their leanest instruction forms (eu_math2.h, round 3)
+template <int DEG>
+__device__ __forceinline__ void eu5_coords8(const eu_src_dev &s, const float *atab, const eu5_tab8 &T, eu5_co8 &c)
+{
+  eu_i2 big0 = { 0, 0 }, big1 = { 0, 0 };
+  const eu_f2 c0 = T.c0;
+  const eu_f2 rx = T.B0 * c0 + T.A0, ry = T.B1 * c0 + T.A1, rz = T.B2 * c0 + T.A2;
+  const eu_i2 ok = { ~eu5_out_of_range3(rx.x, ry.x, rz.x), ~eu5_out_of_range3(rx.y, ry.y, rz.y) };
+  const eu_f2 q2 = rx * rx + rz * rz;
+  const eu_f2 qs = eu_sqrt2_safe(q2);
+  const eu_f2 lat = eu_atan2f_2_lean(ry, qs, atab, 1, big0);
+  const eu_f2 lon = eu_atan2f_2_lean(rx, rz, atab, 0, big1);
+  c.ok = ok & ~(big0 | big1);
+  eu_f2 i0 = { (float)((double)lon.x - s.tex_x0), (float)((double)lon.y - s.tex_x0) };
+  if (s.cdiv_ok) i0 = eu_div2_const(i0, s.ext_w, s.rcp_ext_w);
+  else i0 = eu_div2_rr(i0, s.ext_w, eu_rcp_refined(s.ext_w));
+  i0 = i0 * s.total_w; i0 = i0 - .5f;
+  const eu_f2 sx = i0 - s.win_x_off;
+  const eu_f2 gx = eu5_gate2(sx, s.gate0, s.lower0, s.upper0);
+  eu_f2 fx;
+  if constexpr (DEG & 1) fx = (eu_f2){ floorf(gx.x), floorf(gx.y) };
+  else fx = (eu_f2){ roundf(gx.x), roundf(gx.y) };
+  c.tx = gx - fx;
+  c.ixa = (int)fx.x; c.ixb = (int)fx.y;
+  eu_f2 i1 = { (float)((double)lat.x - s.tex_y0), (float)((double)lat.y - s.tex_y0) };
+  if (s.cdiv_ok) i1 = eu_div2_const(i1, s.ext_h, s.rcp_ext_h);
+  else i1 = eu_div2_rr(i1, s.ext_h, eu_rcp_refined(s.ext_h));
+  i1 = i1 * s.total_h; i1 = i1 - .5f;
+  const eu_f2 sy = i1 - s.win_y_off;
+  c.ty = eu5_gate2(sy, s.gate1, s.lower1, s.upper1);
+}
+
+// the y half of the split: c.ty holds the gated coordinate and becomes its fraction
+template <int DEG>
+__device__ __forceinline__ void eu5_split_y(eu5_co8 &c)
+{
+  const eu_f2 gy = c.ty;
+  eu_f2 fy;
+  if constexpr (DEG & 1) fy = (eu_f2){ floorf(gy.x), floorf(gy.y) };
+  else fy = (eu_f2){ roundf(gy.x), roundf(gy.y) };
+  c.ty = gy - fy;
+  c.iya = (int)fy.x; c.iyb = (int)fy.y;
+}
+
+// boxes of the base positions of the hitting pixels: quarters (q*, lane 15 of every row of 16 lanes), halves
+// (h*, lanes 31 and 63), tile; npass: the tile at once (1), its halves (2) or its quarters (4), whichever fits
+// the slice first; 0: nothing hits, -1: not even the quarters fit. clean: no hitting pixel left the fast path;
+// GATES (the lean coordinate forms): nor did a gate have to fold one
+struct eu5_boxes {
+  int q0, q1, q2, q3, h0, h1, h2, h3;
+  eu5_box full;
+  int npass;
+  bool clean;
+};
+
+template <int DEG, bool GATES>
+__device__ __forceinline__ void eu5_box_stage(int gate0, int gate1, float upper0, float upper1, eu_i2 hit, eu_i2 ok,
+                                              int ixa, int ixb, int iya, int iyb, eu5_boxes &b)
+{
+  constexpr int order = DEG + 1;
+  int q0 = INT_MAX, q1 = INT_MAX, q2 = INT_MIN, q3 = INT_MIN, h0, h1, h2, h3;
+  if (hit.x) { q0 = ixa; q2 = ixa; q1 = iya; q3 = iya; }
+  if (hit.y) { q0 = min(q0, ixb); q2 = max(q2, ixb); q1 = min(q1, iyb); q3 = max(q3, iyb); }
+  eu5_box_reduce(q0, q1, q2, q3, h0, h1, h2, h3);
+  const eu5_box full = eu5_box_join(eu5_box_at(h0, h1, h2, h3, 31), eu5_box_at(h0, h1, h2, h3, 63));
+  bool clean = __ballot((hit.x && !ok.x) || (hit.y && !ok.y)) == 0ull;
+  if constexpr (GATES) {
+    // the gates' range tests, on the box: a coordinate the periodic gate folds (c < lower or
+    // c - lower >= width) leaves ix <= -1 or ix >= width - 1, one the mirror gate folds from
+    // above ix >= width - 1 (a superset: the tiles on the seam, which do not fit anyway)
+    const int cw = (int)(upper0 + 0.5f), ch = (int)(upper1 + 0.5f);
+    if (full.mnx != INT_MAX) {
+      if (gate0 == 2 && full.mnx < 0) clean = false;
+      if (gate0 != 0 && full.mxx >= cw - 1) clean = false;
+      if (gate1 == 2 && full.mny < 0) clean = false;
+      if (gate1 != 0 && full.mxy >= ch - 1) clean = false;
+    }
+  }
+  // passes: the tile at once, its halves or its quarters, whichever fits the slice first
+  int npass = 1;
+  const int f = eu5_box_fits<order>(full);
+  if (f < 0) npass = 0;                               // nothing hits: zeros
+  else if (f == 0) {
+    npass = 2;
+    if (eu5_box_fits<order>(eu5_box_at(h0, h1, h2, h3, 31)) == 0 || eu5_box_fits<order>(eu5_box_at(h0, h1, h2, h3, 63)) == 0) {
+      npass = 4;
+      if (eu5_box_fits<order>(eu5_box_at(q0, q1, q2, q3, 15)) == 0 || eu5_box_fits<order>(eu5_box_at(q0, q1, q2, q3, 31)) == 0 ||
+          eu5_box_fits<order>(eu5_box_at(q0, q1, q2, q3, 47)) == 0 || eu5_box_fits<order>(eu5_box_at(q0, q1, q2, q3, 63)) == 0)
+        npass = -1;
+    }
+  }
+  b.q0 = q0; b.q1 = q1; b.q2 = q2; b.q3 = q3; b.h0 = h0; b.h1 = h1; b.h2 = h2; b.h3 = h3;
+  b.full = full; b.npass = npass; b.clean = clean;
+}
+
 // PRE (with !HOIST, FAST): the tile's table values come in T, requested by the previous tile ahead of its
 // stores, and this tile requests the next one's (have_n, ty_n, x0_n -> Tn) ahead of its own - see eu5_group16
 template <int NCH, int DEG, int PRJ, bool HOIST, bool FAST, bool PRE = false>
@@ -535,6 +646,204 @@ __device__ __forceinline__ void eu5_stage(const eu_src_dev &s, const eu5_box &bx
   }
 }
 
+// ---------------------------------------------------------------------------
+// The second loop's box table (w.boxtab, built with the plans by eu5_boxplan_kernel): what eu5_box_stage says
+// about a 16x8 tile depends on the geometry alone, so it is computed once per plan and not once per frame.
+// EU5_BT_RECS records of four ints per tile, tile = (slot of its row in w.l2_rows) * tiles16 + tile column:
+//   { box min x, box min y, (max x - min x) | (max y - min y) << 16, class }; third int -1: no hitting pixel.
+// Record 0 is the tile's box (one pass) or that of its first half / quarter, records 1-3 the other halves /
+// quarters; the class counts in record 0 only: the pass count 0, 1, 2, 4, or EU5_BT_WORK - not even the
+// quarters fit, or the tile is not clean: to the work list. A one-pass tile costs one four-dword scalar load.
+// ---------------------------------------------------------------------------
+#define EU5_BT_RECS 4
+#define EU5_BT_WORK 8
+#define EU5_WAIT_VM0 0x0F70    // s_waitcnt vmcnt(0) lgkmcnt(15) expcnt(7), as an instruction the compiler's own wait counting sees
+typedef unsigned eu5_u3 __attribute__((ext_vector_type(3)));
+typedef unsigned eu5_u4 __attribute__((ext_vector_type(4)));
+typedef int eu5_i4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) eu5_i4 *eu5_crec;   // read through the scalar cache
+
+__device__ __forceinline__ int eu5_bt_pack(const eu5_box &b, int w3, int c)
+{
+  if (c == 2) return b.mnx == INT_MAX ? -1 : (int)(((unsigned)b.mxx - (unsigned)b.mnx) | (((unsigned)b.mxy - (unsigned)b.mny) << 16));
+  return c == 0 ? b.mnx : c == 1 ? b.mny : w3;
+}
+
+// pre-pass: one wave per second-loop tile, on the functions the render kernel's tile compiles (eu5_load8,
+// eu5_coords8, eu5_box_stage): same bits, same decisions. The records leave through vector stores of the
+// lanes 0-15 (one int each).
+template <int DEG>
+__global__ __launch_bounds__(256) void eu5_boxplan_kernel(const eu_render_params p, const float *atab_g, const int *l2_rows,
+                                                          int tiles16, int ntiles, int *tab)
+{
+  __shared__ __attribute__((aligned(16))) float atab[768];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave == 0) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+      __builtin_amdgcn_global_load_lds((eu4_gbl_void)(atab_g + i * 256 + lane * 4), (eu4_lds_void)(atab + i * 256), 16, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  const int g = (int)blockIdx.x * 4 + wave;
+  if (g >= ntiles) return;
+  const int slot = g / tiles16, tcol = g - slot * tiles16;
+  const int tile_y = __builtin_amdgcn_readfirstlane(l2_rows[slot]);
+  const int x0 = tcol * EU4_TW;
+  const eu_src_dev &s = p.src;
+  // the pixels of the lane and which of them lie inside the frame, as eu5_tile has them
+  const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
+  const int y = p.row_begin + tile_y * EU4_TH + rw;
+  const bool yin = y < p.row_end;
+  const int xa = x0 + 8 * hf + 2 * pr, xb = xa + 1;
+  const bool va = yin && xa < p.width, vb = yin && xb < p.width;
+  eu5_tab8 T;
+  eu5_load8<true>(p, tile_y, x0, lane, T);
+  eu5_co8 c;
+  eu5_coords8<DEG>(s, atab, T, c);
+  eu5_split_y<DEG>(c);
+  const eu_i2 hit = { va ? -1 : 0, vb ? -1 : 0 };
+  eu5_boxes B;
+  eu5_box_stage<DEG, true>(s.gate0, s.gate1, s.upper0, s.upper1, hit, c.ok, c.ixa, c.ixb, c.iya, c.iyb, B);
+  const int cls = (B.npass < 0 || (B.npass > 0 && !B.clean)) ? EU5_BT_WORK : B.npass;
+  eu5_box r[EU5_BT_RECS] = { B.full, B.full, B.full, B.full };
+  if (B.npass == 2) { r[0] = eu5_box_at(B.h0, B.h1, B.h2, B.h3, 31); r[1] = eu5_box_at(B.h0, B.h1, B.h2, B.h3, 63); }
+  if (B.npass == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = eu5_box_at(B.q0, B.q1, B.q2, B.q3, 15 + 16 * k);
+  }
+  int v = 0;
+#pragma unroll
+  for (int k = 0; k < EU5_BT_RECS; k++) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      if (lane == 4 * k + i) v = eu5_bt_pack(r[k], k == 0 ? cls : 0, i);
+  }
+  if (lane < 4 * EU5_BT_RECS) tab[(size_t)g * (4 * EU5_BT_RECS) + lane] = v;
+}
+
+// One 16x8 tile of the second loop WITH the box table. R: the tile's record 0, requested through the scalar
+// cache a tile ahead; rec: where the tile's records lie. The box is known before the coordinates are, so the
+// order of a tile is: table values (requested by the previous tile ahead of its stores) -> staging of the first
+// pass -> coordinate stage and weights, under the staging's round trip -> ONE wait -> taps -> the next tile's
+// table values -> two stores, always. No reduction, no lane reads, no fit cascade, no gate tests, no fast-path
+// flags; a tile of the work list is appended without its coordinate stage. Later passes stay serial in the one
+// slice.
+template <int NCH, int DEG>
+__device__ __forceinline__ void eu5_tile_bt(const eu_render_params &p, const eu4_plan &w, const float *atab, float *wtile,
+                                            int tile_y, int x0, int lane, const eu5_tab8 &T, eu5_i4 R, eu5_crec rec,
+                                            bool have_n, int ty_n, int x0_n, eu5_tab8 &Tn)
+{
+  constexpr int order = DEG + 1;
+  const eu_src_dev &s = p.src;
+#ifdef EU5_STAMPS
+  unsigned long long st_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+#endif
+  EU5_STAMP(0);
+  const int cls = R.w;
+  if (cls & EU5_BT_WORK) {
+    if (lane == 0) {
+      const int id = tile_y * w.tiles16 + x0 / EU4_TW;
+      const int sh = eu4_shard_of(id);
+      const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
+      p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
+    }
+    if (have_n) eu5_load8<true>(p, ty_n, x0_n, lane, Tn);
+    __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);         // (no stores behind these loads: see the stores below)
+    return;
+  }
+  const int npass = cls & 7;
+  const unsigned lds_tile = (unsigned)(unsigned long long)(eu4_lds_void)wtile;
+  // the table values first: their wait is the one for the loads requested ahead of the previous tile's stores;
+  // behind the staging it would be a wait for the staging and those stores (vmcnt counts in issue order)
+  eu5_tab8 Tl = T;
+  asm volatile("" : "+v"(Tl.c0), "+v"(Tl.A0), "+v"(Tl.A1), "+v"(Tl.A2), "+v"(Tl.B0), "+v"(Tl.B1), "+v"(Tl.B2));
+  eu5_box bx = { R.x, R.y, R.x + (R.z & 0xffff), R.y + (R.z >> 16) };
+  bool some = npass > 0 && R.z >= 0;
+  if (some) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
+  const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
+  const int y = p.row_begin + tile_y * EU4_TH + rw;
+  const bool yin = y < p.row_end;
+  const int xa = x0 + 8 * hf + 2 * pr, xb = xa + 1;
+  const bool va = yin && xa < p.width, vb = yin && xb < p.width;
+  eu_f2 rga = { 0.0f, 0.0f }, bxa = { 0.0f, 0.0f }, rgb = { 0.0f, 0.0f }, bxb = { 0.0f, 0.0f };
+  if (npass > 0) {
+    eu5_co8 c;
+    eu5_coords8<DEG>(s, atab, Tl, c);
+    eu5_split_y<DEG>(c);
+#ifdef EU5_STAMPS
+    asm volatile("" : : "v"(c.iya), "v"(c.iyb), "v"(c.ixa), "v"(c.ixb));
+#endif
+    EU5_STAMP(2);
+#ifdef EU5_STAMPS
+    st_[3] = st_[2];
+#endif
+    eu_f2 wx[order], wy[order];
+    if constexpr (DEG >= 2) {
+      eu_weights2<DEG>(s.wm, c.ty, wy);
+      eu_weights2<DEG>(s.wm, c.tx, wx);
+    }
+    const int grp = npass == 1 ? 0 : npass == 2 ? hf : (lane >> 4);
+#pragma unroll 1
+    for (int pi = 0; pi < npass; pi++) {
+      // the next pass's record, requested under this pass
+      eu5_i4 Rn = { 0, 0, -1, 0 };
+      if (pi + 1 < npass) Rn = rec[pi + 1];
+      if (some) {
+        if (pi > 0) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
+        const int ibw = bx.mxx - bx.mnx + order;
+        // lanes of other groups and lanes without a hit read the box origin
+        const bool mine = grp == pi;
+        const int oa = (mine && va) ? ((c.iya - bx.mny) * ibw + (c.ixa - bx.mnx)) * 4 : 0;
+        const int ob = (mine && vb) ? ((c.iyb - bx.mny) * ibw + (c.ixb - bx.mnx)) * 4 : 0;
+        if (pi == 0) EU5_STAMP(4);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (pi == 0) EU5_STAMP(5);
+        if (mine) eu5_taps<NCH, DEG>((eu_lptr)wtile, oa, ob, ibw * 4, wx, wy, c.tx, c.ty, rga, bxa, rgb, bxb);
+      }
+      bx = (eu5_box){ Rn.x, Rn.y, Rn.x + (Rn.z & 0xffff), Rn.y + (Rn.z >> 16) };
+      some = Rn.z >= 0;
+    }
+  }
+#ifdef EU5_STAMPS
+  asm volatile("" : : "v"(rga), "v"(bxa), "v"(rgb), "v"(bxb));
+#endif
+  EU5_STAMP(6);
+  // zero on a miss (FAST: every ray hits, a miss is a pixel outside the frame, which is not stored); storer
+  float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
+  if (have_n) eu5_load8<true>(p, ty_n, x0_n, lane, Tn);
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    // Stores WITHOUT a branch around them: the tile's rows as a buffer, a pixel outside the frame gets an offset
+    // beyond the buffer's end, which the hardware drops (launch4_ndp: eight rows of the output are below 2^31
+    // bytes). Behind 'if (va)' a store sits behind a branch that skips it when no lane stores, the compiler cannot
+    // count the stores behind the table-value loads above, and the next tile's wait for those loads becomes
+    // vmcnt(0): a wait for this tile's stores to be acknowledged, 1-2k cycles at the head of every tile. With two
+    // stores on every path it is vmcnt(2). Every other path to a tile's head ends in an explicit vmcnt(0).
+    float *const base = p.out + (long long)(tile_y * EU4_TH) * p.out_stride + (long long)x0 * NCH;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x80000000u, 0x00027000);
+    const unsigned off = ((unsigned)rw * (unsigned)p.out_stride + (unsigned)((8 * hf + 2 * pr) * NCH)) * 4u;
+    const unsigned oa = va ? off : 0xfffff000u, ob = vb ? oa + NCH * 4u : 0xfffff000u;     // (vb implies va)
+    if constexpr (NCH == 3) {
+      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(qa[0]), __float_as_uint(qa[1]), __float_as_uint(qa[2]) }, rs, (int)oa, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(qb[0]), __float_as_uint(qb[1]), __float_as_uint(qb[2]) }, rs, (int)ob, 0, 0);
+    } else {
+      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(qa[0]), __float_as_uint(qa[1]), __float_as_uint(qa[2]), __float_as_uint(qa[3]) }, rs, (int)oa, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(qb[0]), __float_as_uint(qb[1]), __float_as_uint(qb[2]), __float_as_uint(qb[3]) }, rs, (int)ob, 0, 0);
+    }
+  }
+  EU5_STAMP(7);
+#ifdef EU5_STAMPS
+  if (lane == 0 && w.stamps) {
+    unsigned long long *o = w.stamps + ((size_t)tile_y * w.tiles16 + x0 / EU4_TW) * 8;
+    st_[1] = (unsigned long long)(npass + 1);
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = st_[k];
+  }
+#endif
+}
+
 // A 16x16 tile on tile rows with a column plan (FAST profile, lat/lon source): FOUR pixels per lane - the
 // pairs (xa, xb) of rows y and y + 8. The two pairs share everything that depends on the column (the table
 // entry: base position, x weights, sqrt(rx^2 + rz^2)) and run two independent latitude chains, which is what a
@@ -838,7 +1147,9 @@ __device__ __forceinline__ int eu5_pair_plan(const int *tileplan, int tiles_y, i
 }
 
 // grid: 8 * (workgroups per XCD); the launcher sizes it to what is resident at once
-template <int NCH, int DEG, int PRJ, bool FAST>
+// BOXTAB (FAST lat/lon jobs): the second loop takes its tiles' boxes from w.boxtab (eu5_tile_bt) - an instantiation of
+// its own, not a branch in the tile: the loop's registers have no room for both bodies
+template <int NCH, int DEG, int PRJ, bool FAST, bool BOXTAB = false>
 __global__ __launch_bounds__(64 * EU5_WAVES, EU5_OCC) void eu_render5_kernel(const eu_render_params p, const eu4_plan w)
 {
   __shared__ __attribute__((aligned(16))) float tile_all[EU5_WAVES * EU5_TEXELS * 4];
@@ -924,34 +1235,77 @@ __global__ __launch_bounds__(64 * EU5_WAVES, EU5_OCC) void eu_render5_kernel(con
       if (lane0 == 0) v = atomicAdd(queue, 1);
       return v;                                     // read with readfirstlane where it is needed, not here
     };
-    auto decode = [&](int j, int &ty, int &tcol) -> bool {
-      if (j >= nbatch) return false;
-      const int r = (int)(((unsigned long long)(unsigned)j * w.l2_magic) >> 40);      // j / l2_half
-      ty = rows2[r]; tcol = 2 * (j - r * w.l2_half);
-      return true;
-    };
-    int ty_a = 0, col_a = 0, ty_n = 0, col_n = 0;
-    bool have = decode(__builtin_amdgcn_readfirstlane(take()), ty_a, col_a);
-    eu5_tab8 Ta, Tb;
-    if (have) eu5_load8<FAST>(p, ty_a, col_a * EU4_TW, lane0, Ta);
+    if constexpr (BOXTAB) {
+      static_assert(FAST && PRJ == EU_SPHERICAL, "the box table is that of the FAST lat/lon second loop");
+      // as below, with every tile's record 0 requested through the scalar cache as soon as its id is known: a tile ahead
+      const eu5_crec bt = (eu5_crec)w.boxtab;
+      auto decode = [&](int j, int &ty, int &tcol, int &ti) -> bool {
+        if (j >= nbatch) return false;
+        const int r = (int)(((unsigned long long)(unsigned)j * w.l2_magic) >> 40);      // j / l2_half
+        ty = rows2[r]; tcol = 2 * (j - r * w.l2_half);
+        ti = ((w.l2_off[xcd] + r) * w.tiles16 + tcol) * EU5_BT_RECS;
+        return true;
+      };
+      int ty_a = 0, col_a = 0, ti_a = 0, ty_n = 0, col_n = 0, ti_n = 0;
+      bool have = decode(__builtin_amdgcn_readfirstlane(take()), ty_a, col_a, ti_a);
+      eu5_tab8 Ta, Tb;
+      eu5_i4 Ra = { 0, 0, -1, 0 }, Rb = { 0, 0, -1, 0 };
+      if (have) { Ra = bt[ti_a]; eu5_load8<FAST>(p, ty_a, col_a * EU4_TW, lane0, Ta); }
+      __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);       // (see eu5_tile_bt's stores)
 #pragma unroll 1
-    while (have) {
-      const int jn_lane = take();                   // in flight across the first tile of this batch
-      const bool second = col_a + 1 < w.tiles16;    // (an odd number of tiles per row: the last batch is one tile)
-      {
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        eu5_tile<NCH, DEG, PRJ, false, FAST, true>(p, w, atab, tile, nullptr, ty_a, col_a * EU4_TW, lane, &Ta, second, ty_a,
-                                                   (col_a + 1) * EU4_TW, &Tb);
+      while (have) {
+        const int jn_lane = take();                   // in flight across the first tile of this batch
+        const bool second = col_a + 1 < w.tiles16;    // (an odd number of tiles per row: the last batch is one tile)
+        if (second) Rb = bt[ti_a + EU5_BT_RECS];
+        {
+          int lane = lane0;
+          asm volatile("" : "+v"(lane));
+          eu5_tile_bt<NCH, DEG>(p, w, atab, tile, ty_a, col_a * EU4_TW, lane, Ta, Ra, bt + ti_a, second, ty_a,
+                                (col_a + 1) * EU4_TW, Tb);
+        }
+        const bool have_n = decode(__builtin_amdgcn_readfirstlane(jn_lane), ty_n, col_n, ti_n);
+        if (have_n) Ra = bt[ti_n];
+        if (second) {
+          int lane = lane0;
+          asm volatile("" : "+v"(lane));
+          eu5_tile_bt<NCH, DEG>(p, w, atab, tile, ty_a, (col_a + 1) * EU4_TW, lane, Tb, Rb, bt + ti_a + EU5_BT_RECS, have_n,
+                                ty_n, col_n * EU4_TW, Ta);
+        } else if (have_n) {
+          eu5_load8<FAST>(p, ty_n, col_n * EU4_TW, lane0, Ta);
+          __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);
+        }
+        ty_a = ty_n; col_a = col_n; ti_a = ti_n; have = have_n;
       }
-      const bool have_n = decode(__builtin_amdgcn_readfirstlane(jn_lane), ty_n, col_n);
-      if (second) {
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        eu5_tile<NCH, DEG, PRJ, false, FAST, true>(p, w, atab, tile, nullptr, ty_a, (col_a + 1) * EU4_TW, lane, &Tb, have_n, ty_n,
-                                                   col_n * EU4_TW, &Ta);
-      } else if (have_n) eu5_load8<FAST>(p, ty_n, col_n * EU4_TW, lane0, Ta);
-      ty_a = ty_n; col_a = col_n; have = have_n;
+    } else {
+      auto decode = [&](int j, int &ty, int &tcol) -> bool {
+        if (j >= nbatch) return false;
+        const int r = (int)(((unsigned long long)(unsigned)j * w.l2_magic) >> 40);      // j / l2_half
+        ty = rows2[r]; tcol = 2 * (j - r * w.l2_half);
+        return true;
+      };
+      int ty_a = 0, col_a = 0, ty_n = 0, col_n = 0;
+      bool have = decode(__builtin_amdgcn_readfirstlane(take()), ty_a, col_a);
+      eu5_tab8 Ta, Tb;
+      if (have) eu5_load8<FAST>(p, ty_a, col_a * EU4_TW, lane0, Ta);
+  #pragma unroll 1
+      while (have) {
+        const int jn_lane = take();                   // in flight across the first tile of this batch
+        const bool second = col_a + 1 < w.tiles16;    // (an odd number of tiles per row: the last batch is one tile)
+        {
+          int lane = lane0;
+          asm volatile("" : "+v"(lane));
+          eu5_tile<NCH, DEG, PRJ, false, FAST, true>(p, w, atab, tile, nullptr, ty_a, col_a * EU4_TW, lane, &Ta, second, ty_a,
+                                                     (col_a + 1) * EU4_TW, &Tb);
+        }
+        const bool have_n = decode(__builtin_amdgcn_readfirstlane(jn_lane), ty_n, col_n);
+        if (second) {
+          int lane = lane0;
+          asm volatile("" : "+v"(lane));
+          eu5_tile<NCH, DEG, PRJ, false, FAST, true>(p, w, atab, tile, nullptr, ty_a, (col_a + 1) * EU4_TW, lane, &Tb, have_n, ty_n,
+                                                     col_n * EU4_TW, &Ta);
+        } else if (have_n) eu5_load8<FAST>(p, ty_n, col_n * EU4_TW, lane0, Ta);
+        ty_a = ty_n; col_a = col_n; have = have_n;
+      }
     }
   } else {
     int plan_n = (it.done() || it.row() >= p.tiles_y) ? -2 : (PRJ == EU_SPHERICAL ? ((eu5_cint)w.tileplan)[it.row()] : -1);

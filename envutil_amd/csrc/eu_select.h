@@ -30,7 +30,13 @@ struct eu_switches {
   int share;           // EU_HIP_SHARE: EU_SHARE_* bits - 0: none, m: mirrors, f: faces; else both
   int direct;          // EU_HIP_DIRECT=1: the general kernel never stages through LDS
   int iir_stream;      // EU_HIP_IIR_STREAM: bit 0 rows, bit 1 columns, bit 2 checkpoints; unset: 7
+  int boxtab;          // EU_HIP_BOXTAB=0: the persistent staged kernel's second loop reduces its tile boxes per frame (0); else 1:
+                       // it reads them from a table built with the plans
+  int boxtab_max_kb;   // EU_HIP_BOXTAB_MAX_KB: the largest box table built, KiB (EU_BOXTAB_MAX_KB); a job beyond it gets none
 };
+
+// 64 bytes per second-loop tile: 64 MiB hold the polar faces of a 6 x 8192 cubemap, four times the headline's 16 MiB
+#define EU_BOXTAB_MAX_KB 65536
 
 inline eu_switches eu_read_switches()
 {
@@ -51,6 +57,9 @@ inline eu_switches eu_read_switches()
   s.direct = first("EU_HIP_DIRECT") == '1';
   const char *iir = getenv("EU_HIP_IIR_STREAM");
   s.iir_stream = iir ? atoi(iir) : 7;
+  s.boxtab = first("EU_HIP_BOXTAB") != '0';
+  const char *bm = getenv("EU_HIP_BOXTAB_MAX_KB");
+  s.boxtab_max_kb = bm && bm[0] ? std::max(0, std::min(atoi(bm), 16 * 1024 * 1024)) : EU_BOXTAB_MAX_KB;
   return s;
 }
 

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""profiles/shared_rows_headline_isa.txt (r03_headline_isa.txt: the kernel before the first loop rendered groups): what the
-shipped headline kernel is made of. Compiles eu_render4.hip (which
-includes eu_render5.h) with -save-temps, takes eu_render5_kernel<3,3,SPHERICAL,FAST> out of the ISA listing and
+"""profiles/boxtab_headline_isa.txt (shared_rows_headline_isa.txt: the kernel before the second loop read its tile boxes from
+a table; r03_headline_isa.txt: before the first loop rendered groups): what the shipped headline kernel is made of.
+Compiles eu_render4.hip (which includes eu_render5.h) with -save-temps, reports registers, scratch and occupancy of the
+degree-3 FAST instantiations - with the box table (the shipped form) and without (EU_HIP_BOXTAB=0, a refused table) -
+takes eu_render5_kernel<3,3,SPHERICAL,FAST,BOXTAB> out of the ISA listing and
 reports the code-object metadata, the instruction mix (whole kernel and per stage of the first loop's group of 16x16
 tiles - the coordinate stage, once per group, and the member stage - cut at the stage's first characteristic instruction), and - from the PMC record in profiles/ - the executed counts per tile.
-usage: python tools/isa_report.py > profiles/shared_rows_headline_isa.txt"""
+usage: python tools/isa_report.py > profiles/boxtab_headline_isa.txt"""
 import collections, os, re, subprocess, sys, tempfile, json
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_Z17eu_render5_kernelILi3ELi3ELi0ELb1EEv"
+KERNEL = "_Z17eu_render5_kernelILi3ELi3ELi0ELb1ELb1EEv"
 tmp = tempfile.mkdtemp(prefix="isa_")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17",
                        "-Wno-unused-function", "-Wno-pass-failed", "-save-temps=obj", "-c",
@@ -39,12 +41,20 @@ def cls(op):
     if op.startswith(("s_cbranch", "s_branch")): return "branches"
     return "SALU other"
 
-print(f"# eu_render5_kernel<3,3,SPHERICAL,FAST> at commit {subprocess.check_output(['git','-C',ROOT,'rev-parse','--short','HEAD']).decode().strip()} (hipcc -O3 --offload-arch=gfx950 -ffp-contract=off)")
+print(f"# eu_render5_kernel<3,3,SPHERICAL,FAST,BOXTAB> at commit {subprocess.check_output(['git','-C',ROOT,'rev-parse','--short','HEAD']).decode().strip()} (hipcc -O3 --offload-arch=gfx950 -ffp-contract=off)")
+print("## registers of the degree-3 FAST instantiations <NCH,3,SPHERICAL,true,BOXTAB> (parent: 128 VGPRs, 12 / 20 bytes of scratch, occupancy 4)")
+for nch in (3, 4):
+    for bt in (1, 0):
+        k = f"_Z17eu_render5_kernelILi{nch}ELi3ELi0ELb1ELb{bt}EEv"
+        ks = next(i for i, l in enumerate(lines) if l.startswith(k))
+        info = [l.strip("; ").strip() for l in lines[ks:next(i for i in range(ks, len(lines)) if "; Occupancy" in lines[i]) + 1]
+                if re.search(r"; (NumVgprs|ScratchSize|Occupancy):", l)]
+        print(f"   <{nch},3,0,true,{'true' if bt else 'false'}>  " + "  ".join(info))
 print("## code-object metadata")
 for m in meta + occ: print("  ", m)
 print("   waves per SIMD by registers: 512 / 128 = 4 (launch bounds 256 x 4); workgroups per CU by LDS: 163840 / 39936 = 4 -> 16 waves per CU")
 tot = collections.Counter(cls(op) for _, op in ins)
-print(f"## static instruction mix of the whole kernel ({len(ins)} instructions: two loops, one copy of the first loop's body, two of the second's)")
+print(f"## static instruction mix of the whole kernel ({len(ins)} instructions: two loops, one copy of the first loop's body, two of the second's tile and of its pass loop)")
 for k, v in tot.most_common(): print(f"   {v:6d}  {k}")
 # the first loop's body: the coordinate stage of a group (up to the y reduction, the only DPP block of that loop),
 # then the member stage (a loop over the group's members) from its head to its last store
