@@ -57,6 +57,15 @@ class Target(C.Structure):
                 ("synopsis", C.c_int32), ("single", C.POINTER(Facet))]
 
 
+class Rays(C.Structure):
+    """struct eu_rays"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ninputs", C.c_int32),
+                ("nchannels", C.c_int32), ("ntaps", C.c_int32),
+                ("taps", C.POINTER(C.c_float)),
+                ("rays", C.c_void_p), ("ray_row_stride_bytes", C.c_size_t),
+                ("rays_on_device", C.c_int32)]
+
+
 OUT_FLOAT, OUT_SRGBA8 = 0, 1
 SYN_PANORAMA, SYN_HDR_MERGE = 0, 1
 
@@ -135,6 +144,8 @@ def lib():
     L.eu_hip_render_devices.argtypes = [vp, vp, i32, vp, C.c_size_t, i32]
     L.eu_hip_device_strips.argtypes = [vp, vp, i32, vp, vp]
     L.eu_hip_render_timed.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
+    L.eu_hip_render_rays.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
+    L.eu_hip_render_rays_timed.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_layout_segments.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eu_hip_band_rows.argtypes = [i32, i32, i32, i32]
     L.eu_hip_band_rows.restype = i32
@@ -565,6 +576,7 @@ def render(args, sources, nchannels=None, row_begin=0, row_end=None, stage=0, ou
     t = args.target(nch, row_begin, row_end, stage, band)
     rows = t.row_end - t.row_begin
     w = args.out_width
+    # stage 1: rays, 2: source coordinates, 3 / 4: the x- / y-biased neighbour rays of a twined job
     if args.tethered:
         och = 1
         if out is None:
@@ -577,6 +589,105 @@ def render(args, sources, nchannels=None, row_begin=0, row_end=None, stage=0, ou
     _check(lib().eu_hip_render(C.byref(t), arr, len(sources), out.ctypes.data_as(C.c_void_p),
                                w * och * 4, 0, None))
     return out
+
+
+def _grid(a, what):
+    """a float32 array of shape (..., k), numpy or torch on the device, as a height x width grid of k floats:
+    (address, row stride in bytes, on_device, leading shape, width, height). The leading axes are folded into
+    rows of the last of them (one axis: a flat list, height 1). A three-axis array whose rows are padded -
+    a[:, :w, :] of a wider array - is used in place with its row stride; everything else must be contiguous."""
+    on_device = _is_torch(a)
+    lead = tuple(a.shape[:-1])
+    k = a.shape[-1]
+    n = 1
+    for d in lead:
+        n *= d
+    width = lead[-1] if len(lead) >= 2 else n
+    height = n // width if width else 0
+    stride = width * k * 4
+    if on_device:
+        st = tuple(a.stride())
+        padded = a.ndim == 3 and st[2] == 1 and st[1] == k and st[0] >= width * k
+        if padded:
+            import torch
+            if not a.is_cuda or a.dtype != torch.float32:
+                raise EuError(f"render_rays: {what} is float32 and on the device")
+            torch.cuda.current_stream(a.device).synchronize()
+            return a.data_ptr(), st[0] * 4, True, lead, width, height
+        return _torch_ptr(a), stride, True, lead, width, height
+    if a.dtype != np.float32:
+        raise EuError(f"render_rays: {what} is float32")
+    if a.ndim == 3 and a.strides[2] == 4 and a.strides[1] == 4 * k and a.strides[0] >= stride and a.strides[0] % 4 == 0:
+        return a.ctypes.data, a.strides[0], False, lead, width, height
+    if not a.flags.c_contiguous:
+        raise EuError(f"render_rays: {what} is contiguous, or a three-axis array with padded rows")
+    return a.ctypes.data, stride, False, lead, width, height
+
+
+def _rays_struct(source, rays, nchannels, taps):
+    """(eu_rays, leading shape, objects it points into) for rays (..., 3) or ninepacks (..., 9)"""
+    if not _is_torch(rays) and not (isinstance(rays, np.ndarray) and rays.dtype == np.float32):
+        rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim < 1 or rays.shape[-1] not in (3, 9):
+        raise EuError("render_rays: rays have shape (..., 3), ninepacks (..., 9)")
+    ptr, stride, on_device, lead, width, height = _grid(rays, "rays")
+    r = Rays()
+    r.width, r.height, r.ninputs = width, height, rays.shape[-1]
+    r.nchannels = nchannels or source.fct.nchannels
+    keep = [rays]
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1, 3)
+        keep.append(taps)
+        r.ntaps, r.taps = len(taps), taps.ctypes.data_as(C.POINTER(C.c_float))
+    r.rays, r.ray_row_stride_bytes, r.rays_on_device = ptr, stride, int(on_device)
+    return r, lead, keep
+
+
+def render_rays(source, rays, nchannels=None, taps=None, out=None, stream=None):
+    """eu_hip_render_rays: `act` alone - the resident source evaluated at the caller's rays, three floats
+    x, y, z in the SOURCE's frame (what render(..., stage=1) returns; no facet or camera orientation is
+    applied), or at ninepacks {ray, x-neighbour, y-neighbour} with `taps` = make_spread(...). `rays`: numpy
+    or a float32 torch tensor on the library's device, shape (..., 3) or (..., 9). Returns the rays' leading
+    shape plus a channel axis: a new numpy array, or `out` (numpy or torch). With rays and `out` both on the
+    device the call is asynchronous on `stream` (a hipStream_t address; None: the library's stream) until
+    sync(). A ray with a non-finite component, or with all three zero, is a miss: zeros."""
+    r, lead, keep = _rays_struct(source, rays, nchannels, taps)
+    shape = lead + (r.nchannels,)
+    if out is None:
+        out = np.zeros(shape, np.float32)
+    if tuple(out.shape) != shape:
+        raise EuError(f"render_rays: out has shape {tuple(out.shape)}, expected {shape}")
+    optr, ostride, out_dev, _, _, _ = _grid(out, "out")
+    _check(lib().eu_hip_render_rays(C.byref(r), source.handle, C.c_void_p(optr), ostride, int(out_dev),
+                                    C.c_void_p(stream) if stream else None))
+    return out
+
+
+def render_rays_timed(source, rays, out_dev_ptr, iters, nchannels=None, taps=None):
+    """kernel-only timing of render_rays with HIP events on the library's stream. `rays`: a torch tensor on
+    the device, or numpy (copied to the device for the call); the output stays in HBM at out_dev_ptr, dense.
+    Returns mean milliseconds per launch."""
+    L = lib()
+    tmp = C.c_void_p()
+    try:
+        r, lead, keep = _rays_struct(source, rays, nchannels, taps)
+        if not r.rays_on_device:
+            host = np.ascontiguousarray(keep[0])
+            _check(L.eu_hip_malloc(C.byref(tmp), host.nbytes))
+            _check(L.eu_hip_memcpy_h2d(tmp, _ptr(host), host.nbytes))
+            r.rays, r.rays_on_device, r.ray_row_stride_bytes = tmp.value, 1, r.width * r.ninputs * 4
+        ms = C.c_float()
+        _check(L.eu_hip_render_rays_timed(C.byref(r), source.handle, C.c_void_p(out_dev_ptr),
+                                          r.width * r.nchannels * 4, iters, C.byref(ms)))
+        return ms.value
+    finally:
+        if tmp:
+            L.eu_hip_free(tmp)
+
+
+def sync():
+    """eu_hip_sync: wait for the library's stream and the stream of the last asynchronous call"""
+    _check(lib().eu_hip_sync())
 
 
 def init_devices(devices):

@@ -17,6 +17,7 @@
 #include "eu_alpha.h"
 #include "eu_math2.h"
 #include "eu_launch.h"
+#include "eu_ray_guard.h"
 
 struct eu_source {
   eu_facet fct;
@@ -75,6 +76,10 @@ struct context {
   std::vector<unsigned char> mplan_key;
   int mplan_form = 0, mplan_norm = 0;
   eu_dev_buf<float> strip;                        // eu_hip_render_devices: this slot's rows before they are gathered
+  // eu_hip_render_rays keeps its own tap table (the plan's, `taps`, is part of the cached plan of eu_hip_render)
+  // and its own staging of host rays
+  eu_dev_buf<float> rtaps, rstage;
+  std::vector<float> rtaps_host;                  // what rtaps holds
   eu_dev_buf<int32_t> aplan;                      // row plan of the last device alpha edit
   hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
@@ -341,6 +346,8 @@ int check_target(const eu_target *t)
     return fail(EU_ERR_ARGUMENT, "unknown output format");
   if (t->out_format == EU_OUT_SRGBA8 && t->stage)
     return fail(EU_ERR_ARGUMENT, "stage outputs are float only");
+  if ((t->stage == 3 || t->stage == 4) && t->ntaps == 0)
+    return fail(EU_ERR_ARGUMENT, "stages 3 and 4 are the neighbour rays of a twined job: they need a tap table");
   return EU_OK;
 }
 
@@ -1479,6 +1486,171 @@ int eu_hip_band_rows(int height, int band_rows, int band_count, int band_index)
 {
   if (height < 0 || (band_count > 1 && (band_rows < 1 || band_index < 0 || band_index >= band_count))) return 0;
   return local_rows(height, band_rows, band_count, band_index);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// `act` alone: a resident source evaluated at the caller's rays (include/eu_hip.h, eu_render_rays.hip)
+// ---------------------------------------------------------------------------------------------------------
+
+// everything that can be wrong with the arguments, found without a device
+static int check_rays(const eu_rays *r, const eu_source *src, const float *out, size_t out_row_stride_bytes)
+{
+  if (!r || !src || !out || !r->rays) return fail(EU_ERR_ARGUMENT, "render_rays: null argument");
+  if (r->ninputs != 3 && r->ninputs != 9)
+    return fail(EU_ERR_ARGUMENT, "render_rays: ninputs is 3 (rays) or 9 (ninepacks)");
+  if (r->ninputs == 3 && (r->ntaps != 0 || r->taps))
+    return fail(EU_ERR_ARGUMENT, "render_rays: a tap table goes with ninepacks (ninputs 9) only");
+  if (r->ninputs == 9 && (r->ntaps <= 0 || r->ntaps > EU_MAX_TAPS || !r->taps))
+    return fail(EU_ERR_ARGUMENT, "render_rays: ninepacks need a tap table of 1 .. EU_MAX_TAPS taps");
+  if (r->nchannels < 1 || r->nchannels > 4) return fail(EU_ERR_ARGUMENT, "render_rays: output channels must be 1..4");
+  // as eu_hip_render: a masking source adapts channel counts with mono_t, which knows 1 and 2 output channels only
+  if (src->fct.mask_paint && src->nch != r->nchannels && r->nchannels > 2)
+    return fail(EU_ERR_ARGUMENT, "--mask_for: a facet whose channel count differs from the output's needs 1 or 2 output channels");
+  if (r->width <= 0 || r->height <= 0) return fail(EU_ERR_ARGUMENT, "render_rays: empty ray array");
+  if (r->ray_row_stride_bytes % sizeof(float) || out_row_stride_bytes % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "render_rays: row strides must be multiples of 4 bytes");
+  if (r->ray_row_stride_bytes < (size_t)r->width * r->ninputs * sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "render_rays: ray row stride smaller than a row");
+  if (out_row_stride_bytes < (size_t)r->width * r->nchannels * sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "render_rays: output row stride smaller than a row");
+  return EU_OK;
+}
+
+// the tap table on the device, x and y premultiplied by the bias 4.0 (twine_t ctor, twining.h:106-121)
+static int upload_ray_taps(const eu_rays *r)
+{
+  if (r->ninputs != 9) return EU_OK;
+  std::vector<float> taps(r->taps, r->taps + 3 * (size_t)r->ntaps);
+  for (int k = 0; k < r->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
+  if (g.rtaps.p && taps.size() == g.rtaps_host.size() &&
+      !memcmp(taps.data(), g.rtaps_host.data(), taps.size() * sizeof(float)))
+    return EU_OK;
+  // an earlier call on a caller's stream may still read the table
+  if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  g.rtaps_host.clear();
+  HIPCHK(g.rtaps.reserve(taps.size()));
+  HIPCHK(hipMemcpy(g.rtaps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+  g.rtaps_host.swap(taps);
+  return EU_OK;
+}
+
+// one launch: a w x h piece of the grid, both buffers on the device
+static int launch_rays(const eu_rays *r, const eu_source *src, const eu_switches &sw, const float *rays_dev,
+                       size_t ray_stride_bytes, float *out_dev, size_t out_stride_bytes, int w, int h, hipStream_t st)
+{
+  eu_rays_params p;
+  memset(&p, 0, sizeof p);
+  p.width = w; p.height = h;
+  p.ninputs = r->ninputs; p.ntaps = r->ntaps;
+  p.nch = src->nch; p.nch_out = r->nchannels;
+  p.rays = rays_dev; p.ray_stride = (long long)(ray_stride_bytes / sizeof(float));
+  p.taps = g.rtaps.p;
+  p.out = out_dev; p.out_stride = (long long)(out_stride_bytes / sizeof(float));
+  p.src = src->sd;
+  if (eu_launch_render_rays(&p, eu_select_ray_path(p, sw), st)) return fail(EU_ERR_NO_DEVICE, "render_rays: kernel launch failed");
+  return EU_OK;
+}
+
+// pixels (rays and their output together) of one staged chunk of a call with a host buffer
+#define EU_RAYS_CHUNK_BYTES ((size_t)64 << 20)
+
+int eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out, size_t out_row_stride_bytes, int out_on_device,
+                       void *stream)
+{
+  int rc;
+  if ((rc = check_rays(r, src, out, out_row_stride_bytes))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (!src->dev) return fail(EU_ERR_HANDLE, "render_rays: the source has no container");
+  const eu_switches sw = eu_read_switches();
+  if ((rc = upload_ray_taps(r))) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
+  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
+  if (r->rays_on_device && out_on_device)
+    return launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out, out_row_stride_bytes, r->width, r->height, st);
+  // A host buffer on either side: the grid goes through in chunks of rows - a flat list in chunks of its one
+  // row - of bounded size, copy in, launch, copy out, all in order on `st`; the call returns when `out` is complete
+  const size_t in_px = (size_t)r->ninputs * sizeof(float), out_px = (size_t)r->nchannels * sizeof(float);
+  const bool flat = r->height == 1;
+  const size_t px_per_chunk = std::max<size_t>(1, EU_RAYS_CHUNK_BYTES / (in_px + out_px));
+  const int cw = flat ? (int)std::min<size_t>((size_t)r->width, px_per_chunk) : r->width;
+  const int ch = flat ? 1 : (int)std::min<size_t>((size_t)r->height, std::max<size_t>(1, px_per_chunk / (size_t)r->width));
+  if (!r->rays_on_device) HIPCHK(g.rstage.reserve((size_t)cw * ch * r->ninputs));
+  if (!out_on_device) HIPCHK(g.stage.reserve((size_t)cw * ch * r->nchannels));
+  // whatever happens below, nothing of this call may still read `rays` or write `out` when it returns
+  struct drain { hipStream_t a; ~drain() { (void)hipStreamSynchronize(a); } } drain_on_exit{ st };
+  for (int y0 = 0; y0 < r->height; y0 += ch)
+    for (int x0 = 0; x0 < r->width; x0 += cw) {
+      const int w = std::min(cw, r->width - x0), h = std::min(ch, r->height - y0);
+      const char *rin = (const char *)r->rays + (size_t)y0 * r->ray_row_stride_bytes + (size_t)x0 * in_px;
+      char *rout = (char *)out + (size_t)y0 * out_row_stride_bytes + (size_t)x0 * out_px;
+      const float *rays_dev = (const float *)rin;
+      size_t rays_stride = r->ray_row_stride_bytes;
+      if (!r->rays_on_device) {
+        rays_dev = g.rstage.p; rays_stride = (size_t)w * in_px;
+        HIPCHK(hipMemcpy2DAsync(g.rstage.p, rays_stride, rin, r->ray_row_stride_bytes, rays_stride, (size_t)h,
+                                hipMemcpyHostToDevice, st));
+      }
+      float *out_dev = (float *)rout;
+      size_t out_stride = out_row_stride_bytes;
+      if (!out_on_device) { out_dev = g.stage.p; out_stride = (size_t)w * out_px; }
+      if ((rc = launch_rays(r, src, sw, rays_dev, rays_stride, out_dev, out_stride, w, h, st))) return rc;
+      if (!out_on_device)
+        HIPCHK(hipMemcpy2DAsync(rout, out_row_stride_bytes, g.stage.p, out_stride, out_stride, (size_t)h,
+                                hipMemcpyDeviceToHost, st));
+    }
+  HIPCHK(hipStreamSynchronize(st));
+  return EU_OK;
+}
+
+int eu_hip_render_rays_timed(const eu_rays *r, eu_source *src, float *out_dev, size_t out_row_stride_bytes, int iters,
+                             float *mean_ms)
+{
+  int rc;
+  if ((rc = check_rays(r, src, out_dev, out_row_stride_bytes))) return rc;
+  if (iters <= 0 || !mean_ms) return fail(EU_ERR_ARGUMENT, "bad iteration count");
+  if (!r->rays_on_device) return fail(EU_ERR_ARGUMENT, "render_rays_timed: the rays lie in device memory");
+  if ((rc = ensure_init())) return rc;
+  if (!src->dev) return fail(EU_ERR_HANDLE, "render_rays: the source has no container");
+  const eu_switches sw = eu_read_switches();
+  if ((rc = upload_ray_taps(r))) return rc;
+  auto once = [&]() {
+    return launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out_dev, out_row_stride_bytes, r->width, r->height,
+                       g.stream);
+  };
+  if ((rc = once())) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct guard {
+    hipEvent_t &a, &b;
+    ~guard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } events { e0, e1 };
+  HIPCHK(hipEventCreate(&e0));
+  HIPCHK(hipEventCreate(&e1));
+  HIPCHK(hipEventRecord(e0, g.stream));
+  for (int i = 0; i < iters; i++)
+    if ((rc = once())) return rc;
+  HIPCHK(hipEventRecord(e1, g.stream));
+  HIPCHK(hipEventSynchronize(e1));
+  float ms = 0.0f;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  *mean_ms = ms / iters;
+  return EU_OK;
+}
+
+// DIAGNOSTIC (not declared in eu_hip.h): a source handle without a container, made without a device, so that
+// the argument checks of eu_hip_render_rays can be exercised where there is none (tests/test_rays_host.py).
+// Only eu_hip_render_rays[_timed] - which refuse it once they have a device - and eu_hip_source_release take it.
+int eu_hip_diag_host_source(const eu_facet *fct, int spline_degree, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!out) return fail(EU_ERR_ARGUMENT, "null argument");
+  eu_source *s = new (std::nothrow) eu_source;
+  if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
+  memset(s, 0, sizeof *s);
+  s->fct = *fct; s->degree = spline_degree; s->nch = fct->nchannels;
+  *out = s;
+  return EU_OK;
 }
 
 int eu_hip_sync(void)

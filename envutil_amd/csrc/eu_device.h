@@ -120,4 +120,21 @@ struct eu_render_params {
   eu_inv_planar inv;         // ... of a --single job (all zero otherwise)
 };
 
+// eu_hip_render_rays (eu_render_rays.hip): `act` and `put` on rays the caller supplies, in the source's frame.
+// The array is a width x height grid of rays (ninputs 3) or ninepacks (9); row strides may exceed the rows.
+struct eu_rays_params {
+  int width, height;
+  int ninputs, ntaps;        // 3: rays, no taps; 9: ninepacks {ray, x-neighbour, y-neighbour} and the tap table
+  int nch, nch_out;          // channels of the source / of the output (repix_t when they differ)
+  const float *rays;
+  long long ray_stride;      // floats per row of rays
+  const float *taps;         // [ntaps][3], x and y already scaled by 4
+  float *out;
+  long long out_stride;      // floats per output row
+  int tiles_x, tiles_y;      // grid of wave tiles, four rows each; flat: one row of tiles of four waves each
+  int unit_rows;             // tile rows per XCD unit (eu_xcd_tile)
+  int flat;                  // height == 1: the four waves of a workgroup take consecutive pieces of the row
+  eu_src_dev src;
+};
+
 #endif

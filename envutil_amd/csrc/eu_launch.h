@@ -60,6 +60,8 @@ int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const fl
                       unsigned long long plan_gen, void *stream, int *launches);
 size_t eu_render4_worklist_ints(size_t ntiles);
 size_t eu_render4_worklist_header_ints(void);
+// path: an eu_ray_path, as eu_select_ray_path() chose it
+int eu_launch_render_rays(const eu_rays_params *p, int path, void *stream);
 int eu_launch_render_multi(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);

@@ -58,6 +58,16 @@ __global__ __launch_bounds__(256) void eu_render_kernel(const eu_render_params p
     dst[3 * x] = rx; dst[3 * x + 1] = ry; dst[3 * x + 2] = rz;
     return;
   }
+  if (p.stage == 3 || p.stage == 4) {
+    // the neighbour rays of a twined job (deriv_stepper, stepper.h:1591-1715): r10 of the x-biased stepper,
+    // r01 of the y-biased one - with stage 1 the ninepack twine_t::eval reads
+    if constexpr (TWINE) {
+      if (p.stage == 3) eu_stepper<GEN>(p, p.col + 2 * p.width, p.col + 3 * p.width, rowt, x, rx, ry, rz);
+      else eu_stepper<GEN>(p, col0, col1, rowt + EU_ROW_VARIANT, x, rx, ry, rz);
+      dst[3 * x] = rx; dst[3 * x + 1] = ry; dst[3 * x + 2] = rz;
+    }
+    return;
+  }
   if (p.stage == 2) {
     float sx, sy;
     int face;

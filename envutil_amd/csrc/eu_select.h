@@ -8,6 +8,7 @@
 //   packed in runs   the same, one launch per run of rows that want the same work layout
 //   staged           eu_render4.hip   LDS-staged tiles plus the direct-gather kernel behind them
 //                                     (eu_staged_covers), two launches
+// A call with the caller's own rays (eu_hip_render_rays) has two forms of its own: eu_select_ray_path().
 #ifndef EU_SELECT_H
 #define EU_SELECT_H
 #include <algorithm>
@@ -67,12 +68,19 @@ inline eu_switches eu_read_switches()
 inline bool eu_cube_source(int prj) { return prj == EU_CUBEMAP || prj == EU_BIATAN6; }
 
 // the packed two-pixel kernels (eu_render2.hip): table-driven forms on lat/lon and cube sources
+// ... what they ask of the source and the channel counts: a lat/lon or cube source without lens polynomial,
+// degrees 1-3, dense texels, no channel adaption
+inline bool eu_packed_covers_source(const eu_src_dev &s, int nch, int nch_out)
+{
+  if (s.has_lcp || nch_out != nch) return false;
+  if (s.prj != EU_SPHERICAL && !eu_cube_source(s.prj)) return false;
+  if (s.degree < 1 || s.degree > 3 || s.es0 != nch) return false;
+  return nch >= 1 && nch <= 4;
+}
 inline bool eu_packed_covers(const eu_render_params &p)
 {
-  if (p.stage != 0 || p.form >= EU_FORM_FISH || p.src.has_lcp || p.nch_out != p.nch) return false;
-  if (p.src.prj != EU_SPHERICAL && !eu_cube_source(p.src.prj)) return false;
-  if (p.src.degree < 1 || p.src.degree > 3 || p.src.es0 != p.nch) return false;
-  return p.nch >= 1 && p.nch <= 4;
+  if (p.stage != 0 || p.form >= EU_FORM_FISH) return false;
+  return eu_packed_covers_source(p.src, p.nch, p.nch_out);
 }
 
 // the staged kernels (eu_render4.hip): 16x8 wave tiles, at most 65535 * 8 units of 4 tile rows
@@ -140,6 +148,18 @@ inline eu_path eu_select_path(const eu_render_params &p, const eu_switches &sw, 
   const bool worth = sw.hybrid == 2 || p.src.degree >= 2;
   if (sw.hybrid && worth && !p.twine && p.norm_mode == EU_NORM_NONE && p.src.prj == EU_SPHERICAL) return EU_PATH_PACKED_RUNS;
   return EU_PATH_PACKED;
+}
+
+// ---- rays from the caller (eu_hip_render_rays, eu_render_rays.hip) -------------------------------
+// There is no stepper, so no form, no normalisation and no plan: the source and the channel counts decide.
+//   general  eu_rays_kernel   one ray or ninepack per lane: every mount, every degree, channel adaption, --mask_for
+//   packed   eu_rays2_kernel  two per lane through eu_coord2 / eu_eval2: what eu_packed_covers_source() admits
+enum eu_ray_path { EU_RAYS_GENERAL, EU_RAYS_PACKED };
+
+inline eu_ray_path eu_select_ray_path(const eu_rays_params &p, const eu_switches &sw)
+{
+  if (p.src.mask_paint || sw.force_general) return EU_RAYS_GENERAL;
+  return eu_packed_covers_source(p.src, p.nch, p.nch_out) ? EU_RAYS_PACKED : EU_RAYS_GENERAL;
 }
 
 // ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------

@@ -123,6 +123,12 @@ struct arguments : public facet_base
   bool tethered = false;
   void *p_screen_data = nullptr;
   bool verbose = false;
+  // --ray_map FILE (no counterpart in the reference): the single facet's image is evaluated at the rays of a
+  // 3-channel image instead of a stepper's - x, y, z in the facet's frame, used as given (eu_hip_render_rays);
+  // the output has the map's size. p_ray_map: ray_map_width x ray_map_height x 3 floats, caller-owned.
+  std::string ray_map;
+  const float *p_ray_map = nullptr;
+  int ray_map_width = 0, ray_map_height = 0;
 
   // target extent and step, envutil_main.cc:1203-1232
   void target_setup()
@@ -271,6 +277,16 @@ struct hip_dispatch : public dispatch_base
         if (rc != EU_OK) return rc;
       }
       srcs.push_back(it->second);
+    }
+    if (args.p_ray_map) {
+      // `act` alone at the caller's rays: no stepper, no target geometry, no twining
+      if (srcs.size() != 1 || ninputs != 3 || args.tethered || args.ray_map_width <= 0 || args.ray_map_height <= 0)
+        return EU_ERR_ARGUMENT;
+      eu_rays r {};
+      r.width = args.ray_map_width; r.height = args.ray_map_height;
+      r.ninputs = 3; r.nchannels = nchannels;
+      r.rays = args.p_ray_map; r.ray_row_stride_bytes = size_t(r.width) * 3 * sizeof(float);
+      return eu_hip_render_rays(&r, srcs[0], args.p_output, size_t(r.width) * nchannels * sizeof(float), 0, nullptr);
     }
     eu_target t {};
     t.projection = projection; t.width = args.width; t.height = args.height;

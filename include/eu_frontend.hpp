@@ -145,7 +145,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_precise", 0 }, { "--twine_width", 1 }, { "--twine_density", 1 }, { "--twine_sigma", 1 },
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
-    { "--nchannels", 1 } };
+    { "--nchannels", 1 }, { "--ray_map", 1 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets;
   std::vector<std::string> photos, addenda;
@@ -410,6 +410,24 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   if (a.nfacets == 1) a.solo = 0;
   a.mask_for = in("--mask_for", -1);
   if (a.mask_for >= a.nfacets) { err = "--mask_for beyond the last facet"; return false; }
+
+  // --ray_map: the single facet's image at the rays of a file. The rays are in the facet's frame and are used
+  // as given, so there is nothing an orientation could apply to; what cannot be honoured is refused, not guessed
+  a.ray_map = str("--ray_map", "");
+  if (!a.ray_map.empty()) {
+    if (a.nfacets != 1) { err = "--ray_map evaluates the image of one facet: " + std::to_string(a.nfacets) + " facets given"; return false; }
+    const facet_spec &f0 = a.facet_spec_v[0];
+    if (f0.yaw != 0.0 || f0.pitch != 0.0 || f0.roll != 0.0 || a.yaw != 0.0 || a.pitch != 0.0 || a.roll != 0.0) {
+      err = "--ray_map: the rays are in the facet's own frame - facet and camera yaw / pitch / roll must be zero (rotate the rays instead)";
+      return false;
+    }
+    if ((has("--twine") && a.twine > 1) || !a.twf_file.empty()) {
+      err = "--ray_map evaluates single rays: no --twine above 1 and no --twf_file (twining needs ninepacks, eu_hip_render_rays)";
+      return false;
+    }
+    if (a.single >= 0 || !a.split.empty()) { err = "--ray_map does not go with --single / --split"; return false; }
+    a.twine = 0;                   // automatic twining is not applied either
+  }
 
   // brightness from the Eev values (envutil_main.cc:1003-1060), channel counts (:1062-1157)
   a.nchannels = 1;

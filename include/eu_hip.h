@@ -107,9 +107,13 @@ typedef struct eu_target {
   int32_t ntaps;
   const float *taps;             /* host pointer, ntaps x {x, y, weight}       */
   int32_t row_begin, row_end;    /* rows [row_begin,row_end): multi-GPU tiling */
-  int32_t stage;                 /* 0 pixels; 1 rays; 2 source coordinates
-                                    (stages 1/2 write 3 floats per pixel; used
-                                    by the stage-wise parity tests)            */
+  int32_t stage;                 /* 0 pixels; 1 rays; 2 source coordinates;
+                                    3 / 4 the rays of the x-biased / y-biased
+                                    stepper of a twined job (ntaps > 0; else
+                                    EU_ERR_ARGUMENT): with stage 1 the ninepack
+                                    twine_t::eval reads, see eu_rays. Stages
+                                    1-4 write 3 floats per pixel, single-facet
+                                    jobs only                                  */
   /* args.store_cropped + p_crop_* (envutil_basic.h:684-687; applied at
    * envutil_payload.cc:440-474): the job renders crop_w x crop_h pixels whose
    * discrete coordinates start at (crop_x0, crop_y0) of the width x height
@@ -303,6 +307,47 @@ int  eu_hip_sync(void);
 int  eu_hip_render_timed(const eu_target *trg, eu_source *const *srcs, int nsrc,
                          float *out_dev, size_t out_row_stride_bytes,
                          int iters, float *mean_ms);
+
+/* ---- `act` alone: a resident source at the caller's rays -------------------- */
+/* The reference's pipeline is get (a stepper), act (environment, inside twine_t when twining) and put.
+ * eu_hip_render is all three; this entry is act + put on rays the CALLER supplies: a viewer with a projection
+ * the library has no stepper for, a remap from a precomputed ray map, an environment lookup at an array of
+ * directions.
+ *
+ * Rays are what `act` sees: three floats x, y, z (RIGHT, DOWN, FORWARD) in the SOURCE's frame - exactly what
+ * eu_target.stage = 1 writes. In the reference the facet's orientation is folded into the stepper's basis, so
+ * this path applies NEITHER the facet's yaw / pitch / roll NOR any camera orientation: a caller who wants them
+ * rotates the rays. Rays need not be normalised; they are used as given.
+ *
+ * ninputs = 9: every element is a ninepack {ray, x-neighbour, y-neighbour} as twine_t::eval reads it
+ * (twining.h:128-263, differencing branch; eu_target.stage = 1, 3, 4 write the three parts for a job):
+ * dx = in[3..5] - in[0..2], dy = in[6..8] - in[0..2], out = sum over the taps, in order, of
+ * w * inner(ray + 4x * dx + 4y * dy). `taps` is make_spread's output ({x, y, weight} per tap, host memory).
+ *
+ * Arithmetic: the device functions of the render kernels in their order - the rays of a job give that job's
+ * frame bit for bit. One documented difference from the reference, because a caller's array holds arbitrary
+ * bit patterns: a ray with a non-finite component, or with all three components zero, is a MISS - zeros in
+ * every channel - and so is a ninepack with a non-finite float among its nine or a null centre ray
+ * (eu_ray_guard.h; no other ray can make a read leave the container).
+ *
+ * The array is a width x height grid (a flat list: height = 1); row strides count bytes, are multiples of 4 and
+ * may exceed the rows. One source, float output. `rays` and `out` may each lie in host or in device memory:
+ * with both on the device the call is asynchronous on `stream` (NULL: the library's) until eu_hip_sync();
+ * otherwise the grid is staged in bounded chunks and the call returns when `out` is complete. Argument errors
+ * (EU_ERR_ARGUMENT) are reported before a device is looked for. eu_hip_render, its plan caches and
+ * eu_hip_launch_count() are not touched. */
+typedef struct eu_rays {
+  int32_t width, height;            /* rays per row, rows                                   */
+  int32_t ninputs;                  /* 3: rays; 9: ninepacks (twine_t)                      */
+  int32_t nchannels;                /* output channels 1..4 (repix_t as eu_target.nchannels)*/
+  int32_t ntaps; const float *taps; /* ninputs 9: make_spread output, host, <= EU_MAX_TAPS  */
+  const float *rays; size_t ray_row_stride_bytes; int32_t rays_on_device;
+} eu_rays;
+int  eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out,
+                        size_t out_row_stride_bytes, int out_on_device, void *stream);
+/* the kernel alone, `iters` launches back to back on the library's stream (rays and output in device memory) */
+int  eu_hip_render_rays_timed(const eu_rays *r, eu_source *src, float *out_dev,
+                              size_t out_row_stride_bytes, int iters, float *mean_ms);
 
 /* device memory helpers for hosts without a HIP binding of their own */
 int  eu_hip_malloc(void **p, size_t bytes);

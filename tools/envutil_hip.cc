@@ -3,6 +3,7 @@
 //   envutil_hip --facet pano.pfm spherical 360 0 0 0 --projection cubemap --hfov 90
 //               --width 1024 --degree 3 --output cube.pfm
 //   envutil_hip --pto project.pto --output pano.pfm
+//   envutil_hip --facet pano.pfm spherical 360 0 0 0 --degree 3 --ray_map rays.pfm --output looked_up.pfm
 //   envutil_hip <fixed options> -          (pipe mode: one job per line of stdin)
 //
 // The same options, defaults and PTO handling as the reference's main() / core()
@@ -71,6 +72,8 @@ static int run_payload(const std::string &output)
 {
   int ow = args.width, oh = args.height;
   if (args.store_cropped) { ow = args.p_crop_x1 - args.p_crop_x0; oh = args.p_crop_y1 - args.p_crop_y0; }
+  const bool ray_map = args.p_ray_map != nullptr;            // --ray_map: the output has the map's size
+  if (ray_map) { ow = args.ray_map_width; oh = args.ray_map_height; }
   std::vector<float> out(size_t(ow) * oh * args.nchannels);
   args.p_output = out.data();
   const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
@@ -80,7 +83,7 @@ static int run_payload(const std::string &output)
     return 1;
   }
   std::string err;
-  const bool cube = (args.projection == CUBEMAP || args.projection == BIATAN6) && !args.store_cropped;
+  const bool cube = (args.projection == CUBEMAP || args.projection == BIATAN6) && !args.store_cropped && !ray_map;
   // save_array attaches the target's projection and hfov (degrees) to the file (envutil_basic.h:770-772)
   io::metadata meta;
   meta.projection = projection_name[args.projection];
@@ -90,7 +93,8 @@ static int run_payload(const std::string &output)
     std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
     return 1;
   }
-  if (!io::write_image(output, out.data(), ow, oh, args.nchannels, cube, err, &meta)) {
+  // (a ray map's output has no projection of its own to record)
+  if (!io::write_image(output, out.data(), ow, oh, args.nchannels, cube, err, ray_map ? nullptr : &meta)) {
     std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
     return 1;
   }
@@ -160,6 +164,26 @@ static int core(int argc, const char *const *argv)
     f.pixels = pixels[k].data();
   }
 
+  // --ray_map FILE: a 3-channel PFM of rays in the facet's frame
+  std::vector<float> ray_map;
+  args.p_ray_map = nullptr;
+  if (!args.ray_map.empty()) {
+    int w = 0, h = 0, nch = 0;
+    if (!io::read_image(args.ray_map, ray_map, w, h, nch, err)) {
+      std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+      return 2;
+    }
+    const std::string &n = args.ray_map;
+    if (nch != 3 || n.size() < 4 || n.compare(n.size() - 4, 4, ".pfm") != 0) {
+      std::fprintf(stderr, "envutil_hip: --ray_map %s: a ray map is a 3-channel PFM (x, y, z per pixel)\n", n.c_str());
+      return 2;
+    }
+    args.p_ray_map = ray_map.data(); args.ray_map_width = w; args.ray_map_height = h;
+    const int rc = run_payload(args.output);
+    args.p_ray_map = nullptr;
+    return rc;
+  }
+
   if (!args.split.empty()) {
     int rc = 0;
     const int nfacets = args.nfacets;
@@ -190,6 +214,8 @@ int main(int argc, const char **argv)
         "  source:   --facet IMAGE PROJECTION HFOV YAW PITCH ROLL (repeatable) | --photo IMAGE | --pto FILE [--pto_line LINE]\n"
         "            projections: spherical cylindrical rectilinear stereographic fisheye cubemap biatan6\n"
         "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge\n"
+        "  rays:     --ray_map FILE.pfm  the single facet's image at the rays x y z of a 3-channel PFM, in the facet's\n"
+        "            frame (no yaw / pitch / roll, no twining); the output has the map's size\n"
         "  target:   --output FILE  --projection P  --hfov DEG  --width W  --height H  --yaw --pitch --roll DEG\n"
         "            --x0 --x1 --y0 --y1 (extent instead of hfov)  --nchannels N  --brighten F\n"
         "  spline:   --degree D  --prefilter D  --support_min PX  --tile_size PX (cubemap sources)\n"
