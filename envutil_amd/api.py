@@ -685,6 +685,20 @@ def render_rays_timed(source, rays, out_dev_ptr, iters, nchannels=None, taps=Non
             L.eu_hip_free(tmp)
 
 
+def listed_tiles():
+    """eu_hip_listed_tiles: the wave tiles the last staged launch pair left to the direct-gather kernel"""
+    f = lib().eu_hip_listed_tiles
+    f.restype = C.c_ulonglong
+    return int(f())
+
+
+def launch_count():
+    """eu_hip_launch_count: render kernel launches of single-facet jobs so far"""
+    f = lib().eu_hip_launch_count
+    f.restype = C.c_ulonglong
+    return int(f())
+
+
 def sync():
     """eu_hip_sync: wait for the library's stream and the stream of the last asynchronous call"""
     _check(lib().eu_hip_sync())

@@ -705,8 +705,13 @@ void refresh_seg_flags(const eu_render_params *p)
 // tiles left to the direct-gather kernel that follows it on the same stream) and its order between streams
 int launch_staged(const eu_render_params *p, const eu_switches &sw, hipStream_t st, int *launches)
 {
-  const size_t ntiles = (size_t)((p->width + 15) / 16) * (size_t)((p->row_end - p->row_begin + 7) / 8);
-  const size_t need = eu_render4_worklist_ints(ntiles);
+  // (more tiles than the work list has ids for: eu_staged_covers said no, and eu_select_path never names this path)
+  const unsigned long long ntiles = eu_staged_tiles(p->width, p->row_begin, p->row_end);
+  if (ntiles > EU4_WL_MAX_TILES) return -2;
+  // every tile of the launch may be listed: the capacity holds for all of them (eu_worklist.h). A buffer that grows
+  // starts with an empty header - the entries need no clearing, the counters say how many of them count - and a
+  // smaller job behind a larger one finds the lists emptied by the larger one's last workgroup
+  const size_t need = eu_render4_worklist_ints((size_t)ntiles);
   if (g.wl.cap < need) {
     if (g.wl.reserve(need) != hipSuccess) return -1;
     if (hipMemsetAsync(g.wl.p, 0, eu_render4_worklist_header_ints() * sizeof(int), st) != hipSuccess) { g.wl.cap = 0; return -1; }
@@ -1481,6 +1486,17 @@ int eu_hip_layout_segments(const eu_target *trg, eu_source *const *srcs, int nsr
 // render kernel launches of this process so far (a render step of a big cubic job is
 // several: launch-level layout choice); lets a benchmark report launches per step
 unsigned long long eu_hip_launch_count(void) { return g.launches; }
+
+unsigned long long eu_hip_listed_tiles(void)
+{
+  // the direct-gather kernel's last workgroup leaves the sum of the lists' counters in the header; the event
+  // behind the pair is the library's own (the caller's stream may be gone by now)
+  if (!g.wl.p || !g.wl_stream_set || !g.wl_done) return 0;
+  int n = 0;
+  if (hipEventSynchronize(g.wl_done) != hipSuccess) return 0;
+  if (hipMemcpy(&n, g.wl.p + EU4_WL_LISTED, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return n > 0 ? (unsigned long long)n : 0ull;
+}
 
 int eu_hip_band_rows(int height, int band_rows, int band_count, int band_index)
 {

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include "eu_device.h"
 #include "eu_select.h"
+#include "eu_worklist.h"
 
 // early-miss tables of a multi-facet job (eu_render_multi.hip: eu_multi_maybe): per facet a header and
 // EU_REJ_N bins over u = cos(angle to the facet's axis)
@@ -58,8 +59,6 @@ int eu_launch_render2(const eu_render_params *p, const eu_switches *sw, void *st
 // direct-gather kernels are faster (eu_staged_worth; the plan stays cached)
 int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const float *h_row, size_t h_row_floats,
                       unsigned long long plan_gen, void *stream, int *launches);
-size_t eu_render4_worklist_ints(size_t ntiles);
-size_t eu_render4_worklist_header_ints(void);
 // path: an eu_ray_path, as eu_select_ray_path() chose it
 int eu_launch_render_rays(const eu_rays_params *p, int path, void *stream);
 int eu_launch_render_multi(const eu_multi_params *p, int degree, void *stream);

@@ -48,12 +48,8 @@
                            // 16 single-wave workgroups per CU (the hardware's limit) use 144 of 160 KB
 #define EU4_OCC0 4         // waves per SIMD the registers are capped for
 #endif
-#define EU4_SHARDS 1024    // work list of the direct-gather kernel: EU4_SHARDS lists, a tile goes to list id % EU4_SHARDS
-// layout of eu_render_params::wl (ints); every counter on a 64-byte line of its own
-#define EU4_WL_SHARD(s) (16 * (s))                       // entries in list s
-#define EU4_WL_DONE1 (16 * EU4_SHARDS)                   // finished workgroups, direct-gather kernel
-#define EU4_WL_DYN(x) (16 * (EU4_SHARDS + 1 + (x)))       // eu_render5_kernel: next batch of XCD x's second loop
-#define EU4_WL_ENTRIES (16 * (EU4_SHARDS + 16))          // entry k of list s at + k * EU4_SHARDS + s
+// the work list of the direct-gather kernel - EU4_SHARDS lists, a tile goes to list eu4_shard_of(id) - and the layout
+// of eu_render_params::wl (EU4_WL_*): eu_worklist.h, through eu_launch.h
 #define EU4_UNIT_ROWS 4    // tile rows per XCD unit (32 pixel rows)
 #define EU4_COL_FLOATS 8   // per-column table: ix, tx, wx[0..3], sqrt(rx^2 + rz^2), longitude
 #define EU4_MAX_PLANS 16
@@ -221,7 +217,7 @@ __device__ __forceinline__ void eu4_tile(const eu_render_params &p, const eu4_pl
     // ~88 returning atomics per microsecond on one word)
     if (lane == 0) {
       const int id = tile_y * w.tiles16 + x0 / EU4_TW;
-      const int sh = (int)(((unsigned)id * 0x9E3779B1u) >> 22) & (EU4_SHARDS - 1);   // eu4_shard_of
+      const int sh = eu4_shard_of(id);
       const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
       p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
     }
@@ -427,7 +423,7 @@ __global__ __launch_bounds__(256) void eu_colplan_kernel(const eu_render_params 
 // ---------------------------------------------------------------------------
 // the direct-gather kernel: the tiles of the work list, (d+1)^2 taps from global memory,
 // every scalar fallback of the coordinate arithmetic; the last workgroup to finish
-// empties the list for the next launch pair
+// notes how many tiles the lists held and empties them for the next launch pair
 // ---------------------------------------------------------------------------
 template <int NCH, int DEG, int PRJ>
 __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_params p, const eu4_plan w)
@@ -451,13 +447,20 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
     const int x0 = (id - tile_y * w.tiles16) * EU4_TW;
     eu4_direct_tile<NCH, DEG, PRJ>(p, atab, tile_y, x0, lane);
   }
-  __shared__ int last;
+  __shared__ int last, listed;
   __syncthreads();
-  if (threadIdx.x == 0) last = atomicAdd(p.wl + EU4_WL_DONE1, 1) == (int)gridDim.x - 1;
+  if (threadIdx.x == 0) { listed = 0; last = atomicAdd(p.wl + EU4_WL_DONE1, 1) == (int)gridDim.x - 1; }
   __syncthreads();
   if (last) {
+    // what the lists held, for eu_hip_listed_tiles(): every thread adds up the counters it is about to clear
+    int mine = 0;
+    for (int i = threadIdx.x; i < EU4_SHARDS; i += 256)
+      mine += __hip_atomic_load(p.wl + EU4_WL_SHARD(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    atomicAdd(&listed, mine);
     for (int i = threadIdx.x; i <= EU4_SHARDS + 8; i += 256)         // the lists, the counter of this kernel, the staged kernel's queues
       __hip_atomic_store(p.wl + 16 * i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(p.wl + EU4_WL_LISTED, listed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -545,13 +548,6 @@ static int launch4_n(const eu_render_params &p, const eu4_plan &w, hipStream_t s
   }
   return -2;
 }
-
-// ints the work list buffer needs for a launch of `ntiles` wave tiles
-extern "C" size_t eu_render4_worklist_ints(size_t ntiles)
-{
-  return EU4_WL_ENTRIES + ((ntiles + EU4_SHARDS - 1) / EU4_SHARDS) * EU4_SHARDS;
-}
-extern "C" size_t eu_render4_worklist_header_ints(void) { return EU4_WL_ENTRIES; }
 
 // ---------------------------------------------------------------------------
 // host: the column plans of a launch. A tile row can take the x half of its coordinates

@@ -1,4 +1,4 @@
-// included by eu_render4.hip behind eu4_plan, eu4_dma_row and the work-list layout (EU4_WL_*)
+// included by eu_render4.hip behind eu4_plan and eu4_dma_row; the work list (EU4_WL_*, eu4_shard_of): eu_worklist.h
 // ---------------------------------------------------------------------------
 // Round 3: the staged kernel as PERSISTENT wavefronts (eu_render5_kernel).
 //
@@ -33,15 +33,6 @@
 #ifndef EU5_UNIT_ROWS
 #define EU5_UNIT_ROWS 4     // tile rows per XCD unit
 #endif
-
-// the work list a tile goes to: a multiplicative hash of the tile id. (id % EU4_SHARDS keeps the
-// tile COLUMN: the tiles around a pole then land in a sixth of the lists, and the direct-gather
-// kernel's waves on those lists work through ~10 tiles each while the others idle: 0.23 ms for
-// 1.6 % of the headline's tiles.)
-__device__ __forceinline__ int eu4_shard_of(int id)
-{
-  return (int)(((unsigned)id * 0x9E3779B1u) >> 22) & (EU4_SHARDS - 1);
-}
 
 typedef const __attribute__((address_space(3))) eu4_f4 *eu5_l4ptr;
 

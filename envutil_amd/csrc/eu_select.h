@@ -17,6 +17,7 @@
 #include <vector>
 #include "eu_device.h"
 #include "eu_share_groups.h"
+#include "eu_worklist.h"
 
 // ---- the switches ------------------------------------------------------------------------------
 // One field per EU_HIP_* variable the library reads. eu_read_switches() is the only reader: every
@@ -83,16 +84,26 @@ inline bool eu_packed_covers(const eu_render_params &p)
   return eu_packed_covers_source(p.src, p.nch, p.nch_out);
 }
 
-// the staged kernels (eu_render4.hip): 16x8 wave tiles, at most 65535 * 8 units of 4 tile rows
+// the staged kernels (eu_render4.hip): 16x8 wave tiles, at most 65535 * 8 units of 4 tile rows, and no more
+// tiles in a launch than the work list has ids for (eu_worklist.h: a tile id is an int)
 #define EU_STAGED_TILE_ROWS 8
+#define EU_STAGED_TILE_COLS 16
 #define EU_STAGED_MAX_TILES_Y (65535 * 8 * 4)
+// wave tiles of a launch over rows [row_begin, row_end) of a frame `width` pixels wide
+inline unsigned long long eu_staged_tiles(int width, int row_begin, int row_end)
+{
+  const long long tx = ((long long)width + EU_STAGED_TILE_COLS - 1) / EU_STAGED_TILE_COLS;
+  const long long ty = ((long long)row_end - row_begin + EU_STAGED_TILE_ROWS - 1) / EU_STAGED_TILE_ROWS;
+  return tx > 0 && ty > 0 ? (unsigned long long)tx * (unsigned long long)ty : 0ull;
+}
 inline bool eu_staged_covers(const eu_render_params &p)
 {
   if (!eu_packed_covers(p) || p.twine) return false;
   if (p.norm_mode != EU_NORM_NONE && p.norm_mode != EU_NORM_DIV) return false;
   if (p.nch != 3 && p.nch != 4) return false;
   if (p.src.es1 * 4 >= (1ll << 31)) return false;            // the staging offsets are 32-bit
-  return (p.row_end - p.row_begin + EU_STAGED_TILE_ROWS - 1) / EU_STAGED_TILE_ROWS <= EU_STAGED_MAX_TILES_Y;
+  if ((p.row_end - p.row_begin + EU_STAGED_TILE_ROWS - 1) / EU_STAGED_TILE_ROWS > EU_STAGED_MAX_TILES_Y) return false;
+  return eu_staged_tiles(p.width, p.row_begin, p.row_end) <= EU4_WL_MAX_TILES;
 }
 
 // 'ray = B * c0 + A' without normalisation over the whole frame, on a source every finite ray hits

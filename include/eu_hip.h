@@ -165,6 +165,15 @@ unsigned long long eu_hip_launch_count(void);
  * the tables the kernel reads do not agree bit for bit, and under EU_HIP_SHARE=0 */
 unsigned long long eu_hip_share_follower_tiles(void);
 
+/* 16x8 wave tiles that the last staged launch pair of this process handed to its second kernel, the
+ * direct-gather kernel, through the work list (tiles whose texel box does not fit a wave's LDS slice, tiles
+ * with a lane on a scalar fallback of the coordinate arithmetic); waits for that pair. 0 before the first
+ * staged launch. A job that took another path leaves the count of the last staged pair in place, and so does
+ * a staged strip of no tiles (nothing is launched for it). A hook for tests, for a process that renders on ONE
+ * device: it reads the current device's list without selecting a device, and it copies the word with a
+ * blocking hipMemcpy on the null stream, which also waits for every other blocking stream. */
+unsigned long long eu_hip_listed_tiles(void);
+
 /* number of local rows of part band_index (see eu_target.band_*) in a frame of
  * `height` rows; height itself when band_count <= 1 */
 int  eu_hip_band_rows(int height, int band_rows, int band_count, int band_index);

@@ -126,6 +126,8 @@ void test_paths()
   { eu_render_params p = config3(); p.src.degree = 1; expect("config3 bilinear", p, d, EU_PATH_PACKED); }
   { eu_render_params p = config3(); p.norm_mode = EU_NORM_DIV; p.form = EU_FORM_BA; expect("cube source, normalised BA target", p, d, EU_PATH_STAGED); }
   { eu_render_params p = config3(); p.norm_mode = EU_NORM_CYL; expect("cube source, cylindrical normalisation", p, d, EU_PATH_PACKED); }
+  // a downscaling job of 1024 wave tiles, every one of them for the work list (tests/test_gpu_worklist.py): staged without a switch
+  expect("cube source 1024, cubic, spherical 512 x 256", job(EU_CUBEMAP, 1024, 3, 3, EU_FORM_BCA, EU_NORM_NONE, 512, 256), d, EU_PATH_STAGED);
   // ---- config 4: twining ----
   expect("config4", config4(), d, EU_PATH_PACKED);
   expect("config4 R4=1", config4(), with_r4(1), EU_PATH_PACKED);
@@ -235,6 +237,22 @@ void test_profiles()
   check(eu_staged_covers(headline()) && eu_packed_covers(headline()), "headline: both kernels cover it");
   check(!eu_staged_covers(config4()) && eu_packed_covers(config4()), "config4: packed only");
   check(!eu_staged_covers(config5_facet()) && !eu_packed_covers(config5_facet()), "config5 facet: neither");
+  // a tile id of the work list is an int: the tallest strip the staged kernels take (EU_STAGED_MAX_TILES_Y tile rows)
+  // at 1024 tile columns has 2147450880 tiles, at 1025 columns more than INT_MAX
+  {
+    eu_render_params p = headline();
+    p.height = p.row_end = EU_STAGED_MAX_TILES_Y * EU_STAGED_TILE_ROWS;
+    p.width = 1024 * 16;
+    check(eu_staged_tiles(p.width, p.row_begin, p.row_end) == 2147450880ull && eu_staged_covers(p), "2147450880 tiles: staged");
+    p.width = 1024 * 16 + 1;
+    check(eu_staged_tiles(p.width, p.row_begin, p.row_end) > (unsigned long long)INT_MAX && !eu_staged_covers(p) && eu_packed_covers(p),
+          "more tiles than an int holds: not staged");
+    expect("more tiles than an int holds", p, defaults(), EU_PATH_PACKED_RUNS);
+    expect("more tiles than an int holds, R4=1", p, with_r4(1), EU_PATH_PACKED_RUNS);
+    p.row_end = p.height = p.height + 1;
+    p.width = 16;
+    check(!eu_staged_covers(p), "one tile row more than the grid has: not staged");
+  }
   // the post-plan test: cubic / quadratic and column plans on at least half of the tile rows
   check(eu_staged_worth(3, 3072, 3072), "worth: every tile row planned");
   check(eu_staged_worth(3, 1536, 3072) && eu_staged_worth(2, 1536, 3072), "worth: half of the tile rows planned");
