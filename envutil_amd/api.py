@@ -66,6 +66,13 @@ class Rays(C.Structure):
                 ("rays_on_device", C.c_int32)]
 
 
+class View(C.Structure):
+    """struct eu_view"""
+    _fields_ = [("yaw", C.c_double), ("pitch", C.c_double), ("roll", C.c_double),
+                ("x0", C.c_double), ("x1", C.c_double), ("y0", C.c_double), ("y1", C.c_double)]
+
+
+ROW_FLOATS = 24     # floats per row-table entry (EU_ROW_FLOATS)
 OUT_FLOAT, OUT_SRGBA8 = 0, 1
 SYN_PANORAMA, SYN_HDR_MERGE = 0, 1
 
@@ -146,6 +153,8 @@ def lib():
     L.eu_hip_render_timed.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_rays.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_rays_timed.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
+    L.eu_hip_render_views.argtypes = [vp, vp, i32, vp, vp, C.c_size_t, C.c_size_t, i32, vp]
+    L.eu_hip_view_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.eu_hip_layout_segments.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eu_hip_band_rows.argtypes = [i32, i32, i32, i32]
     L.eu_hip_band_rows.restype = i32
@@ -683,6 +692,90 @@ def render_rays_timed(source, rays, out_dev_ptr, iters, nchannels=None, taps=Non
     finally:
         if tmp:
             L.eu_hip_free(tmp)
+
+
+def _views_struct(args, views):
+    """eu_view[] for (yaw, pitch, roll) or (yaw, pitch, roll, hfov) in degrees; args.hfov where a view gives none"""
+    arr = (View * max(len(views), 1))()
+    for k, v in enumerate(views):
+        v = tuple(v)
+        if len(v) not in (3, 4):
+            raise EuError("render_views: a view is (yaw, pitch, roll) or (yaw, pitch, roll, hfov), degrees")
+        hfov = v[3] if len(v) == 4 else args.hfov
+        e = args.extent if hfov == args.hfov else get_extent(args.projection, args.width, args.height, math.radians(hfov))
+        arr[k].yaw, arr[k].pitch, arr[k].roll = (math.radians(float(a)) for a in v[:3])
+        arr[k].x0, arr[k].x1, arr[k].y0, arr[k].y1 = (float(a) for a in e)
+    return arr
+
+
+def _views_args(args, who):
+    if args.store_cropped or args.tethered or args.single is not None:
+        raise EuError(f"{who}: whole float frames of an ordinary target (no crop, not tethered, no single)")
+
+
+def _frames(a, what):
+    """a float32 (N, H, W, C) array, numpy or torch on the device, whose last two axes are dense: (address, row
+    stride, view stride in bytes, on_device). Padded rows and padded views are used in place."""
+    on_device = _is_torch(a)
+    n, h, w, c = a.shape
+    if on_device:
+        import torch
+        if not a.is_cuda or a.dtype != torch.float32:
+            raise EuError(f"render_views: {what} is float32 and on the device")
+        st = tuple(4 * v for v in a.stride())
+    else:
+        if a.dtype != np.float32:
+            raise EuError(f"render_views: {what} is float32")
+        st = tuple(a.strides)
+    if a.size == 0:                 # nothing to stride over
+        st = (h * w * c * 4, w * c * 4, c * 4, 4)
+    row = st[1] if h > 1 else max(st[1], w * c * 4)
+    view = st[0] if n > 1 else max(st[0], h * row)
+    if n and h and w and (st[3] != 4 or st[2] != 4 * c or row < w * c * 4 or row % 4 or view < h * row or view % 4):
+        raise EuError(f"render_views: {what} has dense pixels; only its rows and views may be padded")
+    if on_device:
+        import torch
+        torch.cuda.current_stream(a.device).synchronize()
+        return a.data_ptr(), row, view, True
+    return a.ctypes.data, row, view, False
+
+
+def render_views(args, views, source, nchannels=None, out=None, stream=None):
+    """eu_hip_render_views: many views of one resident source in one call. `args` gives what the views share
+    (projection, size, spline degree, twining); `views` is a sequence of (yaw, pitch, roll) or (yaw, pitch, roll,
+    hfov) in degrees, args.hfov applying where a view gives none. Returns (N, H, W, C) float32, view k being
+    render() of args with that orientation and hfov, bit for bit: a new numpy array, or `out` (numpy, or a float32
+    torch tensor in device memory - of the device the library runs on, which on a host with several is the caller's
+    to see to; rows and views may be padded). With `out` on the device the call is
+    asynchronous on `stream` (a hipStream_t address; None: the library's stream) until sync()."""
+    _views_args(args, "render_views")
+    views = list(views)
+    nch = nchannels or source.fct.nchannels
+    shape = (len(views), args.height, args.width, nch)
+    if out is None:
+        out = np.zeros(shape, np.float32)
+    if tuple(out.shape) != shape:
+        raise EuError(f"render_views: out has shape {tuple(out.shape)}, expected {shape}")
+    optr, row, view, on_device = _frames(out, "out")
+    t = args.target(nch)
+    arr = _views_struct(args, views)
+    _check(lib().eu_hip_render_views(C.byref(t), arr, len(views), source.handle, C.c_void_p(optr), row, view,
+                                     int(on_device), C.c_void_p(stream) if stream else None))
+    return out
+
+
+def view_tables(args, view, source, nchannels=None):
+    """eu_hip_view_tables, for tests: the stepper tables of one view as the table kernel of render_views builds
+    them and as the host builds them for render(). Returns (col_dev, row_dev, col_host, row_host): columns
+    (6, W), rows (H, ROW_FLOATS), float32."""
+    _views_args(args, "view_tables")
+    t = args.target(nchannels or source.fct.nchannels)
+    arr = _views_struct(args, [view])
+    cols = [np.zeros((6, args.width), np.float32) for _ in range(2)]
+    rows = [np.zeros((args.height, ROW_FLOATS), np.float32) for _ in range(2)]
+    _check(lib().eu_hip_view_tables(C.byref(t), arr, source.handle, _ptr(cols[0]), _ptr(rows[0]), _ptr(cols[1]),
+                                    _ptr(rows[1])))
+    return cols[0], rows[0], cols[1], rows[1]
 
 
 def listed_tiles():

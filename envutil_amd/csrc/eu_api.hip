@@ -80,6 +80,13 @@ struct context {
   // and its own staging of host rays
   eu_dev_buf<float> rtaps, rstage;
   std::vector<float> rtaps_host;                  // what rtaps holds
+  // eu_hip_render_views: the views' scalar blocks, the stepper tables the table kernel makes from them (one chunk
+  // of views), its tap table and the staging of a host output - all its own, like eu_hip_render_rays' buffers
+  eu_dev_buf<eu_view_dev> vscal;
+  eu_dev_buf<float> vcol, vrow, vtaps, vstage;
+  std::vector<float> vtaps_host;                  // what vtaps holds
+  hipStream_t views_user = nullptr;               // the stream the last call worked on with these buffers (last_user is
+                                                  // one slot for all entry points: a render in between overwrites it)
   eu_dev_buf<int32_t> aplan;                      // row plan of the last device alpha edit
   hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
@@ -1650,6 +1657,236 @@ int eu_hip_render_rays_timed(const eu_rays *r, eu_source *src, float *out_dev, s
   float ms = 0.0f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
   *mean_ms = ms / iters;
+  return EU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// many views of one resident source in one call (include/eu_hip.h, eu_render_views.hip)
+// ---------------------------------------------------------------------------------------------------------
+
+// bytes of a host output that are staged on the device at a time (at least one view)
+#define EU_VIEWS_STAGE_BYTES ((size_t)64 << 20)
+
+static bool view_finite(const eu_view &v)
+{
+  return std::isfinite(v.yaw) && std::isfinite(v.pitch) && std::isfinite(v.roll) && std::isfinite(v.x0) &&
+         std::isfinite(v.x1) && std::isfinite(v.y0) && std::isfinite(v.y1);
+}
+
+// everything that can be wrong with the shared target and the source, found without a device
+static int check_views_target(const eu_target *t, const eu_source *src)
+{
+  if (!t || !src) return fail(EU_ERR_ARGUMENT, "render_views: null argument");
+  { int rc0 = check_target(t); if (rc0) return rc0; }
+  if (t->stage != 0) return fail(EU_ERR_ARGUMENT, "render_views: stage outputs belong to eu_hip_render");
+  if (t->crop_w != 0) return fail(EU_ERR_ARGUMENT, "render_views: whole frames only, no crop window");
+  if (t->band_count > 1) return fail(EU_ERR_ARGUMENT, "render_views: whole frames only, no row bands");
+  if (t->single) return fail(EU_ERR_ARGUMENT, "render_views: a --single target belongs to eu_hip_render");
+  if (t->out_format != EU_OUT_FLOAT) return fail(EU_ERR_ARGUMENT, "render_views: float output only");
+  if (t->row_begin != 0 || t->row_end != t->height)
+    return fail(EU_ERR_ARGUMENT, "render_views: whole frames only (row_begin 0, row_end height)");
+  // as eu_hip_render: a masking source adapts channel counts with mono_t, which knows 1 and 2 output channels only
+  if (src->fct.mask_paint && src->nch != t->nchannels && t->nchannels > 2)
+    return fail(EU_ERR_ARGUMENT, "--mask_for: a facet whose channel count differs from the target's needs a 1- or 2-channel target");
+  return EU_OK;
+}
+
+// what this path does not render: EU_ERR_UNSUPPORTED
+static int check_views_supported(const eu_target *t, const eu_view *views, int nviews, const eu_source *src, int *form,
+                                 int *norm_mode)
+{
+  if (eu::has_translation(src->fct))
+    return fail(EU_ERR_UNSUPPORTED, "render_views: a facet with PTO translation is stepped by the generic stepper: use eu_hip_render");
+  const bool twine = t->ntaps > 0;
+  if (!eu::stepper_form(t->projection, twine, *form, *norm_mode))
+    return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
+  if (t->projection == EU_BIATAN6) {
+    // eu_tanf has libm's bits for in-face coordinates up to 1.75 (eu_math.h); columns reach |x0|, |x1| plus the
+    // x bias, rows the in-face value of the first and the last row of every face plus the y bias
+    for (int k = 0; k < nviews; k++) {
+      const eu_view &v = views[k];
+      const float a0 = (float)v.x0, a1 = (float)v.x1, b0 = (float)v.y0, b1 = (float)v.y1;
+      double m = std::max(std::fabs((double)a0), std::fabs((double)a1)) + 0.25 * std::fabs((double)a1 - a0) / t->width;
+      const float section_md = a1 - a0, refc_md = (float)((a1 - a0) / 2.0);
+      for (int face = 0; face < 6; face++)
+        for (int e = 0; e < 2; e++)
+          for (int b = 0; b < 2; b++) {
+            const int y = face * t->width + (e ? t->width - 1 : 0);
+            const float pp = eu::planar_row(t->height, b0, b1, b ? 0.25f : 0.0f, y) + (float)(3 - face) * section_md - refc_md;
+            m = std::max(m, std::fabs((double)pp));
+          }
+      if (!(m <= 1.75))
+        return fail(EU_ERR_UNSUPPORTED, "render_views: a biatan6 view whose in-face coordinates exceed 1.75 (the range tanf is reproduced over): use eu_hip_render");
+    }
+  }
+  return EU_OK;
+}
+
+// the tap table on the device, x and y premultiplied by the bias 4.0 (twine_t ctor, twining.h:106-121);
+// true in *changed when the buffer was rewritten (on `st`, from *keep: the caller synchronises)
+static int upload_view_taps(const eu_target *t, hipStream_t st, std::vector<float> *keep)
+{
+  if (t->ntaps <= 0) return EU_OK;
+  keep->assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
+  for (int k = 0; k < t->ntaps; k++) { (*keep)[3 * k] *= 4.0f; (*keep)[3 * k + 1] *= 4.0f; }
+  if (g.vtaps.p && keep->size() == g.vtaps_host.size() &&
+      !memcmp(keep->data(), g.vtaps_host.data(), keep->size() * sizeof(float)))
+    return EU_OK;
+  g.vtaps_host.clear();
+  HIPCHK(g.vtaps.reserve(keep->size()));
+  HIPCHK(hipMemcpyAsync(g.vtaps.p, keep->data(), keep->size() * sizeof(float), hipMemcpyHostToDevice, st));
+  g.vtaps_host = *keep;
+  return EU_OK;
+}
+
+// The library's view buffers are about to be rewritten on `st`: whoever may still read them has to be through -
+// the stream of the last call that used THEM (views_user), and, as for every entry point, the previous call's
+// stream and the library's own. Work on `st` itself is ordered by the stream. Afterwards `st` is their user.
+static int wait_for_view_buffers(hipStream_t st)
+{
+  if (g.views_user && g.views_user != st) HIPCHK(hipStreamSynchronize(g.views_user));
+  if (g.last_user && g.last_user != st && g.last_user != g.views_user) HIPCHK(hipStreamSynchronize(g.last_user));
+  if (g.stream != st && g.stream != g.views_user) HIPCHK(hipStreamSynchronize(g.stream));
+  g.views_user = st;
+  return EU_OK;
+}
+
+static void view_scalar_blocks(const eu_target *t, const eu_view *views, int nviews, const eu_source *src,
+                               std::vector<eu_view_dev> &sc)
+{
+  sc.resize((size_t)nviews);
+  const eu::mat3 r_fct = eu::make_r3(src->fct.roll, src->fct.pitch, src->fct.yaw, true);
+  for (int k = 0; k < nviews; k++) {
+    const eu_view &v = views[k];
+    const eu::mat3 basis = eu::rotate(eu::make_r3(v.roll, v.pitch, v.yaw, false), r_fct);
+    eu::view_scalars(t->width, t->height, v.x0, v.x1, v.y0, v.y1, basis, sc[(size_t)k]);
+  }
+}
+
+int eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
+                        size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream)
+{
+  int rc;
+  if (!trg || !views || !src || !out) return fail(EU_ERR_ARGUMENT, "render_views: null argument");
+  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
+  if ((rc = check_views_target(trg, src))) return rc;
+  for (int k = 0; k < nviews; k++)
+    if (!view_finite(views[k])) return fail(EU_ERR_ARGUMENT, "render_views: a view with a non-finite field");
+  const size_t row_bytes = (size_t)trg->width * trg->nchannels * sizeof(float);
+  if (out_row_stride_bytes % sizeof(float) || out_view_stride_bytes % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "render_views: strides must be multiples of 4 bytes");
+  if (out_row_stride_bytes < row_bytes) return fail(EU_ERR_ARGUMENT, "render_views: row stride smaller than a row");
+  if (out_view_stride_bytes / (size_t)trg->height < out_row_stride_bytes)
+    return fail(EU_ERR_ARGUMENT, "render_views: view stride smaller than `height` rows");
+  int form = 0, norm_mode = 0;
+  if ((rc = check_views_supported(trg, views, nviews, src, &form, &norm_mode))) return rc;
+  if (nviews == 0) return EU_OK;
+  if ((rc = ensure_init())) return rc;
+  if (!src->dev) return fail(EU_ERR_HANDLE, "render_views: the source has no container");
+  const eu_switches sw = eu_read_switches();
+  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
+  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
+
+  const int W = trg->width, H = trg->height;
+  const size_t col_floats = (size_t)6 * W, row_floats = (size_t)H * EU_ROW_FLOATS;
+  const size_t frame_bytes = (size_t)H * row_bytes;
+  int per_chunk = std::min(nviews, eu_views_per_chunk(W, H, sw.views_max_kb));
+  if (!out_on_device) per_chunk = (int)std::min<size_t>((size_t)per_chunk, std::max<size_t>(1, EU_VIEWS_STAGE_BYTES / frame_bytes));
+
+  std::vector<eu_view_dev> sc;
+  std::vector<float> taps;
+  view_scalar_blocks(trg, views, nviews, src, sc);
+  // whatever happens below, nothing of this call may still read the host vectors or write a host `out` when it returns
+  struct drain { hipStream_t a; bool on; ~drain() { if (on) (void)hipStreamSynchronize(a); } } drain_on_exit{ st, true };
+  if ((rc = wait_for_view_buffers(st))) return rc;
+  HIPCHK(g.vcol.reserve(col_floats * per_chunk));
+  HIPCHK(g.vrow.reserve(row_floats * per_chunk));
+  if (!out_on_device) HIPCHK(g.vstage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
+  // the one host synchronisation of the call: every view's scalars, and a new tap table, in flight from host vectors
+  HIPCHK(g.vscal.reserve((size_t)nviews));
+  HIPCHK(hipMemcpyAsync(g.vscal.p, sc.data(), sc.size() * sizeof(eu_view_dev), hipMemcpyHostToDevice, st));
+  if ((rc = upload_view_taps(trg, st, &taps))) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  drain_on_exit.on = !out_on_device;
+
+  eu_render_params p;
+  memset(&p, 0, sizeof p);
+  p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
+  p.form = form; p.norm_mode = norm_mode;
+  p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps; p.nch = src->nch; p.nch_out = trg->nchannels;
+  p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p;
+  p.src = src->sd;
+  p.direct = 1;
+  const int path = eu_select_view_path(p, sw);
+  for (int c0 = 0; c0 < nviews; c0 += per_chunk) {
+    const int nv = std::min(per_chunk, nviews - c0);
+    if (eu_launch_view_tables(g.vscal.p + c0, nv, trg->projection, W, H, p.twine, g.vcol.p, g.vrow.p, st))
+      return fail(EU_ERR_NO_DEVICE, "render_views: table kernel launch failed");
+    eu_view_strides vs;
+    vs.col = (long long)col_floats; vs.row = (long long)row_floats;
+    char *dst = (char *)out + (size_t)c0 * out_view_stride_bytes;
+    if (out_on_device) {
+      p.out = (float *)dst;
+      p.out_stride = (long long)(out_row_stride_bytes / sizeof(float));
+      vs.out = (long long)(out_view_stride_bytes / sizeof(float));
+    } else {
+      p.out = g.vstage.p;
+      p.out_stride = (long long)(row_bytes / sizeof(float));
+      vs.out = (long long)(frame_bytes / sizeof(float));
+    }
+    if (eu_launch_render_views(&p, &vs, nv, path, &sw, st)) return fail(EU_ERR_NO_DEVICE, "render_views: kernel launch failed");
+    if (!out_on_device)
+      for (int k = 0; k < nv; k++)
+        HIPCHK(hipMemcpy2DAsync(dst + (size_t)k * out_view_stride_bytes, out_row_stride_bytes,
+                                (const char *)g.vstage.p + (size_t)k * frame_bytes, row_bytes, row_bytes, (size_t)H,
+                                hipMemcpyDeviceToHost, st));
+  }
+  if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
+  return EU_OK;
+}
+
+// For tests: the tables the table kernel writes for one view, and eu::build_stepper_tables for the same view
+int eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src, float *col_dev_built,
+                       float *row_dev_built, float *col_host_built, float *row_host_built)
+{
+  int rc;
+  if (!trg || !view || !src || !col_dev_built || !row_dev_built || !col_host_built || !row_host_built)
+    return fail(EU_ERR_ARGUMENT, "view_tables: null argument");
+  if ((rc = check_views_target(trg, src))) return rc;
+  if (!view_finite(*view)) return fail(EU_ERR_ARGUMENT, "view_tables: a view with a non-finite field");
+  int form = 0, norm_mode = 0;
+  if ((rc = check_views_supported(trg, view, 1, src, &form, &norm_mode))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (!src->dev) return fail(EU_ERR_HANDLE, "view_tables: the source has no container");
+  const int W = trg->width, H = trg->height;
+  const bool twine = trg->ntaps > 0;
+  const size_t col_floats = (size_t)6 * W, row_floats = (size_t)H * EU_ROW_FLOATS;
+  {
+    eu_target t = *trg;
+    t.yaw = view->yaw; t.pitch = view->pitch; t.roll = view->roll;
+    t.x0 = view->x0; t.x1 = view->x1; t.y0 = view->y0; t.y1 = view->y1;
+    const eu::mat3 basis = eu::rotate(eu::make_r3(t.roll, t.pitch, t.yaw, false),
+                                      eu::make_r3(src->fct.roll, src->fct.pitch, src->fct.yaw, true));
+    eu::stepper_tables tb;
+    if (!eu::build_stepper_tables(t, basis, twine, twine, tb) || tb.form != form || tb.norm_mode != norm_mode)
+      return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
+    memcpy(col_host_built, tb.col.data(), col_floats * sizeof(float));
+    memcpy(row_host_built, tb.row.data(), row_floats * sizeof(float));
+  }
+  std::vector<eu_view_dev> sc;
+  view_scalar_blocks(trg, view, 1, src, sc);
+  if ((rc = wait_for_view_buffers(g.stream))) return rc;
+  struct note_stream { ~note_stream() { g.last_user = nullptr; } } note_on_exit;
+  HIPCHK(g.vcol.reserve(col_floats));
+  HIPCHK(g.vrow.reserve(row_floats));
+  HIPCHK(g.vscal.reserve(1));
+  HIPCHK(hipMemcpyAsync(g.vscal.p, sc.data(), sizeof(eu_view_dev), hipMemcpyHostToDevice, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  if (eu_launch_view_tables(g.vscal.p, 1, trg->projection, W, H, twine, g.vcol.p, g.vrow.p, g.stream))
+    return fail(EU_ERR_NO_DEVICE, "view_tables: table kernel launch failed");
+  HIPCHK(hipMemcpyAsync(col_dev_built, g.vcol.p, col_floats * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipMemcpyAsync(row_dev_built, g.vrow.p, row_floats * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
   return EU_OK;
 }
 

@@ -137,4 +137,19 @@ struct eu_rays_params {
   eu_src_dev src;
 };
 
+// eu_hip_render_views (eu_render_views.hip): what eu::build_stepper_tables computes in front of its loops, one
+// block per view (eu::view_scalars). The table kernel makes the view's column and row tables from it.
+struct eu_view_dev {
+  float xx[3], yy[3], zz[3];   // rotate(make_r3(camera), make_r3(facet, inverse)), narrowed
+  float a0, a1, b0, b1;        // the view's extent
+  float fx0, fx1, fy0, fy1;    // (float)(a / (2.0 * W)), (float)(b / (2.0 * H)): double divisions
+  float delta;                 // EU_LANES * (a1 - a0) / W: what a lane adds per step inside its segment
+  float bias_x[2], bias_y[2];  // bias * (a1 - a0) / W and bias * (b1 - b0) / H for the biases 0 and 0.25
+  float section_md, refc_md;   // cube targets: a1 - a0 and half of it
+  float pad[7];                // 128 bytes
+};
+
+// the view on blockIdx.y: floats from one view's column table, row table and frame to the next one's
+struct eu_view_strides { long long col, row, out; };
+
 #endif

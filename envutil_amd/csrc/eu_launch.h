@@ -61,6 +61,12 @@ int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const fl
                       unsigned long long plan_gen, void *stream, int *launches);
 // path: an eu_ray_path, as eu_select_ray_path() chose it
 int eu_launch_render_rays(const eu_rays_params *p, int path, void *stream);
+// eu_render_views.hip. The table kernel: col [nviews][6][width] and row [nviews][height][EU_ROW_FLOATS] from the
+// views' scalar blocks. The render kernels: p describes view 0 of the launch, path is an eu_view_path
+int eu_launch_view_tables(const eu_view_dev *views, int nviews, int prj, int width, int height, int twine, float *col,
+                          float *row, void *stream);
+int eu_launch_render_views(const eu_render_params *p, const eu_view_strides *vs, int nviews, int path,
+                           const eu_switches *sw, void *stream);
 int eu_launch_render_multi(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);

@@ -9,6 +9,7 @@
 //   staged           eu_render4.hip   LDS-staged tiles plus the direct-gather kernel behind them
 //                                     (eu_staged_covers), two launches
 // A call with the caller's own rays (eu_hip_render_rays) has two forms of its own: eu_select_ray_path().
+// So has a sequence of views (eu_hip_render_views): eu_select_view_path().
 #ifndef EU_SELECT_H
 #define EU_SELECT_H
 #include <algorithm>
@@ -35,10 +36,14 @@ struct eu_switches {
   int boxtab;          // EU_HIP_BOXTAB=0: the persistent staged kernel's second loop reduces its tile boxes per frame (0); else 1:
                        // it reads them from a table built with the plans
   int boxtab_max_kb;   // EU_HIP_BOXTAB_MAX_KB: the largest box table built, KiB (EU_BOXTAB_MAX_KB); a job beyond it gets none
+  int views_max_kb;    // EU_HIP_VIEWS_MAX_KB: the most stepper tables eu_hip_render_views keeps at a time, KiB
+                       // (EU_VIEWS_MAX_KB); a longer sequence goes through in chunks of views
 };
 
 // 64 bytes per second-loop tile: 64 MiB hold the polar faces of a 6 x 8192 cubemap, four times the headline's 16 MiB
 #define EU_BOXTAB_MAX_KB 65536
+// 120 KiB per 1024 x 1024 view: 64 MiB hold the tables of 546 of them
+#define EU_VIEWS_MAX_KB 65536
 
 inline eu_switches eu_read_switches()
 {
@@ -62,6 +67,8 @@ inline eu_switches eu_read_switches()
   s.boxtab = first("EU_HIP_BOXTAB") != '0';
   const char *bm = getenv("EU_HIP_BOXTAB_MAX_KB");
   s.boxtab_max_kb = bm && bm[0] ? std::max(0, std::min(atoi(bm), 16 * 1024 * 1024)) : EU_BOXTAB_MAX_KB;
+  const char *vm = getenv("EU_HIP_VIEWS_MAX_KB");
+  s.views_max_kb = vm && vm[0] ? std::max(0, std::min(atoi(vm), 16 * 1024 * 1024)) : EU_VIEWS_MAX_KB;
   return s;
 }
 
@@ -171,6 +178,29 @@ inline eu_ray_path eu_select_ray_path(const eu_rays_params &p, const eu_switches
 {
   if (p.src.mask_paint || sw.force_general) return EU_RAYS_GENERAL;
   return eu_packed_covers_source(p.src, p.nch, p.nch_out) ? EU_RAYS_PACKED : EU_RAYS_GENERAL;
+}
+
+// ---- a sequence of views (eu_hip_render_views, eu_render_views.hip) --------------------------------
+// The stepper tables of every view are made on the device, so nothing here may depend on a plan: no runs, no
+// staged kernels, row strips only.
+//   general  eu_views_kernel   one pixel per lane, as eu_render_kernel: every mount and degree, channel adaption,
+//                              twining, --mask_for
+//   packed   eu_views2_kernel  two per lane, as eu_render2_kernel: what eu_packed_covers() admits
+enum eu_view_path { EU_VIEWS_GENERAL, EU_VIEWS_PACKED };
+
+inline eu_view_path eu_select_view_path(const eu_render_params &p, const eu_switches &sw)
+{
+  if (p.src.mask_paint || sw.force_general) return EU_VIEWS_GENERAL;
+  return eu_packed_covers(p) ? EU_VIEWS_PACKED : EU_VIEWS_GENERAL;
+}
+
+// views of one chunk: as many as the table bound holds (at least one), and no more than a grid's y extent
+#define EU_VIEWS_MAX_GRID_Y 65535
+inline int eu_views_per_chunk(int width, int height, int max_kb)
+{
+  const unsigned long long per = ((unsigned long long)6 * width + (unsigned long long)EU_ROW_FLOATS * height) * sizeof(float);
+  const unsigned long long n = per ? (unsigned long long)max_kb * 1024ull / per : EU_VIEWS_MAX_GRID_Y;
+  return (int)std::max<unsigned long long>(1, std::min<unsigned long long>(n, EU_VIEWS_MAX_GRID_Y));
 }
 
 // ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------

@@ -495,6 +495,41 @@ inline bool build_stepper_tables(const eu_target &t, const mat3 &basis, bool nor
   return true;
 }
 
+// eu_hip_render_views: form and normalisation as build_stepper_tables decides them, without the tables
+inline bool stepper_form(int prj, bool normalize, int &form, int &norm_mode)
+{
+  norm_mode = EU_NORM_NONE;
+  switch (prj) {
+    case EU_SPHERICAL: form = EU_FORM_BCA; return true;
+    case EU_CYLINDRICAL: form = EU_FORM_BCA; if (normalize) norm_mode = EU_NORM_CYL; return true;
+    case EU_RECTILINEAR: case EU_CUBEMAP: case EU_BIATAN6: form = EU_FORM_BA; if (normalize) norm_mode = EU_NORM_DIV; return true;
+    case EU_FISHEYE: form = EU_FORM_FISH; return true;
+    case EU_STEREOGRAPHIC: form = EU_FORM_STER; return true;
+  }
+  return false;
+}
+
+// ... and the scalars build_stepper_tables, planar_columns and planar_row compute in front of their loops, for a
+// W x H view with extent (x0, x1, y0, y1): the same expressions, so the same bits. The table kernel
+// (eu_render_views.hip) does the loops.
+inline void view_scalars(int W, int H, double x0, double x1, double y0, double y1, const mat3 &basis, eu_view_dev &d)
+{
+  memset(&d, 0, sizeof d);
+  const float a0 = (float)x0, a1 = (float)x1, b0 = (float)y0, b1 = (float)y1;
+  for (int i = 0; i < 3; i++) { d.xx[i] = (float)basis.m[i]; d.yy[i] = (float)basis.m[3 + i]; d.zz[i] = (float)basis.m[6 + i]; }
+  d.a0 = a0; d.a1 = a1; d.b0 = b0; d.b1 = b1;
+  d.fx1 = (float)(a1 / (2.0 * W)); d.fx0 = (float)(a0 / (2.0 * W));
+  d.fy1 = (float)(b1 / (2.0 * H)); d.fy0 = (float)(b0 / (2.0 * H));
+  d.delta = (float)EU_LANES * (a1 - a0) / (float)W;
+  const float bias[2] = { 0.0f, 0.25f };
+  for (int v = 0; v < 2; v++) {
+    d.bias_x[v] = bias[v] * (a1 - a0) / (float)W;
+    d.bias_y[v] = bias[v] * (b1 - b0) / (float)H;
+  }
+  d.section_md = a1 - a0;
+  d.refc_md = (float)((a1 - a0) / 2.0);
+}
+
 // generic_r3(ft, fs) for ft = the job's target (no translation of its own), envutil_payload.cc:
 // 1757-1810: the facet's tf3d_t. Float matrix products as rotate(r3_t<float>, r3_t<float>)
 // (geometry.h:80-97) forms them. false: target projections whose planar -> ray functor

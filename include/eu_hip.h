@@ -358,6 +358,38 @@ int  eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out,
 int  eu_hip_render_rays_timed(const eu_rays *r, eu_source *src, float *out_dev,
                               size_t out_row_stride_bytes, int iters, float *mean_ms);
 
+/* Many views of one resident source in one call: the jobs of a tethered viewer or a pipe-mode loop, which differ
+ * only in yaw, pitch, roll and hfov (envutil_main.cc:1755-1869), a camera path, a batch of crops from one panorama.
+ * `trg` supplies what all views share - projection, width, height, nchannels, the tap table; its own orientation
+ * and extent are ignored. View k is written at out + k * out_view_stride_bytes, rows out_row_stride_bytes apart,
+ * and is bit for bit the frame eu_hip_render gives for `trg` with that view's orientation and extent. The stepper
+ * tables of every view are made on the device from a few scalars per view (eu_render_views.hip), so the host does
+ * per view neither libm work nor an upload nor a synchronisation; tables of at most EU_HIP_VIEWS_MAX_KB KiB are
+ * kept at a time (a longer sequence, or one of more than 65535 views, goes through in chunks of views).
+ *
+ * One source, float output, whole frames. EU_ERR_ARGUMENT, before a device is looked for: null pointers,
+ * nviews < 0, a non-finite field of a view, stage != 0, a crop window, row bands, single != NULL, EU_OUT_SRGBA8,
+ * row_begin / row_end other than the whole frame, strides that are no multiples of 4, a row stride smaller than a
+ * row, a view stride smaller than `height` rows. EU_ERR_UNSUPPORTED: a facet with PTO translation, a target
+ * projection without a stepper, a biatan6 target whose in-face coordinates leave [-1.75, 1.75]. nviews == 0 is
+ * EU_OK and writes nothing.
+ *
+ * With `out` on the device the call is asynchronous on `stream` (NULL: the library's) until eu_hip_sync();
+ * otherwise the views are staged through a bounded device buffer and the call returns when `out` is complete.
+ * The call uses buffers of its own: eu_hip_render, its plan caches, eu_hip_launch_count() and the staged kernels'
+ * work list are not touched. */
+typedef struct eu_view {
+  double yaw, pitch, roll;      /* camera orientation, radians (as eu_target)            */
+  double x0, x1, y0, y1;        /* extent of this view (get_extent of its hfov)          */
+} eu_view;
+int  eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
+                         size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream);
+/* For tests. All four are host buffers of 6 * width and height * 24 floats (the column table [6][width], the row
+ * table [height][24]): the first two receive what the table kernel wrote for this view, the last two what the host
+ * function behind eu_hip_render builds for it. */
+int  eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src, float *col_dev_built,
+                        float *row_dev_built, float *col_host_built, float *row_host_built);
+
 /* device memory helpers for hosts without a HIP binding of their own */
 int  eu_hip_malloc(void **p, size_t bytes);
 int  eu_hip_free(void *p);
