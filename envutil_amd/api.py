@@ -154,6 +154,7 @@ def lib():
     L.eu_hip_render_rays.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_rays_timed.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_views.argtypes = [vp, vp, i32, vp, vp, C.c_size_t, C.c_size_t, i32, vp]
+    L.eu_hip_render_views_multi.argtypes = [vp, vp, i32, vp, i32, vp, C.c_size_t, C.c_size_t, i32, vp]
     L.eu_hip_view_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.eu_hip_layout_segments.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eu_hip_band_rows.argtypes = [i32, i32, i32, i32]
@@ -741,16 +742,21 @@ def _frames(a, what):
 
 
 def render_views(args, views, source, nchannels=None, out=None, stream=None):
-    """eu_hip_render_views: many views of one resident source in one call. `args` gives what the views share
-    (projection, size, spline degree, twining); `views` is a sequence of (yaw, pitch, roll) or (yaw, pitch, roll,
-    hfov) in degrees, args.hfov applying where a view gives none. Returns (N, H, W, C) float32, view k being
-    render() of args with that orientation and hfov, bit for bit: a new numpy array, or `out` (numpy, or a float32
+    """eu_hip_render_views / eu_hip_render_views_multi: many views of one resident source, or of a multi-facet job,
+    in one call. `source` is a Source or a list or tuple of them (the facets, composed per pixel as render()
+    composes them: args.synopsis); a list of one is that source. `args` gives what the views share (projection,
+    size, spline degree, twining); `views` is a sequence of (yaw, pitch, roll) or (yaw, pitch, roll, hfov) in
+    degrees, args.hfov applying where a view gives none. Returns (N, H, W, C) float32, view k being render() of args
+    with that orientation and hfov, bit for bit: a new numpy array, or `out` (numpy, or a float32
     torch tensor in device memory - of the device the library runs on, which on a host with several is the caller's
-    to see to; rows and views may be padded). With `out` on the device the call is
-    asynchronous on `stream` (a hipStream_t address; None: the library's stream) until sync()."""
+    to see to; rows and views may be padded). C defaults to the first facet's channel count. With `out` on the
+    device the call is asynchronous on `stream` (a hipStream_t address; None: the library's stream) until sync()."""
     _views_args(args, "render_views")
     views = list(views)
-    nch = nchannels or source.fct.nchannels
+    facets = list(source) if isinstance(source, (list, tuple)) else [source]
+    if not facets:
+        raise EuError("render_views: no source")
+    nch = nchannels or facets[0].fct.nchannels
     shape = (len(views), args.height, args.width, nch)
     if out is None:
         out = np.zeros(shape, np.float32)
@@ -759,8 +765,14 @@ def render_views(args, views, source, nchannels=None, out=None, stream=None):
     optr, row, view, on_device = _frames(out, "out")
     t = args.target(nch)
     arr = _views_struct(args, views)
-    _check(lib().eu_hip_render_views(C.byref(t), arr, len(views), source.handle, C.c_void_p(optr), row, view,
-                                     int(on_device), C.c_void_p(stream) if stream else None))
+    st = C.c_void_p(stream) if stream else None
+    if len(facets) == 1:
+        _check(lib().eu_hip_render_views(C.byref(t), arr, len(views), facets[0].handle, C.c_void_p(optr), row, view,
+                                         int(on_device), st))
+    else:
+        handles = (C.c_void_p * len(facets))(*[s.handle for s in facets])
+        _check(lib().eu_hip_render_views_multi(C.byref(t), arr, len(views), handles, len(facets), C.c_void_p(optr),
+                                               row, view, int(on_device), st))
     return out
 
 

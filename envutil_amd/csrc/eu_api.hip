@@ -84,6 +84,7 @@ struct context {
   // of views), its tap table and the staging of a host output - all its own, like eu_hip_render_rays' buffers
   eu_dev_buf<eu_view_dev> vscal;
   eu_dev_buf<float> vcol, vrow, vtaps, vstage;
+  eu_dev_buf<eu_src_dev> vsrc;                    // eu_hip_render_views_multi: the facets' evaluator parameters
   std::vector<float> vtaps_host;                  // what vtaps holds
   hipStream_t views_user = nullptr;               // the stream the last call worked on with these buffers (last_user is
                                                   // one slot for all entry points: a render in between overwrites it)
@@ -1691,6 +1692,29 @@ static int check_views_target(const eu_target *t, const eu_source *src)
   return EU_OK;
 }
 
+// eu_tanf has libm's bits for in-face coordinates up to 1.75 (eu_math.h); columns reach |x0|, |x1| plus the
+// x bias, rows the in-face value of the first and the last row of every face plus the y bias
+static int check_views_biatan6(const eu_target *t, const eu_view *views, int nviews)
+{
+  if (t->projection != EU_BIATAN6) return EU_OK;
+  for (int k = 0; k < nviews; k++) {
+    const eu_view &v = views[k];
+    const float a0 = (float)v.x0, a1 = (float)v.x1, b0 = (float)v.y0, b1 = (float)v.y1;
+    double m = std::max(std::fabs((double)a0), std::fabs((double)a1)) + 0.25 * std::fabs((double)a1 - a0) / t->width;
+    const float section_md = a1 - a0, refc_md = (float)((a1 - a0) / 2.0);
+    for (int face = 0; face < 6; face++)
+      for (int e = 0; e < 2; e++)
+        for (int b = 0; b < 2; b++) {
+          const int y = face * t->width + (e ? t->width - 1 : 0);
+          const float pp = eu::planar_row(t->height, b0, b1, b ? 0.25f : 0.0f, y) + (float)(3 - face) * section_md - refc_md;
+          m = std::max(m, std::fabs((double)pp));
+        }
+    if (!(m <= 1.75))
+      return fail(EU_ERR_UNSUPPORTED, "render_views: a biatan6 view whose in-face coordinates exceed 1.75 (the range tanf is reproduced over): use eu_hip_render");
+  }
+  return EU_OK;
+}
+
 // what this path does not render: EU_ERR_UNSUPPORTED
 static int check_views_supported(const eu_target *t, const eu_view *views, int nviews, const eu_source *src, int *form,
                                  int *norm_mode)
@@ -1700,26 +1724,7 @@ static int check_views_supported(const eu_target *t, const eu_view *views, int n
   const bool twine = t->ntaps > 0;
   if (!eu::stepper_form(t->projection, twine, *form, *norm_mode))
     return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
-  if (t->projection == EU_BIATAN6) {
-    // eu_tanf has libm's bits for in-face coordinates up to 1.75 (eu_math.h); columns reach |x0|, |x1| plus the
-    // x bias, rows the in-face value of the first and the last row of every face plus the y bias
-    for (int k = 0; k < nviews; k++) {
-      const eu_view &v = views[k];
-      const float a0 = (float)v.x0, a1 = (float)v.x1, b0 = (float)v.y0, b1 = (float)v.y1;
-      double m = std::max(std::fabs((double)a0), std::fabs((double)a1)) + 0.25 * std::fabs((double)a1 - a0) / t->width;
-      const float section_md = a1 - a0, refc_md = (float)((a1 - a0) / 2.0);
-      for (int face = 0; face < 6; face++)
-        for (int e = 0; e < 2; e++)
-          for (int b = 0; b < 2; b++) {
-            const int y = face * t->width + (e ? t->width - 1 : 0);
-            const float pp = eu::planar_row(t->height, b0, b1, b ? 0.25f : 0.0f, y) + (float)(3 - face) * section_md - refc_md;
-            m = std::max(m, std::fabs((double)pp));
-          }
-      if (!(m <= 1.75))
-        return fail(EU_ERR_UNSUPPORTED, "render_views: a biatan6 view whose in-face coordinates exceed 1.75 (the range tanf is reproduced over): use eu_hip_render");
-    }
-  }
-  return EU_OK;
+  return check_views_biatan6(t, views, nviews);
 }
 
 // the tap table on the device, x and y premultiplied by the bias 4.0 (twine_t ctor, twining.h:106-121);
@@ -1835,6 +1840,143 @@ int eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, 
       vs.out = (long long)(frame_bytes / sizeof(float));
     }
     if (eu_launch_render_views(&p, &vs, nv, path, &sw, st)) return fail(EU_ERR_NO_DEVICE, "render_views: kernel launch failed");
+    if (!out_on_device)
+      for (int k = 0; k < nv; k++)
+        HIPCHK(hipMemcpy2DAsync(dst + (size_t)k * out_view_stride_bytes, out_row_stride_bytes,
+                                (const char *)g.vstage.p + (size_t)k * frame_bytes, row_bytes, row_bytes, (size_t)H,
+                                hipMemcpyDeviceToHost, st));
+  }
+  if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
+  return EU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// many views of a multi-facet job in one call (include/eu_hip.h, eu_render_views_multi.hip)
+// ---------------------------------------------------------------------------------------------------------
+// What build_multi does per camera on the host - one build_stepper_tables per facet, a pageable upload of the row
+// tables, two synchronisations - is one scalar block per (view, facet) here: the table kernel makes the tables of
+// a chunk of views in one launch, the render kernel has the view on blockIdx.y. The buffers are those of
+// eu_hip_render_views plus the facets' parameter blocks (g.vsrc); none of build_multi's (g.mcol, g.mrow, g.msrc,
+// g.mtaps, g.mplan_key) is touched. EU_HIP_REJ is not applied: the early-miss tables change no bit and were
+// measured slower (build_multi).
+int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
+                              float *out, size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device,
+                              void *stream)
+{
+  int rc;
+  if (!trg || !views || !srcs || !out) return fail(EU_ERR_ARGUMENT, "render_views_multi: null argument");
+  if (nsrc < 1) return fail(EU_ERR_ARGUMENT, "render_views_multi: no source");
+  if (nsrc > EU_VIEWS_MAX_GRID_Y) return fail(EU_ERR_ARGUMENT, "render_views_multi: more than 65535 facets");
+  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
+  for (int f = 0; f < nsrc; f++)
+    if (!srcs[f]) return fail(EU_ERR_HANDLE, "render_views_multi: null source");
+  if (nsrc == 1)
+    return eu_hip_render_views(trg, views, nviews, srcs[0], out, out_row_stride_bytes, out_view_stride_bytes,
+                               out_on_device, stream);
+  // the target, and the --mask_for channel rule of every facet
+  for (int f = 0; f < nsrc; f++)
+    if ((rc = check_views_target(trg, srcs[f]))) return rc;
+  for (int f = 1; f < nsrc; f++)
+    if (srcs[f]->degree != srcs[0]->degree)
+      return fail(EU_ERR_ARGUMENT, "render_views_multi: facets must share the spline degree");
+  for (int k = 0; k < nviews; k++)
+    if (!view_finite(views[k])) return fail(EU_ERR_ARGUMENT, "render_views: a view with a non-finite field");
+  const size_t row_bytes = (size_t)trg->width * trg->nchannels * sizeof(float);
+  if (out_row_stride_bytes % sizeof(float) || out_view_stride_bytes % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "render_views: strides must be multiples of 4 bytes");
+  if (out_row_stride_bytes < row_bytes) return fail(EU_ERR_ARGUMENT, "render_views: row stride smaller than a row");
+  if (out_view_stride_bytes / (size_t)trg->height < out_row_stride_bytes)
+    return fail(EU_ERR_ARGUMENT, "render_views: view stride smaller than `height` rows");
+  for (int f = 0; f < nsrc; f++)
+    if (eu::has_translation(srcs[f]->fct))
+      return fail(EU_ERR_UNSUPPORTED, "render_views_multi: a facet with PTO translation is stepped by the generic stepper: use eu_hip_render");
+  // a multi-facet job always normalises (build_multi)
+  int form = 0, norm_mode = 0;
+  if (!eu::stepper_form(trg->projection, true, form, norm_mode))
+    return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
+  if ((rc = check_views_biatan6(trg, views, nviews))) return rc;
+  if (nviews == 0) return EU_OK;
+  if ((rc = ensure_init())) return rc;
+  for (int f = 0; f < nsrc; f++)
+    if (!srcs[f]->dev) return fail(EU_ERR_HANDLE, "render_views_multi: a source has no container");
+  const eu_switches sw = eu_read_switches();
+  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
+  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
+
+  const int W = trg->width, H = trg->height;
+  const bool twine = trg->ntaps > 0;
+  // one table block per (view, facet): the columns of a view are those of its first block
+  const size_t col_floats = (size_t)6 * W * nsrc, row_floats = (size_t)H * EU_ROW_FLOATS * nsrc;
+  const size_t frame_bytes = (size_t)H * row_bytes;
+  int per_chunk = std::min(nviews, eu_views_per_chunk(W, H, sw.views_max_kb, nsrc));
+  if (!out_on_device) per_chunk = (int)std::min<size_t>((size_t)per_chunk, std::max<size_t>(1, EU_VIEWS_STAGE_BYTES / frame_bytes));
+
+  // [view][facet]: basis = rotate(r_cam(view), r_fct(facet)), as build_multi forms it
+  std::vector<eu_view_dev> sc((size_t)nviews * nsrc);
+  {
+    std::vector<eu::mat3> r_fct((size_t)nsrc);
+    for (int f = 0; f < nsrc; f++) r_fct[f] = eu::make_r3(srcs[f]->fct.roll, srcs[f]->fct.pitch, srcs[f]->fct.yaw, true);
+    for (int k = 0; k < nviews; k++) {
+      const eu_view &v = views[k];
+      const eu::mat3 r_cam = eu::make_r3(v.roll, v.pitch, v.yaw, false);
+      for (int f = 0; f < nsrc; f++)
+        eu::view_scalars(W, H, v.x0, v.x1, v.y0, v.y1, eu::rotate(r_cam, r_fct[f]), sc[(size_t)k * nsrc + f]);
+    }
+  }
+  // the facets' evaluator parameters (they can change between calls: always refreshed)
+  std::vector<eu_src_dev> sd((size_t)nsrc);
+  for (int f = 0; f < nsrc; f++) sd[f] = srcs[f]->sd;
+  std::vector<float> taps;
+  // whatever happens below, nothing of this call may still read the host vectors or write a host `out` when it returns
+  struct drain { hipStream_t a; bool on; ~drain() { if (on) (void)hipStreamSynchronize(a); } } drain_on_exit{ st, true };
+  if ((rc = wait_for_view_buffers(st))) return rc;
+  HIPCHK(g.vcol.reserve(col_floats * per_chunk));
+  HIPCHK(g.vrow.reserve(row_floats * per_chunk));
+  if (!out_on_device) HIPCHK(g.vstage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
+  // the one host synchronisation of the call: the scalar blocks, the facets, and a new tap table, in flight from host vectors
+  HIPCHK(g.vscal.reserve(sc.size()));
+  HIPCHK(g.vsrc.reserve(sd.size()));
+  HIPCHK(hipMemcpyAsync(g.vscal.p, sc.data(), sc.size() * sizeof(eu_view_dev), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(g.vsrc.p, sd.data(), sd.size() * sizeof(eu_src_dev), hipMemcpyHostToDevice, st));
+  if ((rc = upload_view_taps(trg, st, &taps))) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  drain_on_exit.on = !out_on_device;
+
+  eu_multi_params p;
+  memset(&p, 0, sizeof p);
+  p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
+  p.form = form; p.norm_mode = norm_mode; p.twine = twine; p.ntaps = trg->ntaps;
+  p.nch = trg->nchannels; p.nfct = nsrc; p.plus = (trg->nchannels == 2 || trg->nchannels == 4);
+  p.hdr = trg->synopsis == EU_SYN_HDR_MERGE;
+  {
+    // _hdr_merge_syn ctor (envutil_payload.cc:1346-1376): the first strict minimum / maximum of brighten
+    float lowest = 100000.0f, highest = -1.0f;
+    p.hdr_low = p.hdr_high = -1;
+    for (int f = 0; f < nsrc; f++) {
+      const float b = srcs[f]->sd.brighten;
+      if (b < lowest) { lowest = b; p.hdr_low = f; }
+      if (b > highest) { highest = b; p.hdr_high = f; }
+    }
+  }
+  p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p; p.srcs = g.vsrc.p;
+  eu_view_strides vs;
+  vs.col = (long long)col_floats; vs.row = (long long)row_floats;
+  for (int c0 = 0; c0 < nviews; c0 += per_chunk) {
+    const int nv = std::min(per_chunk, nviews - c0);
+    if (eu_launch_view_tables(g.vscal.p + (size_t)c0 * nsrc, nv * nsrc, trg->projection, W, H, twine, g.vcol.p, g.vrow.p, st))
+      return fail(EU_ERR_NO_DEVICE, "render_views_multi: table kernel launch failed");
+    char *dst = (char *)out + (size_t)c0 * out_view_stride_bytes;
+    if (out_on_device) {
+      p.out = (float *)dst;
+      p.out_stride = (long long)(out_row_stride_bytes / sizeof(float));
+      vs.out = (long long)(out_view_stride_bytes / sizeof(float));
+    } else {
+      p.out = g.vstage.p;
+      p.out_stride = (long long)(row_bytes / sizeof(float));
+      vs.out = (long long)(frame_bytes / sizeof(float));
+    }
+    if (eu_launch_render_views_multi(&p, &vs, nv, srcs[0]->degree, st))
+      return fail(EU_ERR_NO_DEVICE, "render_views_multi: kernel launch failed");
     if (!out_on_device)
       for (int k = 0; k < nv; k++)
         HIPCHK(hipMemcpy2DAsync(dst + (size_t)k * out_view_stride_bytes, out_row_stride_bytes,

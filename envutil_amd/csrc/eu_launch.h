@@ -72,6 +72,13 @@ int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stre
 int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch3(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch4(const eu_multi_params *p, int degree, void *stream);
+// eu_render_views_multi.hip: p describes view 0 of the launch (col [6][width], row [nfct][height][EU_ROW_FLOATS],
+// out), vs what lies between one view's tables and frame and the next one's
+int eu_launch_render_views_multi(const eu_multi_params *p, const eu_view_strides *vs, int nviews, int degree, void *stream);
+int eu_launch_render_views_multi_nch1(const eu_multi_params *p, const eu_view_strides *vs, int nviews, int degree, void *stream);
+int eu_launch_render_views_multi_nch2(const eu_multi_params *p, const eu_view_strides *vs, int nviews, int degree, void *stream);
+int eu_launch_render_views_multi_nch3(const eu_multi_params *p, const eu_view_strides *vs, int nviews, int degree, void *stream);
+int eu_launch_render_views_multi_nch4(const eu_multi_params *p, const eu_view_strides *vs, int nviews, int degree, void *stream);
 int eu_launch_to_screen(const float *in, long long in_stride, unsigned *out, long long out_stride, int w, int rows,
                         int nch, const float *lut, void *stream);
 // iir_stream: eu_switches::iir_stream

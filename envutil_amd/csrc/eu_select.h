@@ -195,12 +195,15 @@ inline eu_view_path eu_select_view_path(const eu_render_params &p, const eu_swit
 }
 
 // views of one chunk: as many as the table bound holds (at least one), and no more than a grid's y extent
+// A multi-facet job (eu_hip_render_views_multi) has one table block per (view, facet), and the table kernel has the
+// block on blockIdx.y: views * nfct stays within the grid's y extent (nfct itself does: the entry point sees to it)
 #define EU_VIEWS_MAX_GRID_Y 65535
-inline int eu_views_per_chunk(int width, int height, int max_kb)
+inline int eu_views_per_chunk(int width, int height, int max_kb, int nfct = 1)
 {
-  const unsigned long long per = ((unsigned long long)6 * width + (unsigned long long)EU_ROW_FLOATS * height) * sizeof(float);
+  const unsigned long long nf = (unsigned long long)std::max(nfct, 1);
+  const unsigned long long per = nf * ((unsigned long long)6 * width + (unsigned long long)EU_ROW_FLOATS * height) * sizeof(float);
   const unsigned long long n = per ? (unsigned long long)max_kb * 1024ull / per : EU_VIEWS_MAX_GRID_Y;
-  return (int)std::max<unsigned long long>(1, std::min<unsigned long long>(n, EU_VIEWS_MAX_GRID_Y));
+  return (int)std::max<unsigned long long>(1, std::min<unsigned long long>(n, EU_VIEWS_MAX_GRID_Y / nf));
 }
 
 // ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------

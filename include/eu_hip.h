@@ -384,6 +384,23 @@ typedef struct eu_view {
 } eu_view;
 int  eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
                          size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream);
+/* The same for a multi-facet job: view k is bit for bit the frame eu_hip_render(trg', srcs, nsrc, ...) gives, trg'
+ * being `trg` with view k's orientation and extent; trg->synopsis selects panorama (voronoi_syn / voronoi_syn_plus)
+ * or hdr_merge as there. Layout, strides, `out_on_device` and `stream` are those of eu_hip_render_views. nsrc == 1
+ * forwards to eu_hip_render_views. Per (view, facet) the host computes one block of scalars - the basis
+ * rotate(r_cam(view), r_fct(facet)) - and nothing else; the facets' parameters and the tap table go up once per
+ * call. A view's tables take nsrc * (6 * width + 24 * height) * 4 bytes of the EU_HIP_VIEWS_MAX_KB bound.
+ *
+ * EU_ERR_ARGUMENT, before a device is looked for: everything eu_hip_render_views refuses (the --mask_for channel
+ * rule per facet), nsrc < 1 or > 65535, srcs == NULL, facets that do not share the spline degree. A null entry of
+ * srcs is EU_ERR_HANDLE. EU_ERR_UNSUPPORTED: any facet with PTO translation, a target projection without a
+ * stepper, the biatan6 range of a view. nviews == 0 is EU_OK and writes nothing.
+ *
+ * The call uses the buffers of eu_hip_render_views and one more of its own: eu_hip_render's multi-facet tables and
+ * plan key, eu_hip_launch_count() and the work list are not touched. EU_HIP_REJ has no effect here. */
+int  eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
+                               float *out, size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device,
+                               void *stream);
 /* For tests. All four are host buffers of 6 * width and height * 24 floats (the column table [6][width], the row
  * table [height][24]): the first two receive what the table kernel wrote for this view, the last two what the host
  * function behind eu_hip_render builds for it. */
