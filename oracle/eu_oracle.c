@@ -1151,6 +1151,8 @@ int euo_inverse_lcp(double a, double b, double c, double r_max, int sz, const fl
 
 /* ------------------------------------------------------------------------ */
 /* steppers (stepper.h) - one instance per row segment                       */
+/* PINNED: bit for bit the reference's own stepper.h, compiled in place     */
+/* (oracle/ref_zimt.cc, tests/test_stepper_pinned.py); the basis is an input */
 /* ------------------------------------------------------------------------ */
 
 typedef struct {
@@ -2185,6 +2187,8 @@ void euo_source_coordinates(const euo_source *src, const float *rays, long n, fl
 int euo_render(const euo_job *job, const euo_source *srcs, int nsrc,
                float *out, long ors)
 {
+  /* stages 3 and 4, the rays of deriv_stepper's r10 and r01 (stepper.h:1606-1624): single-facet twined jobs only */
+  if ((job->stage == 3 || job->stage == 4) && (nsrc != 1 || job->ntaps <= 0)) return -6;
   if (nsrc > 1) return euo_render_multi(job, srcs, nsrc, out, ors);
   if (nsrc != 1) return -2;
   const euo_source *src = &srcs[0];
@@ -2235,8 +2239,8 @@ int euo_render(const euo_job *job, const euo_source *srcs, int nsrc,
     float *row = out + (long)(y - job->row_begin) * ors;
     for (int x = 0; x < W; x++) {
       float ray[3], px[4], dbg[3];
-      stepper_ray(&st00, x, y, ray);
-      if (job->stage == 1) {
+      stepper_ray(job->stage == 3 ? &st10 : job->stage == 4 ? &st01 : &st00, x, y, ray);
+      if (job->stage == 1 || job->stage == 3 || job->stage == 4) {
         row[3 * x] = ray[0]; row[3 * x + 1] = ray[1]; row[3 * x + 2] = ray[2];
         continue;
       }
@@ -2266,6 +2270,21 @@ int euo_render(const euo_job *job, const euo_source *srcs, int nsrc,
     }
   }
   free(taps);
+  return 0;
+}
+
+/* planar_stepper (stepper.h:1730-1789) over the job's frame: the planar coordinate of every pixel of the
+ * (cropped) frame, two floats each, from a stepper_base with these bias factors */
+int euo_planar(const euo_job *job, float bias_x, float bias_y, float *out2)
+{
+  const double basis[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+  stepper_t st;
+  stepper_init(&st, job->projection, 0, basis, job->width, job->height, job->x0, job->x1, job->y0, job->y1,
+               bias_x, bias_y);
+  int W = job->width, H = job->height;
+  if (job->crop_w > 0) { st.x_off = job->crop_x0; st.y_off = job->crop_y0; W = job->crop_w; H = job->crop_h; }
+  for (int y = 0; y < H; y++)
+    for (int x = 0; x < W; x++) planar_at(&st, x, y, out2 + 2 * ((long)y * W + x));
   return 0;
 }
 

@@ -11,7 +11,11 @@
  *     against the reference's own zimt headers compiled in place
  *     (oracle/_ref/libref_zimt.so, tests/test_oracle_vs_ref.py) and against
  *     committed fixtures generated from them (tests/golden/).
- *   - envutil stages (steppers, geometry.h projections, mounts, cubemap
+ *   - the steppers (stepper_init, planar_at, stepper_ray; stages 1, 3, 4 and
+ *     euo_planar) are checked bit-for-bit against the reference's stepper.h,
+ *     compiled in place too (tests/test_stepper_pinned.py); their basis is an
+ *     input there and stays unpinned (the reference makes it with Imath).
+ *   - the other envutil stages (geometry.h projections, mounts, cubemap
  *     pickup, IR build, twining, rotation set-up) are restated from the
  *     source text: those headers need OpenImageIO/Imath, which the image
  *     lacks, so the reference cannot be built for them here. They are pinned
@@ -85,7 +89,8 @@ typedef struct {
   int ntaps;                   /* 0: ninputs 3; >0: ninputs 9 (twining) */
   const float *taps;           /* ntaps x {x, y, weight}, make_spread output */
   int row_begin, row_end;      /* rows [row_begin,row_end) are rendered    */
-  int stage;                   /* 0 pixels, 1 rays, 2 source coordinate    */
+  int stage;                   /* 0 pixels, 1 rays, 2 source coordinate, 3 / 4 the rays of the x- / y-biased
+                                * neighbour steppers of a twined single-facet job (else euo_render fails) */
   int nthreads;
   /* store_cropped (envutil_payload.cc:440-474): the output is crop_w x crop_h
    * and the discrete coordinates fed to the stepper are raised by
@@ -158,6 +163,10 @@ void   euo_eval_shifted(const euo_spline *s, int degree, const float *crd2,
 /* the hot path: zimt::process(shape, stepper, environment|twine_t, storer) */
 int    euo_render(const euo_job *job, const euo_source *src, int nsrc,
                   float *out, long out_row_stride /* floats */);
+
+/* planar_stepper over the job's (cropped) frame: crop_h (or height) x crop_w (or width) x 2 floats; bias_x,
+ * bias_y are the stepper's bias factors (.25 for deriv_stepper's neighbours) */
+int    euo_planar(const euo_job *job, float bias_x, float bias_y, float *out2);
 
 /* geometry functors, double precision, for the reference's own property
  * tests (geometry.cc:283-420) */

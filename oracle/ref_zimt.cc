@@ -20,11 +20,15 @@
 //   * masking_t / alpha_masking_t            (masking.h: zimt/bspline.h + zimt/eval.h only), round 3
 //   * pto_parser_type                        (pto.h: standard library only, behind <iostream> as in
 //     envutil_main.cc), round 3
-// envutil's other headers (geometry.h, stepper.h, environment.h, cubemap.h,
-// twining.h) cannot be compiled here: every one of them reaches
-// envutil_basic.h:198-200, which includes OpenImageIO (absent from the image).
-// Those stages are restated from the source text and are NOT pinned by this
-// library ("Oracle").
+//   * the ray generators                    (stepper.h: it includes nothing but zimt/zimt.h; its only
+//     foreign names are the six CM_* enumerators of face_index_t, which oracle/Makefile cuts out of
+//     envutil_basic.h into _ref/face_index.h at build time): the seven target steppers, deriv_stepper,
+//     planar_stepper and generic_stepper's chain, driven by zimt::process (ref_stepper_rays and below)
+// envutil's other headers (geometry.h, environment.h, cubemap.h, twining.h) cannot be
+// compiled here: every one of them reaches envutil_basic.h:198-200, which includes
+// OpenImageIO (absent from the image). Those stages are restated from the source text and
+// are NOT pinned by this library ("Oracle"). Nor is the steppers' basis: the
+// reference makes it with Imath, so here it is an input.
 
 #include <cstring>
 #include <vector>
@@ -39,6 +43,8 @@
 #include <iostream>         // pto.h uses std::cerr / std::cout and leaves the include to envutil_main.cc
 #include "pto.h"            // pto_parser_type: <map>, <vector>, <fstream>, <regex>
 #include <string>
+#include "face_index.h"     // oracle/_ref/face_index.h: face_index_t, cut out of envutil_basic.h by the Makefile
+#include "stepper.h"        // the steppers: zimt/zimt.h and the six CM_* names only
 
 namespace {
 
@@ -403,4 +409,118 @@ extern "C" long ref_pto_parse(const char *text, char *out, long cap)
     out[n] = 0;
   }
   return (long)res.size() + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// stepper.h compiles in place too: the ray generators, driven the way envutil drives them
+// ---------------------------------------------------------------------------------------------------
+
+// zimt::process(shape, stepper, pass_through, storer, bill) over an out_w x out_h raster of N floats per pixel,
+// bill.get_offset = (off_x, off_y): what envutil_payload.cc does for a (cropped) job, with the act functor and
+// everything after it left out. The back-end is the one this file pins: goading, 16 lanes, segment 512.
+template <int N, typename S>
+static void stepper_run(S st, long off_x, long off_y, long out_w, long out_h, float *out)
+{
+  typedef zimt::xel_t<float, N> px_t;
+  zimt::view_t<2, px_t> trg((px_t *)out, {1L, out_w}, {std::size_t(out_w), std::size_t(out_h)});
+  zimt::storer<float, N, 2, L> put(trg);
+  zimt::pass_through<float, N, L> act;
+  zimt::bill_t bill;
+  bill.get_offset.push_back(off_x);
+  bill.get_offset.push_back(off_y);
+  zimt::process(trg.shape, st, act, put, bill);
+}
+
+// kind: projection_t's numbering (SPHERICAL 0 ... BIATAN6 6), which is also the oracle's EUO_* and the library's
+#define REF_STEPPER_KINDS(CALL)                                                                        \
+  switch (kind) {                                                                                      \
+    case 0: CALL(spherical_stepper) break;                                                             \
+    case 1: CALL(cylindrical_stepper) break;                                                           \
+    case 2: CALL(rectilinear_stepper) break;                                                           \
+    case 3: CALL(stereographic_stepper) break;                                                         \
+    case 4: CALL(fisheye_stepper) break;                                                               \
+    case 5: CALL(cubemap_stepper) break;                                                               \
+    case 6: CALL(biatan6_stepper) break;                                                               \
+    default: return -1;                                                                                \
+  }
+
+typedef zimt::xel_t<float, 3> ref_c3;
+
+// S<float, 16, normalize>(xx, yy, zz, W, H, a0, a1, b0, b1, bias_x, bias_y): three floats per pixel. The extent
+// and the basis arrive as doubles and narrow to float at the constructor call, as they do in envutil and in the
+// oracle (stepper_init). The basis (rows xx, yy, zz) is an INPUT: the reference makes it with Imath.
+extern "C" int ref_stepper_rays(int kind, int normalize, int W, int H, double a0, double a1, double b0, double b1,
+                                const double *basis9, float bias_x, float bias_y, long off_x, long off_y,
+                                long out_w, long out_h, float *out)
+{
+  using namespace project;
+  ref_c3 xx{float(basis9[0]), float(basis9[1]), float(basis9[2])}, yy{float(basis9[3]), float(basis9[4]), float(basis9[5])},
+         zz{float(basis9[6]), float(basis9[7]), float(basis9[8])};
+#define REF_ST(S)                                                                                                  \
+  if (normalize) stepper_run<3>(S<float, L, true>(xx, yy, zz, W, H, float(a0), float(a1), float(b0), float(b1),   \
+                                                  bias_x, bias_y), off_x, off_y, out_w, out_h, out);              \
+  else stepper_run<3>(S<float, L, false>(xx, yy, zz, W, H, float(a0), float(a1), float(b0), float(b1),            \
+                                         bias_x, bias_y), off_x, off_y, out_w, out_h, out);
+  REF_STEPPER_KINDS(REF_ST)
+#undef REF_ST
+  return 0;
+}
+
+// deriv_stepper<float, 16, S> (stepper.h:1587-1715, normalize = true as twining uses it): the ninepack r00, r10,
+// r01 of every pixel, nine floats
+extern "C" int ref_deriv_rays(int kind, int W, int H, double a0, double a1, double b0, double b1,
+                              const double *basis9, float bias, long off_x, long off_y, long out_w, long out_h,
+                              float *out9)
+{
+  using namespace project;
+  ref_c3 xx{float(basis9[0]), float(basis9[1]), float(basis9[2])}, yy{float(basis9[3]), float(basis9[4]), float(basis9[5])},
+         zz{float(basis9[6]), float(basis9[7]), float(basis9[8])};
+#define REF_DS(S)                                                                                                  \
+  stepper_run<9>(deriv_stepper<float, L, S>(xx, yy, zz, W, H, float(a0), float(a1), float(b0), float(b1), bias),  \
+                 off_x, off_y, out_w, out_h, out9);
+  REF_STEPPER_KINDS(REF_DS)
+#undef REF_DS
+  return 0;
+}
+
+// planar_stepper<float, 16> (stepper.h:1730-1789): the 2D planar coordinate of every pixel - stepper_base's chain
+// (init per segment, += delta per vector) and nothing else
+extern "C" int ref_planar(int W, int H, double a0, double a1, double b0, double b1, float bias_x, float bias_y,
+                          long off_x, long off_y, long out_w, long out_h, float *out2)
+{
+  using namespace project;
+  stepper_run<2>(planar_stepper<float, L>(W, H, float(a0), float(a1), float(b0), float(b1), bias_x, bias_y),
+                 off_x, off_y, out_w, out_h, out2);
+  return 0;
+}
+
+// generic_stepper<float, 16, normalize> (stepper.h:353-490) over a functor of this harness's own, planar (x, y) ->
+// (x, y, 1): envutil's tf_ex_facet needs geometry.h, which is closed. This pins the planar chain of the generic
+// path and where it normalizes, not the transformation.
+namespace {
+struct planar_to_xy1 : public zimt::unary_functor<zimt::xel_t<float, 2>, zimt::xel_t<float, 3>, L> {
+  template <typename I, typename O>
+  void eval(const I &in, O &out) const {
+    out[0] = in[0];
+    out[1] = in[1];
+    out[2] = 1.0f;
+  }
+};
+}  // namespace
+
+extern "C" int ref_generic_rays(int normalize, int W, int H, double a0, double a1, double b0, double b1,
+                                float bias_x, float bias_y, long off_x, long off_y, long out_w, long out_h,
+                                float *out3)
+{
+  using namespace project;
+  if (normalize) {
+    generic_stepper<float, L, true>::tf_t tf = planar_to_xy1();
+    stepper_run<3>(generic_stepper<float, L, true>(W, H, float(a0), float(a1), float(b0), float(b1), bias_x, bias_y, tf),
+                   off_x, off_y, out_w, out_h, out3);
+  } else {
+    generic_stepper<float, L, false>::tf_t tf = planar_to_xy1();
+    stepper_run<3>(generic_stepper<float, L, false>(W, H, float(a0), float(a1), float(b0), float(b1), bias_x, bias_y, tf),
+                   off_x, off_y, out_w, out_h, out3);
+  }
+  return 0;
 }

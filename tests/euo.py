@@ -84,6 +84,9 @@ def lib():
         _lib.euo_get_step.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double]
         _lib.euo_get_extent.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
         _lib.euo_make_r3.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        _lib.euo_rotate_r3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.euo_rotate_r3.restype = None
+        _lib.euo_planar.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         _lib.euo_make_spread.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float,
                                          C.c_float, C.c_void_p, C.c_int]
         _lib.euo_basis_weights.argtypes = [C.c_int, C.c_float, C.c_void_p]
@@ -113,6 +116,14 @@ def get_extent(prj, w, h, hfov):
 def make_r3(roll, pitch, yaw, inverse=False):
     m = np.zeros(9, np.float64)
     lib().euo_make_r3(roll, pitch, yaw, int(inverse), ptr(m))
+    return m.reshape(3, 3)
+
+
+def rotate_r3(lhs, rhs):
+    """rotate(r3_t lhs, r3_t rhs) (euo_rotate_r3): the stepper's basis is rotate(r_camera, r_facet^-1)"""
+    lhs, rhs = (np.ascontiguousarray(m, np.float64) for m in (lhs, rhs))
+    m = np.zeros(9, np.float64)
+    lib().euo_rotate_r3(ptr(lhs), ptr(rhs), ptr(m))
     return m.reshape(3, 3)
 
 

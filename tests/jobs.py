@@ -149,7 +149,9 @@ def oracle_source_from_container(prj, width, height, hfov_deg, container, geom, 
 
 def oracle_render(args, osrc, stage=0, row_begin=0, row_end=None, nthreads=8, nch=None):
     """args: envutil_amd.arguments (only its plain fields are read); osrc: one
-    OracleSource or a list of them (multi-facet job)"""
+    OracleSource or a list of them (multi-facet job). stage 1: the rays; 2: source coordinates; 3 / 4: the
+    rays of the x- / y-biased neighbour steppers of a twined single-facet job (any other job: euo_render
+    fails, as eu_hip_render does)"""
     srcs = osrc if isinstance(osrc, (list, tuple)) else [osrc]
     osrc = srcs[0]
     arr = (euo.Source * len(srcs))(*[o.s for o in srcs])
@@ -188,6 +190,24 @@ def oracle_render(args, osrc, stage=0, row_begin=0, row_end=None, nthreads=8, nc
     och = 3 if stage else (nch or osrc.nch)
     out = np.zeros((j.row_end - j.row_begin, w, och), np.float32)
     rc = euo.lib().euo_render(C.byref(j), arr, len(srcs), euo.ptr(out), w * och)
+    assert rc == 0, rc
+    return out
+
+
+def oracle_planar(args, bias_x=0.0, bias_y=0.0):
+    """the planar coordinate of every pixel of the job's (cropped) frame, (rows, width, 2): planar_stepper with these
+    bias factors (euo_planar). args: as for oracle_render; only the target's geometry and the crop are read"""
+    j = euo.Job()
+    j.projection = args.projection
+    j.width, j.height = args.width, args.height
+    j.x0, j.x1, j.y0, j.y1 = (float(v) for v in args.extent)
+    w, h = args.width, args.height
+    if getattr(args, "store_cropped", False):
+        x0, x1, y0, y1 = args.p_crop
+        j.crop_x0, j.crop_y0, j.crop_w, j.crop_h = x0, y0, x1 - x0, y1 - y0
+        w, h = x1 - x0, y1 - y0
+    out = np.zeros((h, w, 2), np.float32)
+    rc = euo.lib().euo_planar(C.byref(j), bias_x, bias_y, euo.ptr(out))
     assert rc == 0, rc
     return out
 

@@ -1,8 +1,8 @@
 """ctypes bindings of oracle/_ref/libref_zimt.so - the reference's own zimt
 headers compiled in place from a reference checkout (oracle/Makefile, REF). Only
 present where that checkout is; tests marked 'ref' compare with it live there, and
-elsewhere with the SHA-256 of its results recorded in tests/golden/ref_digests.json
-(same())."""
+elsewhere with the SHA-256 of its results recorded in tests/golden/ref_digests.json and,
+for the steppers, tests/golden/stepper_digests.json (same())."""
 import ctypes as C
 import hashlib
 import json
@@ -13,12 +13,16 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "_ref", "libref_zimt.so")
 DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")
+# the digests of the steppers' results (keys "stepper_...", tests/test_stepper_pinned.py) have a file of their own
+STEPPER_DIGESTS = os.path.join(ROOT, "tests", "golden", "stepper_digests.json")
 RECORDING = False       # tests/golden/make_ref_digests.py: collect into RECORDED, skip the check against DIGESTS
 RECORDED = {}
 
 
-def available():
-    return os.path.exists(LIB)
+def available(symbol=None):
+    """the library is built - and, when a symbol is named, exports it (a library built from an earlier
+    oracle/ref_zimt.cc does not have the steppers)"""
+    return os.path.exists(LIB) and (symbol is None or hasattr(lib(), symbol))
 
 
 def digest(a):
@@ -30,17 +34,21 @@ def digest(a):
 _digests = None
 
 
-def same(key, ours, reference):
+def same(key, ours, reference, symbol=None):
     """True when `ours` is bit for bit the reference's result: `reference()` (a call into the library) where
-    the library is built - and then its digest must be the one recorded under `key` - else the recorded digest"""
+    the library is built (and exports `symbol`, if one is named) - and then its digest must be the one recorded
+    under `key` - else the recorded digest"""
     global _digests
     if _digests is None:
-        _digests = json.load(open(DIGESTS)) if os.path.exists(DIGESTS) else {}
-    if not available():
+        _digests = {}
+        for path in (DIGESTS, STEPPER_DIGESTS):
+            if os.path.exists(path):
+                _digests.update(json.load(open(path)))
+    if not available(symbol):
         return digest(ours) == _digests[key]
     ref = np.ascontiguousarray(reference(), np.float32)
     RECORDED[key] = digest(ref)
-    assert RECORDING or _digests.get(key) == RECORDED[key], f"tests/golden/ref_digests.json is stale at {key}"
+    assert RECORDING or _digests.get(key) == RECORDED[key], f"the digest recorded under tests/golden for {key} is stale"
     ours = np.ascontiguousarray(ours, np.float32)
     return ours.shape == ref.shape and (ours.view(np.uint32) == ref.view(np.uint32)).all()
 
@@ -208,4 +216,64 @@ def alpha_masking(spline, paint, crd):
     f.restype = None
     f.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_long, C.c_void_p]
     f(spline.h_, paint, ptr(crd), crd.shape[0], ptr(out))
+    return out
+
+
+def _basis(basis):
+    return np.ascontiguousarray(basis, np.float64).reshape(9)
+
+
+_STEPPER_TAIL = [C.c_long] * 4 + [C.c_void_p]      # off_x, off_y, out_w, out_h, out
+
+
+def stepper_rays(kind, normalize, w, h, extent, basis, bias=(0.0, 0.0), offset=(0, 0), out_shape=None):
+    """S<float, 16, normalize>(xx, yy, zz, w, h, extent..., bias_x, bias_y) through zimt::process with
+    bill.get_offset = offset, over out_shape = (width, height) (default: the whole w x h): (rows, width, 3).
+    kind: projection_t's number. basis: 3 x 3 doubles, rows xx, yy, zz - an input, not pinned (Imath)"""
+    ow, oh = out_shape or (w, h)
+    out = np.full((oh, ow, 3), np.nan, np.float32)
+    b = _basis(basis)
+    f = lib().ref_stepper_rays
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] * 4 + [C.c_double] * 4 + [C.c_void_p, C.c_float, C.c_float] + _STEPPER_TAIL
+    rc = f(kind, int(normalize), w, h, *(float(v) for v in extent), ptr(b), bias[0], bias[1], offset[0], offset[1],
+           ow, oh, ptr(out))
+    assert rc == 0, rc
+    return out
+
+
+def deriv_rays(kind, w, h, extent, basis, bias=0.25, offset=(0, 0), out_shape=None):
+    """deriv_stepper<float, 16, S>(xx, yy, zz, w, h, extent..., bias): the ninepacks r00, r10, r01, (rows, width, 9)"""
+    ow, oh = out_shape or (w, h)
+    out = np.full((oh, ow, 9), np.nan, np.float32)
+    b = _basis(basis)
+    f = lib().ref_deriv_rays
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] * 3 + [C.c_double] * 4 + [C.c_void_p, C.c_float] + _STEPPER_TAIL
+    rc = f(kind, w, h, *(float(v) for v in extent), ptr(b), bias, offset[0], offset[1], ow, oh, ptr(out))
+    assert rc == 0, rc
+    return out
+
+
+def planar(w, h, extent, bias=(0.0, 0.0), offset=(0, 0), out_shape=None):
+    """planar_stepper<float, 16>(w, h, extent..., bias_x, bias_y): (rows, width, 2)"""
+    ow, oh = out_shape or (w, h)
+    out = np.full((oh, ow, 2), np.nan, np.float32)
+    f = lib().ref_planar
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] * 2 + [C.c_double] * 4 + [C.c_float, C.c_float] + _STEPPER_TAIL
+    rc = f(w, h, *(float(v) for v in extent), bias[0], bias[1], offset[0], offset[1], ow, oh, ptr(out))
+    assert rc == 0, rc
+    return out
+
+
+def generic_rays(normalize, w, h, extent, bias=(0.0, 0.0), offset=(0, 0), out_shape=None):
+    """generic_stepper<float, 16, normalize> over the harness's own functor (x, y) -> (x, y, 1): (rows, width, 3)"""
+    ow, oh = out_shape or (w, h)
+    out = np.full((oh, ow, 3), np.nan, np.float32)
+    f = lib().ref_generic_rays
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] * 3 + [C.c_double] * 4 + [C.c_float, C.c_float] + _STEPPER_TAIL
+    rc = f(int(normalize), w, h, *(float(v) for v in extent), bias[0], bias[1], offset[0], offset[1], ow, oh, ptr(out))
+    assert rc == 0, rc
     return out
