@@ -137,6 +137,7 @@ def lib():
     L.eu_hip_container_geometry.argtypes = [i32, i32, i32, C.c_int64, C.c_int64, vp]
     L.eu_hip_source_load.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_source_load_edited.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_source_load_samples.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_facet_alpha_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.eu_hip_facet_alpha_rows.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32]
     L.eu_hip_source_adopt.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -243,6 +244,13 @@ def _facet_edit(polygons, crop, crop_kind, pixel_channels, on_device):
     e.crop_x0, e.crop_x1, e.crop_y0, e.crop_y1 = crop if crop is not None else (0, 0, 0, 0)
     e.pixel_channels, e.pixels_on_device = pixel_channels, int(on_device)
     return e, (keep, arr)
+
+
+class Samples(C.Structure):
+    """struct eu_samples"""
+    _fields_ = [("data", C.c_void_p), ("bits", C.c_int32), ("big_endian", C.c_int32),
+                ("pixel_channels", C.c_int32), ("on_device", C.c_int32),
+                ("colour_table", C.c_void_p), ("alpha_table", C.c_void_p)]
 
 
 def _is_torch(x):
@@ -401,6 +409,55 @@ class Source:
             return cls(h, fct)
         _check(lib().eu_hip_source_load(C.byref(cf), _ptr(pixels), spline_degree,
                                         prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct)
+
+    @classmethod
+    def load_samples(cls, fct, samples, colour_table=None, alpha_table=None, maxval=None, big_endian=False,
+                     spline_degree=1, prefilter_degree=None, support_min=8, tile_size=64, masks=(), crop=None,
+                     crop_kind=0):
+        """8- or 16-bit integer samples -> the same source as load() of table[samples], decoded on the device
+        (eu_hip_source_load_samples): the samples go up as they are, no float copy is made on the host.
+        `samples`: a uint8 / uint16 numpy array or a contiguous torch tensor of those dtypes on the library's
+        device, (h, w, channels) or (h, w); big_endian: 16-bit samples are stored high byte first, as in PNM /
+        PAM files. colour_table / alpha_table: float32, 256 or 65536 entries - the float each value becomes in
+        a colour channel / in the last of 2 or 4 channels (alpha_table None: the colour table). Without tables
+        both are v / maxval in float32, maxval defaulting to 255 / 65535. masks, crop, crop_kind as load()."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
+        on_device = _is_torch(samples)
+        if on_device:
+            import torch
+            bits = {torch.uint8: 8, torch.uint16: 16}.get(samples.dtype)
+            if bits is None or not samples.is_cuda or not samples.is_contiguous():
+                raise EuError("a torch tensor handed over as samples is uint8 or uint16, contiguous and on the device")
+            torch.cuda.current_stream(samples.device).synchronize()
+            data = samples.data_ptr()
+        else:
+            samples = np.asarray(samples)
+            bits = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16}.get(samples.dtype.newbyteorder("="))
+            if bits is None:
+                raise EuError("samples are uint8 or uint16")
+            if bits == 16 and samples.dtype.byteorder == ">":
+                samples, big_endian = samples.view(np.uint16), True      # the bytes as they are
+            samples = np.ascontiguousarray(samples)
+            data = samples.ctypes.data
+        n = 1 << bits
+        if colour_table is None:
+            mv = np.float32(maxval if maxval is not None else n - 1)
+            colour_table = np.arange(n, dtype=np.float32) / mv
+        tabs = [np.ascontiguousarray(t, np.float32) for t in (colour_table, alpha_table) if t is not None]
+        if any(t.shape != (n,) for t in tabs):
+            raise EuError(f"a table for {bits}-bit samples has {n} entries")
+        # (h, w, channels); (h, w) for the one channel of a facet that gains alpha; else as the facet says
+        pch = samples.shape[2] if samples.ndim == 3 else 1 if samples.ndim == 2 and fct.nchannels == 2 else fct.nchannels
+        sm = Samples(data, bits, int(bool(big_endian)), pch, int(on_device), tabs[0].ctypes.data,
+                     tabs[1].ctypes.data if len(tabs) > 1 else None)
+        e, hold = _facet_edit(masks, crop, crop_kind, pch, on_device)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        edited = len(masks) or crop is not None
+        _check(lib().eu_hip_source_load_samples(C.byref(cf), C.byref(sm), C.byref(e) if edited else None, spline_degree,
+                                                prefilter_degree, support_min, tile_size, C.byref(h)))
         return cls(h, fct)
 
     @classmethod

@@ -15,6 +15,7 @@
 #include "eu_setup_math.h"
 #include "eu_imageprep.h"
 #include "eu_alpha.h"
+#include "eu_decode.h"
 #include "eu_math2.h"
 #include "eu_launch.h"
 #include "eu_ray_guard.h"
@@ -1119,6 +1120,108 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
     (void)hipFree(s->dev);
     delete s;
     if (prc) return prc;           // the plan's upload or the edit's launch: the message is set
+    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
+    return fail(rc, "device set-up stage failed");
+  }
+  *out = s;
+  return EU_OK;
+}
+
+int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
+                               int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!smp || !smp->data || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (smp->bits != 8 && smp->bits != 16) return fail(EU_ERR_ARGUMENT, "source_load_samples: bits must be 8 or 16");
+  if (!smp->colour_table) return fail(EU_ERR_ARGUMENT, "source_load_samples: null colour table");
+  // the edit as given, with the samples' channel count in place of its own
+  eu_facet_edit ed {};
+  if (edit) ed = *edit;
+  ed.pixel_channels = smp->pixel_channels;
+  ed.pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(&ed, fct->nchannels, "source_load_samples", &asked))) return rc;
+  if (smp->on_device && smp->bits == 16 && reinterpret_cast<uintptr_t>(smp->data) % 2)
+    return fail(EU_ERR_ARGUMENT, "source_load_samples: 16-bit samples on the device lie at an even address");
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  if ((rc = ensure_init())) return rc;
+  int bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  const int nch = s->nch, src_ch = smp->pixel_channels, iir_stream = eu_read_switches().iir_stream;
+  const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
+  const bool cube = eu_cube_source(fct->projection);
+  eu::metrics m {};
+  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  const int w = cube ? int(m.face_px) : int(s->geom.core[0]), h = cube ? int(6 * m.face_px) : int(s->geom.core[1]);
+  const size_t npix = size_t(w) * size_t(h), ntab = size_t(1) << smp->bits;
+  const size_t nbytes = npix * size_t(src_ch) * size_t(smp->bits / 8);
+  // both tables in one block, and behind them the samples of a host image, as they are
+  std::vector<float> tabs;
+  try {
+    tabs.assign(smp->colour_table, smp->colour_table + ntab);
+    const float *at = smp->alpha_table ? smp->alpha_table : smp->colour_table;
+    tabs.insert(tabs.end(), at, at + ntab);
+  } catch (...) { (void)hipFree(s->dev); delete s; return fail(EU_ERR_MEMORY, "source_load_samples: host memory"); }
+  char *block = nullptr;
+  float *staged = nullptr, *faces = nullptr;     // decoded pixels in front of the edit; the faces of a cubemap
+  int prc = 0;
+  hipError_t e = hipMalloc((void **)&block, tabs.size() * sizeof(float) + (smp->on_device ? 0 : nbytes));
+  if (e == hipSuccess) e = hipMemcpyAsync(block, tabs.data(), tabs.size() * sizeof(float), hipMemcpyHostToDevice, g.stream);
+  const void *samples = smp->data;
+  if (e == hipSuccess && !smp->on_device) {
+    e = hipMemcpyAsync(block + tabs.size() * sizeof(float), smp->data, nbytes, hipMemcpyHostToDevice, g.stream);
+    samples = block + tabs.size() * sizeof(float);
+  }
+  if (e == hipSuccess && edited) e = hipMalloc((void **)&staged, npix * src_ch * sizeof(float));
+  if (e == hipSuccess && cube) e = hipMalloc((void **)&faces, npix * nch * sizeof(float));
+  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
+  if (e == hipSuccess) {
+    const eu_container &gm = s->geom;
+    float *dst = cube ? faces : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
+    const size_t dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
+    // samples -> floats: straight into the faces / the core of the container, or - with masks or a crop - into a
+    // dense buffer that the edit reads as it reads pixels_on_device input (the channel a facet gains is then its work)
+    eu_decode_params d {};
+    d.src = samples; d.tables = reinterpret_cast<const float *>(block);
+    d.dst = edited ? staged : dst;
+    d.dst_pitch = edited ? size_t(w) : dst_pitch;
+    d.w = w; d.h = h; d.bits = smp->bits; d.big_endian = smp->big_endian != 0;
+    d.nch = edited ? src_ch : nch; d.src_ch = src_ch;
+    if (eu_launch_decode(&d, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_samples: kernel launch failed");
+    if (!prc && edited) {
+      eu_alpha_params p {};
+      p.src = staged; p.dst = dst;
+      p.src_pitch = size_t(w); p.dst_pitch = dst_pitch;
+      p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
+      prc = upload_alpha_plan(&ed, w, h, &p);
+      if (!prc && eu_launch_facet_alpha(&p, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_samples: kernel launch failed");
+    }
+  }
+  if (e == hipSuccess && !prc) {
+    if (cube) {
+      rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
+                                   m.refc_md, m.model_to_px, prefilter_degree, iir_stream, g.stream);
+    } else {
+      // as eu_hip_source_load: full spherical images get the two-axis periodic scheme
+      int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
+                      && fct->width == 2 * fct->height;
+      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
+    }
+  }
+  const hipError_t e2 = hipStreamSynchronize(g.stream);
+  if (e == hipSuccess) e = e2;
+  if (block) (void)hipFree(block);
+  if (staged) (void)hipFree(staged);
+  if (faces) (void)hipFree(faces);
+  if (e != hipSuccess || rc || prc) {
+    (void)hipFree(s->dev);
+    delete s;
+    if (prc) return prc;
     if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
     return fail(rc, "device set-up stage failed");
   }

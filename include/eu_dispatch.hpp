@@ -94,6 +94,14 @@ struct facet_spec : public facet_base
   // edit (envutil_main.cc:1062-1075). 0: nchannels.
   int pixel_channels = 0;
   const float *pixels = nullptr;  // window_width x window_height x nchannels (cubemaps: 6 faces)
+  // The same image as 8- or 16-bit integer samples instead (pixels == nullptr): `pixel_channels` (0: nchannels)
+  // samples per pixel, and the float each value becomes as two host tables of 1 << sample_bits entries - one for
+  // the colour channels, one for the last of 2 or 4 channels (nullptr: the colour table). payload() sends the
+  // samples up as they are and decodes them on the device (eu_hip_source_load_samples), masks and crop included.
+  const void *samples = nullptr;
+  int sample_bits = 0;            // 8 or 16
+  bool samples_big_endian = false;
+  const float *colour_table = nullptr, *alpha_table = nullptr;
 };
 
 struct arguments : public facet_base
@@ -250,17 +258,28 @@ struct hip_dispatch : public dispatch_base
         eu_facet e = to_eu(fct);
         eu_source *s = nullptr;
         int rc;
-        if ((fct.has_pto_mask || fct.has_lens_crop) && !fct.pixels_prepared) {
-          // PTO masks and lens crops edit the pixels at load time, as source_t's constructor does
-          // (environment.h:700-890) - here on the device, on the way into the container
-          std::vector<eu_mask_polygon> polys;
+        // PTO masks and lens crops edit the pixels at load time, as source_t's constructor does
+        // (environment.h:700-890) - here on the device, on the way into the container
+        const bool edit = (fct.has_pto_mask || fct.has_lens_crop) && !fct.pixels_prepared;
+        std::vector<eu_mask_polygon> polys;
+        eu_facet_edit ed {};
+        if (edit) {
           for (const auto &m : fct.pto_mask_v)
             if (m.variant == 0) polys.push_back({ int(m.vx.size()), m.vx.data(), m.vy.data() });   // other variants: ignored, as there
-          eu_facet_edit ed {};
           ed.polygons = polys.data(); ed.npolygons = int(polys.size());
           ed.crop_kind = !fct.has_lens_crop ? 0 : fct.projection == FISHEYE ? 2 : 1;
           ed.crop_x0 = fct.crop_x0; ed.crop_x1 = fct.crop_x1; ed.crop_y0 = fct.crop_y0; ed.crop_y1 = fct.crop_y1;
           ed.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
+        }
+        if (fct.samples && !fct.pixels) {
+          // integer samples: uploaded as they are, decoded on the device through the facet's tables and the same edit
+          eu_samples sm {};
+          sm.data = fct.samples; sm.bits = fct.sample_bits; sm.big_endian = fct.samples_big_endian;
+          sm.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
+          sm.colour_table = fct.colour_table; sm.alpha_table = fct.alpha_table;
+          rc = eu_hip_source_load_samples(&e, &sm, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
+                                          args.support_min, args.tile_size, &s);
+        } else if (edit) {
           rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
                                          args.support_min, args.tile_size, &s);
         } else {

@@ -270,6 +270,30 @@ int  eu_hip_source_load(const eu_facet *fct, const float *pixels,
 int  eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit,
                                int spline_degree, int prefilter_degree, int support_min,
                                int tile_size, eu_source **out);
+/* The same container from 8- or 16-bit integer samples: a decoder's frame, the payload of a PNM / PAM file.
+ * The samples go to the device as they are - a quarter or half of the float image's bytes - and become
+ * floats there (eu_decode.hip) through the caller's tables, on the way into the container: bit for bit the
+ * container eu_hip_source_load_edited builds from float pixels p[i] = table_of_channel[sample[i]] with the
+ * same edit (edit == NULL: none; edit->pixel_channels and edit->pixels_on_device are ignored in favour of
+ * smp). The tables ALWAYS have 1 << bits entries, so that every bit pattern has one - samples above a PNM
+ * file's maxval too; the library knows nothing of colour spaces or of maxval, the tables say it all. Argument
+ * errors (EU_ERR_ARGUMENT) are reported before a device is looked for: null pointers, bits other than 8 or
+ * 16, pixel_channels other than nchannels or nchannels - 1 or below 1, a null colour_table, an edit or a
+ * gained channel on a facet whose nchannels is not 2 or 4, device data of 16-bit samples at an odd address,
+ * degrees out of range. */
+typedef struct eu_samples {
+  const void *data;          /* width x height x pixel_channels samples, rows dense; cubemaps: the six faces stacked */
+  int32_t bits;              /* 8: uint8_t, 16: uint16_t */
+  int32_t big_endian;        /* bits 16: high byte first, as PNM / PAM store it; 0: host order */
+  int32_t pixel_channels;    /* fct->nchannels, or fct->nchannels - 1: the facet gains alpha = 1.0f here */
+  int32_t on_device;         /* `data` is memory of the library's device */
+  const float *colour_table; /* host, 1 << bits floats: the float a colour sample becomes */
+  const float *alpha_table;  /* host, 1 << bits floats: the same for the LAST channel when pixel_channels is 2 or 4;
+                                NULL: colour_table for it too */
+} eu_samples;
+int  eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit,
+                                int spline_degree, int prefilter_degree, int support_min, int tile_size,
+                                eu_source **out);
 /* Adopt an already prefiltered and braced container (host pointer, shape as
  * eu_hip_container_geometry reports; cubemaps: the IR image section_px x
  * 6*section_px). This is what a bound reference hands over when it keeps its

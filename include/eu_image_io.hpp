@@ -29,6 +29,10 @@
 // format string with one %s, filled with left, right, top, bottom, front, back (cubeface_series,
 // envutil_basic.h:267-340).
 //
+// Integer files can also be handed on as they are: read_samples() returns the file's sample bytes and
+// sample_tables() the float each sample value becomes on the way read_image() + convert_colour() take it -
+// what eu_hip_source_load_samples wants, which widens and linearises on the device.
+//
 // Header-only, host code, no dependency on the HIP library.
 #ifndef EU_IMAGE_IO_HPP
 #define EU_IMAGE_IO_HPP
@@ -334,23 +338,58 @@ inline float from_linear(colour_class c, float v)
   if (c == CSP_REC709) return v < 0.018f ? 4.5f * v : 1.099f * std::pow(v, 0.45f) - 0.099f;
   return v;
 }
-// npix pixels of nch interleaved channels from colour space `from` to `to`, in place; the alpha channel (the
-// last of 2 or 4) stays. False with a message for a name this table does not know.
-inline bool convert_colour(float *px, size_t npix, int nch, const std::string &from, const std::string &to, std::string &err)
+// the classes of a conversion `from` -> `to`; *same: nothing to do (equal names, equal classes). False with a
+// message for a name this table does not know.
+inline bool colour_pair(const std::string &from, const std::string &to, colour_class &a, colour_class &b, bool &same, std::string &err)
 {
+  a = b = CSP_UNKNOWN;
+  same = true;
   if (from == to) return true;
-  const colour_class a = classify_colour_space(from), b = classify_colour_space(to);
+  a = classify_colour_space(from); b = classify_colour_space(to);
   if (a == CSP_UNKNOWN || b == CSP_UNKNOWN) {
     err = "colour space '" + (a == CSP_UNKNOWN ? from : to) + "' is not known here (known: Linear / scene_linear / lin_srgb, sRGB, Rec709; OpenColorIO configurations are not read)";
     return false;
   }
-  if (a == b) return true;
+  same = a == b;
+  return true;
+}
+// one colour sample from class a to class b: the ONE statement of the curve, for convert_colour and sample_tables
+inline float convert_sample(colour_class a, colour_class b, float v) { return from_linear(b, to_linear(a, v)); }
+// npix pixels of nch interleaved channels from colour space `from` to `to`, in place; the alpha channel (the
+// last of 2 or 4) stays. False with a message for a name this table does not know.
+inline bool convert_colour(float *px, size_t npix, int nch, const std::string &from, const std::string &to, std::string &err)
+{
+  colour_class a, b;
+  bool same;
+  if (!colour_pair(from, to, a, b, same, err)) return false;
+  if (same) return true;
   const int ncol = (nch == 2 || nch == 4) ? nch - 1 : nch;
   for (size_t i = 0; i < npix; i++)
     for (int c = 0; c < ncol; c++) {
       float &v = px[i * size_t(nch) + c];
-      v = from_linear(b, to_linear(a, v));
+      v = convert_sample(a, b, v);
     }
+  return true;
+}
+
+// The floats the samples of an integer image become, as tables over EVERY value of `bits` bits (8 or 16; values
+// above maxval included - a file may hold them): alpha[v] is read_one's float(v) / float(maxval), colour[v] what
+// convert_colour makes of that float on the way from `from` to `to`. A sample's float depends on its value alone,
+// so a look-up in these tables gives the bits of read_image + convert_colour (eu_hip_source_load_samples).
+inline bool sample_tables(int bits, int maxval, const std::string &from, const std::string &to, std::vector<float> &colour,
+                          std::vector<float> &alpha, std::string &err)
+{
+  if ((bits != 8 && bits != 16) || maxval < 1 || maxval >= (1 << bits)) { err = "sample tables: 8 or 16 bits, maxval within them"; return false; }
+  colour_class a, b;
+  bool same;
+  if (!colour_pair(from, to, a, b, same, err)) return false;
+  const size_t n = size_t(1) << bits;
+  const float mv = float(maxval);
+  colour.resize(n); alpha.resize(n);
+  for (size_t v = 0; v < n; v++) {
+    alpha[v] = float(v) / mv;
+    colour[v] = same ? alpha[v] : convert_sample(a, b, alpha[v]);
+  }
   return true;
 }
 
@@ -369,6 +408,53 @@ inline bool read_image(const std::string &name, std::vector<float> &pixels, int 
   for (size_t i = 0; i < faces.size(); i++)
     if (!read_one(faces[i], h, pixels.data() + i * per, err)) return false;
   width = h.width; height = h.height * int(faces.size()); nchannels = h.nchannels;
+  return true;
+}
+
+// the raw samples of a PNM / PAM file: `bytes` per sample, big endian as stored; the header checks and messages
+// are read_one's
+inline bool read_samples_one(const std::string &name, header &h, uint8_t *dst, std::string &err)
+{
+  FILE *f = std::fopen(name.c_str(), "rb");
+  if (!f) { err = "cannot open " + name; return false; }
+  header g;
+  if (!read_header(f, g, err)) { std::fclose(f); err = name + ": " + err; return false; }
+  if (h.width && (g.width != h.width || g.height != h.height || g.nchannels != h.nchannels)) {
+    std::fclose(f);
+    err = name + ": size differs from the first image of the set";
+    return false;
+  }
+  // (one pair of tables serves the whole set)
+  if (h.width && g.maxval != h.maxval) { std::fclose(f); err = name + ": MAXVAL differs from the first image of the set"; return false; }
+  if (g.maxval == 0) { std::fclose(f); err = name + ": not an integer format"; return false; }
+  h = g;
+  const size_t n = size_t(h.width) * h.height * h.nchannels * (h.maxval > 255 ? 2 : 1);
+  const bool ok = std::fread(dst, 1, n, f) == n;
+  std::fclose(f);
+  if (!ok) err = name + ": truncated pixel data";
+  return ok;
+}
+
+// read_image for the integer formats, without the step to float: the file's sample bytes (16 bit: big endian, as
+// PNM / PAM store them), rows top to bottom, six cube faces stacked. `bits` is 8 for maxval <= 255, else 16.
+// .pfm / .hdr / .pic: false, "not an integer format".
+inline bool read_samples(const std::string &name, std::vector<uint8_t> &samples, int &width, int &height, int &nchannels,
+                         int &maxval, int &bits, std::string &err)
+{
+  std::vector<std::string> faces;
+  if (name.find('%') != std::string::npos) {
+    if (!cubeface_names(name, faces)) { err = "a format string needs exactly one %s: " + name; return false; }
+  } else faces.push_back(name);
+  header h;
+  if (!probe_one(faces[0], h, err)) return false;
+  if (h.maxval == 0) { err = faces[0] + ": not an integer format"; return false; }
+  const size_t per = size_t(h.width) * h.height * h.nchannels * (h.maxval > 255 ? 2 : 1);
+  try { samples.resize(per * faces.size()); }
+  catch (const std::exception &) { err = name + ": not enough host memory for " + std::to_string(h.width) + " x " + std::to_string(h.height) + " pixels"; return false; }
+  for (size_t i = 0; i < faces.size(); i++)
+    if (!read_samples_one(faces[i], h, samples.data() + i * per, err)) return false;
+  width = h.width; height = h.height * int(faces.size()); nchannels = h.nchannels;
+  maxval = h.maxval; bits = h.maxval > 255 ? 8 * 2 : 8;
   return true;
 }
 

@@ -124,8 +124,10 @@ static int core(int argc, const char *const *argv)
     return 2;
   }
 
-  // pixels of the facets that are not resident yet (asset_handler, environment.h:84-227)
-  std::vector<std::vector<float>> pixels(args.facet_spec_v.size());
+  // pixels of the facets that are not resident yet (asset_handler, environment.h:84-227): floats, or - PNM / PAM
+  // files - the file's integer samples with the tables that say which float each value becomes
+  std::vector<std::vector<float>> pixels(args.facet_spec_v.size()), colour_tab(args.facet_spec_v.size()), alpha_tab(args.facet_spec_v.size());
+  std::vector<std::vector<uint8_t>> samples(args.facet_spec_v.size());
   for (size_t k = 0; k < args.facet_spec_v.size(); k++) {
     facet_spec &f = args.facet_spec_v[k];
     if (args.solo >= 0 && int(k) != args.solo) continue;
@@ -133,18 +135,28 @@ static int core(int argc, const char *const *argv)
       if (args.verbose) std::printf("asset %s is already resident\n", f.asset_key.c_str());
       continue;
     }
-    int w = 0, h = 0, nch = 0;
-    if (!io::read_image(f.filename, pixels[k], w, h, nch, err)) {
+    f.pixels = nullptr; f.samples = nullptr;
+    int w = 0, h = 0, nch = 0, maxval = 0, sbits = 0;
+    // an integer file goes up as it is and is widened and linearised on the device; whatever read_samples refuses
+    // is left to the float route and to its messages
+    std::string serr;
+    const bool as_samples = io::read_samples(f.filename, samples[k], w, h, nch, maxval, sbits, serr);
+    if (!as_samples && !io::read_image(f.filename, pixels[k], w, h, nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
       return 2;
     }
+    if (args.verbose)
+      std::printf("%s: %s\n", f.filename.c_str(), as_samples ? (sbits == 8 ? "8-bit samples, decoded on the device" : "16-bit samples, decoded on the device")
+                                                             : "float pixels");
     // read_image_data: from the facet's colour space - Csp clause / --input_colour_space, else what the file's
     // format says - to the working one (envutil_basic.h:950-977)
     {
       const std::string csp = f.colour_space.empty() ? io::file_colour_space(f.filename) : f.colour_space;
       if (args.verbose && csp != args.working_colour_space)
         std::printf("converting %s from %s to %s\n", f.filename.c_str(), csp.c_str(), args.working_colour_space.c_str());
-      if (!io::convert_colour(pixels[k].data(), size_t(w) * h, nch, csp, args.working_colour_space, err)) {
+      const bool ok = as_samples ? io::sample_tables(sbits, maxval, csp, args.working_colour_space, colour_tab[k], alpha_tab[k], err)
+                                 : io::convert_colour(pixels[k].data(), size_t(w) * h, nch, csp, args.working_colour_space, err);
+      if (!ok) {
         std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
         return 2;
       }
@@ -157,11 +169,14 @@ static int core(int argc, const char *const *argv)
     }
     // PTO masks and lens crops edit the loaded pixels (environment.h:700-890): the dispatch does that on the
     // device when it loads the facet, from the pixels at the file's own channel count
-    if (!check_facet_pixels(f, pixels[k].size(), nch, err)) {
+    if (!check_facet_pixels(f, as_samples ? samples[k].size() / size_t(sbits / 8) : pixels[k].size(), nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
       return 2;
     }
-    f.pixels = pixels[k].data();
+    if (as_samples) {
+      f.samples = samples[k].data(); f.sample_bits = sbits; f.samples_big_endian = true;
+      f.colour_table = colour_tab[k].data(); f.alpha_table = alpha_tab[k].data();
+    } else f.pixels = pixels[k].data();
   }
 
   // --ray_map FILE: a 3-channel PFM of rays in the facet's frame
