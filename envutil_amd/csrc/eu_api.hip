@@ -1818,14 +1818,15 @@ static int check_views_biatan6(const eu_target *t, const eu_view *views, int nvi
   return EU_OK;
 }
 
-// what this path does not render: EU_ERR_UNSUPPORTED
-static int check_views_supported(const eu_target *t, const eu_view *views, int nviews, const eu_source *src, int *form,
-                                 int *norm_mode)
+// what this path does not render: EU_ERR_UNSUPPORTED. `who` is the entry point the message names; a multi-facet
+// job always normalises (build_multi)
+static int check_views_supported(const char *who, const eu_target *t, const eu_view *views, int nviews,
+                                 eu_source *const *srcs, int nsrc, int *form, int *norm_mode)
 {
-  if (eu::has_translation(src->fct))
-    return fail(EU_ERR_UNSUPPORTED, "render_views: a facet with PTO translation is stepped by the generic stepper: use eu_hip_render");
-  const bool twine = t->ntaps > 0;
-  if (!eu::stepper_form(t->projection, twine, *form, *norm_mode))
+  for (int f = 0; f < nsrc; f++)
+    if (eu::has_translation(srcs[f]->fct))
+      return fail(EU_ERR_UNSUPPORTED, std::string(who) + ": a facet with PTO translation is stepped by the generic stepper: use eu_hip_render");
+  if (!eu::stepper_form(t->projection, nsrc > 1 || t->ntaps > 0, *form, *norm_mode))
     return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
   return check_views_biatan6(t, views, nviews);
 }
@@ -1859,123 +1860,37 @@ static int wait_for_view_buffers(hipStream_t st)
   return EU_OK;
 }
 
-static void view_scalar_blocks(const eu_target *t, const eu_view *views, int nviews, const eu_source *src,
+// one block per (view, facet), [view][facet]: basis = rotate(r_cam(view), r_fct(facet)), as build_multi forms it
+static void view_scalar_blocks(const eu_target *t, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
                                std::vector<eu_view_dev> &sc)
 {
-  sc.resize((size_t)nviews);
-  const eu::mat3 r_fct = eu::make_r3(src->fct.roll, src->fct.pitch, src->fct.yaw, true);
+  sc.resize((size_t)nviews * nsrc);
+  std::vector<eu::mat3> r_fct((size_t)nsrc);
+  for (int f = 0; f < nsrc; f++) r_fct[f] = eu::make_r3(srcs[f]->fct.roll, srcs[f]->fct.pitch, srcs[f]->fct.yaw, true);
   for (int k = 0; k < nviews; k++) {
     const eu_view &v = views[k];
-    const eu::mat3 basis = eu::rotate(eu::make_r3(v.roll, v.pitch, v.yaw, false), r_fct);
-    eu::view_scalars(t->width, t->height, v.x0, v.x1, v.y0, v.y1, basis, sc[(size_t)k]);
+    const eu::mat3 r_cam = eu::make_r3(v.roll, v.pitch, v.yaw, false);
+    for (int f = 0; f < nsrc; f++)
+      eu::view_scalars(t->width, t->height, v.x0, v.x1, v.y0, v.y1, eu::rotate(r_cam, r_fct[f]), sc[(size_t)k * nsrc + f]);
   }
 }
 
-int eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
-                        size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream)
+// One view sequence, of one source or of a multi-facet job (nsrc > 1): the checks behind the entry point's own, in
+// the order both entry points have always made them, the chunk size, the scalar blocks, the buffer waits, the one
+// synchronising upload, and the chunk loop with its device or staged output. The buffers are g.vcol, g.vrow, g.vscal,
+// g.vtaps, g.vstage and, for the facets' parameter blocks of a multi-facet job, g.vsrc; none of build_multi's is touched.
+// `who` is the entry point that messages name where they always have.
+// `job` is what the entry point supplies:
+//   job.prepare(form, norm_mode, sw)   once, when the buffers stand: the kernel parameters of the call
+//   job.launch(nv, vs, sw, st)         renders nv views from the tables in g.vcol / g.vrow to job.p.out, rows
+//                                      job.p.out_stride apart; nonzero: the launch failed
+extern "C++" template <class JOB>
+static int run_view_sequence(const char *who, const eu_target *trg, const eu_view *views, int nviews,
+                             eu_source *const *srcs, int nsrc, float *out, size_t out_row_stride_bytes,
+                             size_t out_view_stride_bytes, int out_on_device, void *stream, JOB &job)
 {
   int rc;
-  if (!trg || !views || !src || !out) return fail(EU_ERR_ARGUMENT, "render_views: null argument");
-  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
-  if ((rc = check_views_target(trg, src))) return rc;
-  for (int k = 0; k < nviews; k++)
-    if (!view_finite(views[k])) return fail(EU_ERR_ARGUMENT, "render_views: a view with a non-finite field");
-  const size_t row_bytes = (size_t)trg->width * trg->nchannels * sizeof(float);
-  if (out_row_stride_bytes % sizeof(float) || out_view_stride_bytes % sizeof(float))
-    return fail(EU_ERR_ARGUMENT, "render_views: strides must be multiples of 4 bytes");
-  if (out_row_stride_bytes < row_bytes) return fail(EU_ERR_ARGUMENT, "render_views: row stride smaller than a row");
-  if (out_view_stride_bytes / (size_t)trg->height < out_row_stride_bytes)
-    return fail(EU_ERR_ARGUMENT, "render_views: view stride smaller than `height` rows");
-  int form = 0, norm_mode = 0;
-  if ((rc = check_views_supported(trg, views, nviews, src, &form, &norm_mode))) return rc;
-  if (nviews == 0) return EU_OK;
-  if ((rc = ensure_init())) return rc;
-  if (!src->dev) return fail(EU_ERR_HANDLE, "render_views: the source has no container");
-  const eu_switches sw = eu_read_switches();
-  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
-
-  const int W = trg->width, H = trg->height;
-  const size_t col_floats = (size_t)6 * W, row_floats = (size_t)H * EU_ROW_FLOATS;
-  const size_t frame_bytes = (size_t)H * row_bytes;
-  int per_chunk = std::min(nviews, eu_views_per_chunk(W, H, sw.views_max_kb));
-  if (!out_on_device) per_chunk = (int)std::min<size_t>((size_t)per_chunk, std::max<size_t>(1, EU_VIEWS_STAGE_BYTES / frame_bytes));
-
-  std::vector<eu_view_dev> sc;
-  std::vector<float> taps;
-  view_scalar_blocks(trg, views, nviews, src, sc);
-  // whatever happens below, nothing of this call may still read the host vectors or write a host `out` when it returns
-  struct drain { hipStream_t a; bool on; ~drain() { if (on) (void)hipStreamSynchronize(a); } } drain_on_exit{ st, true };
-  if ((rc = wait_for_view_buffers(st))) return rc;
-  HIPCHK(g.vcol.reserve(col_floats * per_chunk));
-  HIPCHK(g.vrow.reserve(row_floats * per_chunk));
-  if (!out_on_device) HIPCHK(g.vstage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
-  // the one host synchronisation of the call: every view's scalars, and a new tap table, in flight from host vectors
-  HIPCHK(g.vscal.reserve((size_t)nviews));
-  HIPCHK(hipMemcpyAsync(g.vscal.p, sc.data(), sc.size() * sizeof(eu_view_dev), hipMemcpyHostToDevice, st));
-  if ((rc = upload_view_taps(trg, st, &taps))) return rc;
-  HIPCHK(hipStreamSynchronize(st));
-  drain_on_exit.on = !out_on_device;
-
-  eu_render_params p;
-  memset(&p, 0, sizeof p);
-  p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
-  p.form = form; p.norm_mode = norm_mode;
-  p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps; p.nch = src->nch; p.nch_out = trg->nchannels;
-  p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p;
-  p.src = src->sd;
-  p.direct = 1;
-  const int path = eu_select_view_path(p, sw);
-  for (int c0 = 0; c0 < nviews; c0 += per_chunk) {
-    const int nv = std::min(per_chunk, nviews - c0);
-    if (eu_launch_view_tables(g.vscal.p + c0, nv, trg->projection, W, H, p.twine, g.vcol.p, g.vrow.p, st))
-      return fail(EU_ERR_NO_DEVICE, "render_views: table kernel launch failed");
-    eu_view_strides vs;
-    vs.col = (long long)col_floats; vs.row = (long long)row_floats;
-    char *dst = (char *)out + (size_t)c0 * out_view_stride_bytes;
-    if (out_on_device) {
-      p.out = (float *)dst;
-      p.out_stride = (long long)(out_row_stride_bytes / sizeof(float));
-      vs.out = (long long)(out_view_stride_bytes / sizeof(float));
-    } else {
-      p.out = g.vstage.p;
-      p.out_stride = (long long)(row_bytes / sizeof(float));
-      vs.out = (long long)(frame_bytes / sizeof(float));
-    }
-    if (eu_launch_render_views(&p, &vs, nv, path, &sw, st)) return fail(EU_ERR_NO_DEVICE, "render_views: kernel launch failed");
-    if (!out_on_device)
-      for (int k = 0; k < nv; k++)
-        HIPCHK(hipMemcpy2DAsync(dst + (size_t)k * out_view_stride_bytes, out_row_stride_bytes,
-                                (const char *)g.vstage.p + (size_t)k * frame_bytes, row_bytes, row_bytes, (size_t)H,
-                                hipMemcpyDeviceToHost, st));
-  }
-  if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
-  return EU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// many views of a multi-facet job in one call (include/eu_hip.h, eu_render_views_multi.hip)
-// ---------------------------------------------------------------------------------------------------------
-// What build_multi does per camera on the host - one build_stepper_tables per facet, a pageable upload of the row
-// tables, two synchronisations - is one scalar block per (view, facet) here: the table kernel makes the tables of
-// a chunk of views in one launch, the render kernel has the view on blockIdx.y. The buffers are those of
-// eu_hip_render_views plus the facets' parameter blocks (g.vsrc); none of build_multi's (g.mcol, g.mrow, g.msrc,
-// g.mtaps, g.mplan_key) is touched. EU_HIP_REJ is not applied: the early-miss tables change no bit and were
-// measured slower (build_multi).
-int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
-                              float *out, size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device,
-                              void *stream)
-{
-  int rc;
-  if (!trg || !views || !srcs || !out) return fail(EU_ERR_ARGUMENT, "render_views_multi: null argument");
-  if (nsrc < 1) return fail(EU_ERR_ARGUMENT, "render_views_multi: no source");
-  if (nsrc > EU_VIEWS_MAX_GRID_Y) return fail(EU_ERR_ARGUMENT, "render_views_multi: more than 65535 facets");
-  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
-  for (int f = 0; f < nsrc; f++)
-    if (!srcs[f]) return fail(EU_ERR_HANDLE, "render_views_multi: null source");
-  if (nsrc == 1)
-    return eu_hip_render_views(trg, views, nviews, srcs[0], out, out_row_stride_bytes, out_view_stride_bytes,
-                               out_on_device, stream);
+  const bool multi = nsrc > 1;
   // the target, and the --mask_for channel rule of every facet
   for (int f = 0; f < nsrc; f++)
     if ((rc = check_views_target(trg, srcs[f]))) return rc;
@@ -1990,45 +1905,31 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
   if (out_row_stride_bytes < row_bytes) return fail(EU_ERR_ARGUMENT, "render_views: row stride smaller than a row");
   if (out_view_stride_bytes / (size_t)trg->height < out_row_stride_bytes)
     return fail(EU_ERR_ARGUMENT, "render_views: view stride smaller than `height` rows");
-  for (int f = 0; f < nsrc; f++)
-    if (eu::has_translation(srcs[f]->fct))
-      return fail(EU_ERR_UNSUPPORTED, "render_views_multi: a facet with PTO translation is stepped by the generic stepper: use eu_hip_render");
-  // a multi-facet job always normalises (build_multi)
   int form = 0, norm_mode = 0;
-  if (!eu::stepper_form(trg->projection, true, form, norm_mode))
-    return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
-  if ((rc = check_views_biatan6(trg, views, nviews))) return rc;
+  if ((rc = check_views_supported(who, trg, views, nviews, srcs, nsrc, &form, &norm_mode))) return rc;
   if (nviews == 0) return EU_OK;
   if ((rc = ensure_init())) return rc;
   for (int f = 0; f < nsrc; f++)
-    if (!srcs[f]->dev) return fail(EU_ERR_HANDLE, "render_views_multi: a source has no container");
+    if (!srcs[f]->dev)
+      return fail(EU_ERR_HANDLE, multi ? "render_views_multi: a source has no container" : "render_views: the source has no container");
   const eu_switches sw = eu_read_switches();
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
   struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
 
   const int W = trg->width, H = trg->height;
-  const bool twine = trg->ntaps > 0;
   // one table block per (view, facet): the columns of a view are those of its first block
   const size_t col_floats = (size_t)6 * W * nsrc, row_floats = (size_t)H * EU_ROW_FLOATS * nsrc;
   const size_t frame_bytes = (size_t)H * row_bytes;
   int per_chunk = std::min(nviews, eu_views_per_chunk(W, H, sw.views_max_kb, nsrc));
   if (!out_on_device) per_chunk = (int)std::min<size_t>((size_t)per_chunk, std::max<size_t>(1, EU_VIEWS_STAGE_BYTES / frame_bytes));
 
-  // [view][facet]: basis = rotate(r_cam(view), r_fct(facet)), as build_multi forms it
-  std::vector<eu_view_dev> sc((size_t)nviews * nsrc);
-  {
-    std::vector<eu::mat3> r_fct((size_t)nsrc);
-    for (int f = 0; f < nsrc; f++) r_fct[f] = eu::make_r3(srcs[f]->fct.roll, srcs[f]->fct.pitch, srcs[f]->fct.yaw, true);
-    for (int k = 0; k < nviews; k++) {
-      const eu_view &v = views[k];
-      const eu::mat3 r_cam = eu::make_r3(v.roll, v.pitch, v.yaw, false);
-      for (int f = 0; f < nsrc; f++)
-        eu::view_scalars(W, H, v.x0, v.x1, v.y0, v.y1, eu::rotate(r_cam, r_fct[f]), sc[(size_t)k * nsrc + f]);
-    }
-  }
-  // the facets' evaluator parameters (they can change between calls: always refreshed)
-  std::vector<eu_src_dev> sd((size_t)nsrc);
-  for (int f = 0; f < nsrc; f++) sd[f] = srcs[f]->sd;
+  std::vector<eu_view_dev> sc;
+  view_scalar_blocks(trg, views, nviews, srcs, nsrc, sc);
+  // the facets' evaluator parameters (they can change between calls: always refreshed); one source's travel in
+  // the kernel argument
+  std::vector<eu_src_dev> sd;
+  if (multi)
+    for (int f = 0; f < nsrc; f++) sd.push_back(srcs[f]->sd);
   std::vector<float> taps;
   // whatever happens below, nothing of this call may still read the host vectors or write a host `out` when it returns
   struct drain { hipStream_t a; bool on; ~drain() { if (on) (void)hipStreamSynchronize(a); } } drain_on_exit{ st, true };
@@ -2038,48 +1939,26 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
   if (!out_on_device) HIPCHK(g.vstage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
   // the one host synchronisation of the call: the scalar blocks, the facets, and a new tap table, in flight from host vectors
   HIPCHK(g.vscal.reserve(sc.size()));
-  HIPCHK(g.vsrc.reserve(sd.size()));
+  if (multi) HIPCHK(g.vsrc.reserve(sd.size()));
   HIPCHK(hipMemcpyAsync(g.vscal.p, sc.data(), sc.size() * sizeof(eu_view_dev), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(g.vsrc.p, sd.data(), sd.size() * sizeof(eu_src_dev), hipMemcpyHostToDevice, st));
+  if (multi) HIPCHK(hipMemcpyAsync(g.vsrc.p, sd.data(), sd.size() * sizeof(eu_src_dev), hipMemcpyHostToDevice, st));
   if ((rc = upload_view_taps(trg, st, &taps))) return rc;
   HIPCHK(hipStreamSynchronize(st));
   drain_on_exit.on = !out_on_device;
 
-  eu_multi_params p;
-  memset(&p, 0, sizeof p);
-  p.width = W; p.height = H; p.row_begin = 0; p.row_end = H;
-  p.form = form; p.norm_mode = norm_mode; p.twine = twine; p.ntaps = trg->ntaps;
-  p.nch = trg->nchannels; p.nfct = nsrc; p.plus = (trg->nchannels == 2 || trg->nchannels == 4);
-  p.hdr = trg->synopsis == EU_SYN_HDR_MERGE;
-  {
-    // _hdr_merge_syn ctor (envutil_payload.cc:1346-1376): the first strict minimum / maximum of brighten
-    float lowest = 100000.0f, highest = -1.0f;
-    p.hdr_low = p.hdr_high = -1;
-    for (int f = 0; f < nsrc; f++) {
-      const float b = srcs[f]->sd.brighten;
-      if (b < lowest) { lowest = b; p.hdr_low = f; }
-      if (b > highest) { highest = b; p.hdr_high = f; }
-    }
-  }
-  p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p; p.srcs = g.vsrc.p;
   eu_view_strides vs;
   vs.col = (long long)col_floats; vs.row = (long long)row_floats;
+  vs.out = (long long)((out_on_device ? out_view_stride_bytes : frame_bytes) / sizeof(float));
+  job.prepare(form, norm_mode, sw);
+  job.p.out_stride = (long long)((out_on_device ? out_row_stride_bytes : row_bytes) / sizeof(float));
   for (int c0 = 0; c0 < nviews; c0 += per_chunk) {
     const int nv = std::min(per_chunk, nviews - c0);
-    if (eu_launch_view_tables(g.vscal.p + (size_t)c0 * nsrc, nv * nsrc, trg->projection, W, H, twine, g.vcol.p, g.vrow.p, st))
-      return fail(EU_ERR_NO_DEVICE, "render_views_multi: table kernel launch failed");
+    if (eu_launch_view_tables(g.vscal.p + (size_t)c0 * nsrc, nv * nsrc, trg->projection, W, H, trg->ntaps > 0, g.vcol.p, g.vrow.p, st))
+      return fail(EU_ERR_NO_DEVICE, std::string(who) + ": table kernel launch failed");
     char *dst = (char *)out + (size_t)c0 * out_view_stride_bytes;
-    if (out_on_device) {
-      p.out = (float *)dst;
-      p.out_stride = (long long)(out_row_stride_bytes / sizeof(float));
-      vs.out = (long long)(out_view_stride_bytes / sizeof(float));
-    } else {
-      p.out = g.vstage.p;
-      p.out_stride = (long long)(row_bytes / sizeof(float));
-      vs.out = (long long)(frame_bytes / sizeof(float));
-    }
-    if (eu_launch_render_views_multi(&p, &vs, nv, srcs[0]->degree, st))
-      return fail(EU_ERR_NO_DEVICE, "render_views_multi: kernel launch failed");
+    job.p.out = out_on_device ? (float *)dst : g.vstage.p;
+    if (job.launch(nv, vs, sw, st))
+      return fail(EU_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
     if (!out_on_device)
       for (int k = 0; k < nv; k++)
         HIPCHK(hipMemcpy2DAsync(dst + (size_t)k * out_view_stride_bytes, out_row_stride_bytes,
@@ -2088,6 +1967,87 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
   }
   if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
   return EU_OK;
+}
+
+int eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
+                        size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream)
+{
+  if (!trg || !views || !src || !out) return fail(EU_ERR_ARGUMENT, "render_views: null argument");
+  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
+  struct {
+    const eu_target *trg;
+    const eu_source *src;
+    eu_render_params p;
+    int path;
+    void prepare(int form, int norm_mode, const eu_switches &sw)
+    {
+      memset(&p, 0, sizeof p);
+      p.width = trg->width; p.height = trg->height; p.row_begin = 0; p.row_end = trg->height;
+      p.form = form; p.norm_mode = norm_mode;
+      p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps; p.nch = src->nch; p.nch_out = trg->nchannels;
+      p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p;
+      p.src = src->sd;
+      p.direct = 1;
+      path = eu_select_view_path(p, sw);
+    }
+    int launch(int nv, const eu_view_strides &vs, const eu_switches &sw, hipStream_t st)
+    {
+      return eu_launch_render_views(&p, &vs, nv, path, &sw, st);
+    }
+  } job{ trg, src };
+  return run_view_sequence("render_views", trg, views, nviews, &src, 1, out, out_row_stride_bytes, out_view_stride_bytes,
+                           out_on_device, stream, job);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// many views of a multi-facet job in one call (include/eu_hip.h, eu_render_views_multi.hip)
+// ---------------------------------------------------------------------------------------------------------
+// What build_multi does per camera on the host - one build_stepper_tables per facet, a pageable upload of the row
+// tables, two synchronisations - is one scalar block per (view, facet) here: the table kernel makes the tables of
+// a chunk of views in one launch, the render kernel has the view on blockIdx.y. EU_HIP_REJ is not applied: the
+// early-miss tables change no bit and were measured slower (build_multi).
+int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
+                              float *out, size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device,
+                              void *stream)
+{
+  if (!trg || !views || !srcs || !out) return fail(EU_ERR_ARGUMENT, "render_views_multi: null argument");
+  if (nsrc < 1) return fail(EU_ERR_ARGUMENT, "render_views_multi: no source");
+  if (nsrc > EU_VIEWS_MAX_GRID_Y) return fail(EU_ERR_ARGUMENT, "render_views_multi: more than 65535 facets");
+  if (nviews < 0) return fail(EU_ERR_ARGUMENT, "render_views: negative number of views");
+  for (int f = 0; f < nsrc; f++)
+    if (!srcs[f]) return fail(EU_ERR_HANDLE, "render_views_multi: null source");
+  if (nsrc == 1)
+    return eu_hip_render_views(trg, views, nviews, srcs[0], out, out_row_stride_bytes, out_view_stride_bytes,
+                               out_on_device, stream);
+  struct {
+    const eu_target *trg;
+    eu_source *const *srcs;
+    int nsrc;
+    eu_multi_params p;
+    void prepare(int form, int norm_mode, const eu_switches &)
+    {
+      memset(&p, 0, sizeof p);
+      p.width = trg->width; p.height = trg->height; p.row_begin = 0; p.row_end = trg->height;
+      p.form = form; p.norm_mode = norm_mode; p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps;
+      p.nch = trg->nchannels; p.nfct = nsrc; p.plus = (trg->nchannels == 2 || trg->nchannels == 4);
+      p.hdr = trg->synopsis == EU_SYN_HDR_MERGE;
+      // _hdr_merge_syn ctor (envutil_payload.cc:1346-1376): the first strict minimum / maximum of brighten
+      float lowest = 100000.0f, highest = -1.0f;
+      p.hdr_low = p.hdr_high = -1;
+      for (int f = 0; f < nsrc; f++) {
+        const float b = srcs[f]->sd.brighten;
+        if (b < lowest) { lowest = b; p.hdr_low = f; }
+        if (b > highest) { highest = b; p.hdr_high = f; }
+      }
+      p.col = g.vcol.p; p.row = g.vrow.p; p.taps = g.vtaps.p; p.srcs = g.vsrc.p;
+    }
+    int launch(int nv, const eu_view_strides &vs, const eu_switches &, hipStream_t st)
+    {
+      return eu_launch_render_views_multi(&p, &vs, nv, srcs[0]->degree, st);
+    }
+  } job{ trg, srcs, nsrc };
+  return run_view_sequence("render_views_multi", trg, views, nviews, srcs, nsrc, out, out_row_stride_bytes,
+                           out_view_stride_bytes, out_on_device, stream, job);
 }
 
 // For tests: the tables the table kernel writes for one view, and eu::build_stepper_tables for the same view
@@ -2100,7 +2060,7 @@ int eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src
   if ((rc = check_views_target(trg, src))) return rc;
   if (!view_finite(*view)) return fail(EU_ERR_ARGUMENT, "view_tables: a view with a non-finite field");
   int form = 0, norm_mode = 0;
-  if ((rc = check_views_supported(trg, view, 1, src, &form, &norm_mode))) return rc;
+  if ((rc = check_views_supported("render_views", trg, view, 1, &src, 1, &form, &norm_mode))) return rc;
   if ((rc = ensure_init())) return rc;
   if (!src->dev) return fail(EU_ERR_HANDLE, "view_tables: the source has no container");
   const int W = trg->width, H = trg->height;
@@ -2119,7 +2079,7 @@ int eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src
     memcpy(row_host_built, tb.row.data(), row_floats * sizeof(float));
   }
   std::vector<eu_view_dev> sc;
-  view_scalar_blocks(trg, view, 1, src, sc);
+  view_scalar_blocks(trg, view, 1, &src, 1, sc);
   if ((rc = wait_for_view_buffers(g.stream))) return rc;
   struct note_stream { ~note_stream() { g.last_user = nullptr; } } note_on_exit;
   HIPCHK(g.vcol.reserve(col_floats));

@@ -517,5 +517,41 @@ __device__ __forceinline__ void eu_synopsis_hdr(const eu_multi_params &p, const 
 #endif
 #define EU_MULTI_OCC __attribute__((amdgpu_waves_per_eu(EU_MULTI_WAVES, EU_MULTI_WAVES)))
 
+// The instantiation of a job, for both launchers: launch.go<DEG, HDR, GEN, BIG>(bytes of dynamic LDS) starts
+// the launcher's own kernel (the view form has no generic stepper and maps GEN onto the one it has).
+template <bool PLUS, class L>
+static int eu_multi_ladder(const eu_multi_params &p, int degree, const L &launch)
+{
+  if (PLUS && !p.hdr && p.nfct > EU_MULTI_MAXF) {
+    // the one instantiation serves jobs with and without generic-stepper facets
+    if constexpr (PLUS) launch.template go<-1, false, true, true>(0);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  // alpha compositing keeps z (and, for up to EU_MULTI_KEEP facets, the source coordinate) of every facet per
+  // thread in LDS
+  const size_t lds = PLUS && !p.hdr ? (size_t)(p.nfct <= EU_MULTI_KEEP ? 3 : 1) * p.nfct * 256 * sizeof(float) : 0;
+  if (p.gen) {
+    if (p.hdr) launch.template go<-1, true, true, false>(lds);
+    else launch.template go<-1, false, true, false>(lds);
+  } else if (p.hdr) {
+    switch (degree) {
+      case 0: launch.template go<0, true, false, false>(lds); break;
+      case 1: launch.template go<1, true, false, false>(lds); break;
+      case 2: launch.template go<2, true, false, false>(lds); break;
+      case 3: launch.template go<3, true, false, false>(lds); break;
+      default: launch.template go<-1, true, false, false>(lds); break;
+    }
+  } else {
+    switch (degree) {
+      case 0: launch.template go<0, false, false, false>(lds); break;
+      case 1: launch.template go<1, false, false, false>(lds); break;
+      case 2: launch.template go<2, false, false, false>(lds); break;
+      case 3: launch.template go<3, false, false, false>(lds); break;
+      default: launch.template go<-1, false, false, false>(lds); break;
+    }
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 #endif  // EU_MULTI_NCH
 #endif

@@ -326,6 +326,46 @@ __device__ __forceinline__ void eu_eval2(const eu_src_dev &s, eu_f2 sx, eu_f2 sy
   }
 }
 
+// The packed pixel path, two pixels per lane: from the centre rays r00 to pxa, pxb. The one copy behind
+// eu_render2_kernel, eu_views2_kernel and eu_rays2_kernel.
+//   p           eu_render_params or eu_rays_params, whole: src, taps, ntaps
+//   neighbours  (r10, r01) of a twined job (deriv_stepper, stepper.h:1591-1715), from tables or registers
+//   guard       (hit, sx, sy) behind eu_coord2: the ray form's finiteness test and miss mask; empty otherwise
+template <int NCH, int DEG, int PRJ, bool TWINE, class P, class NB, class GUARD>
+__device__ __forceinline__ void eu_pixels2(const P &p, const eu_ray2 &r00, const NB &neighbours, const GUARD &guard,
+                                           const float *atab, float *pxa, float *pxb)
+{
+  const eu_src_dev &s = p.src;
+  if constexpr (!TWINE) {
+    eu_f2 sx, sy;
+    eu_i2 hit = eu_coord2<PRJ>(s, r00, sx, sy, atab);
+    guard(hit, sx, sy);
+    eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
+  } else {
+    // twine_t::eval (twining.h:128-263), differencing branch
+    eu_ray2 r10, r01;
+    neighbours(r10, r01);
+    const eu_f2 dxx = r10.x - r00.x, dxy = r10.y - r00.y, dxz = r10.z - r00.z;
+    const eu_f2 dyx = r01.x - r00.x, dyy = r01.y - r00.y, dyz = r01.z - r00.z;
+#pragma unroll
+    for (int c = 0; c < NCH; c++) { pxa[c] = 0.0f; pxb[c] = 0.0f; }
+    eu_cptr taps = (eu_cptr)p.taps;
+    for (int k = 0; k < p.ntaps; k++) {
+      const float cx = taps[3 * k], cy = taps[3 * k + 1], cw = taps[3 * k + 2];
+      eu_ray2 rk;
+      rk.x = r00.x + cx * dxx + cy * dyx;
+      rk.y = r00.y + cx * dxy + cy * dyy;
+      rk.z = r00.z + cx * dxz + cy * dyz;
+      eu_f2 sx, sy;
+      eu_i2 hit = eu_coord2<PRJ>(s, rk, sx, sy, atab);
+      guard(hit, sx, sy);
+      float qa[NCH], qb[NCH];
+      eu_eval2<NCH, DEG>(s, sx, sy, hit, qa, qb);
+#pragma unroll
+      for (int c = 0; c < NCH; c++) { pxa[c] = pxa[c] + cw * qa[c]; pxb[c] = pxb[c] + cw * qb[c]; }
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------
 // The same two stages without any scalar fallback (eu_render4.hip, staged kernel): lanes

@@ -79,55 +79,11 @@ __global__ __launch_bounds__(256) void eu_render_kernel(const eu_render_params p
     return;
   }
 
-  if (p.nch_out != NCH) {
-    // channel adaption (repix_t): the source has NCH channels, the target nch_out
-    const int on = p.nch_out;
-    float q4[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    if constexpr (!TWINE) {
-      eu_environment_repix<NCH, DEG>(p.src, on, rx, ry, rz, acc);
-    } else {
-      const float *col2 = p.col + 2 * p.width, *col3 = p.col + 3 * p.width;
-      float ax, ay, az, bx, by, bz;
-      eu_stepper<GEN>(p, col2, col3, rowt, x, ax, ay, az);
-      eu_stepper<GEN>(p, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);
-      float dxx = ax - rx, dxy = ay - ry, dxz = az - rz;
-      float dyx = bx - rx, dyy = by - ry, dyz = bz - rz;
-      for (int k = 0; k < p.ntaps; k++) {
-        float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-        eu_environment_repix<NCH, DEG>(p.src, on, rx + cx * dxx + cy * dyx, ry + cx * dxy + cy * dyy,
-                                       rz + cx * dxz + cy * dyz, q4);
-        for (int c = 0; c < on; c++) acc[c] = acc[c] + cw * q4[c];
-      }
-    }
-    float *o4 = dst + (long long)x * on;
-    for (int c = 0; c < on; c++) o4[c] = acc[c];
-    return;
-  }
-  float px[NCH];
-  if constexpr (!TWINE) {
-    eu_environment<NCH, DEG>(p.src, rx, ry, rz, px);
-  } else {
-    // deriv_stepper (stepper.h:1591-1715) + twine_t::eval (twining.h:128-263)
-    const float *col2 = p.col + 2 * p.width, *col3 = p.col + 3 * p.width;
-    float ax, ay, az, bx, by, bz;
-    eu_stepper<GEN>(p, col2, col3, rowt, x, ax, ay, az);          // r10: x-biased
-    eu_stepper<GEN>(p, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);      // r01: y-biased
-    float dxx = ax - rx, dxy = ay - ry, dxz = az - rz;
-    float dyx = bx - rx, dyy = by - ry, dyz = bz - rz;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) px[c] = 0.0f;
-    for (int k = 0; k < p.ntaps; k++) {
-      float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-      float kx = rx + cx * dxx + cy * dyx;
-      float ky = ry + cx * dxy + cy * dyy;
-      float kz = rz + cx * dxz + cy * dyz;
-      float q[NCH];
-      eu_environment<NCH, DEG>(p.src, kx, ky, kz, q);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) px[c] = px[c] + cw * q[c];
-    }
-  }
-  eu_put<NCH>(dst, x, px);
+  eu_pixel<NCH, DEG, TWINE>(p, eu_env_act(), rx, ry, rz,
+      [&](float &ax, float &ay, float &az, float &bx, float &by, float &bz) __attribute__((always_inline)) {
+        eu_stepper<GEN>(p, p.col + 2 * p.width, p.col + 3 * p.width, rowt, x, ax, ay, az);   // r10: x-biased
+        eu_stepper<GEN>(p, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);                // r01: y-biased
+      }, dst, x);
 }
 
 // ---------------------------------------------------------------------------

@@ -43,40 +43,17 @@ __global__ __launch_bounds__(256) EU2_OCC void eu_render2_kernel(const eu_render
   if (xa >= p.width) return;
   const bool vb = xb < p.width;
   const int xbc = vb ? xb : xa;
-  const eu_src_dev &s = p.src;
 
   eu_cptr rowt = (eu_cptr)(p.row + (long long)eu_frame_row(y, p.band_shift, p.band_count, p.band_index) * EU_ROW_FLOATS);
   const eu_ray2 r00 = eu_rays2(p.form, p.norm_mode, rowt, p.col, p.col + p.width, xa, xbc);
 
   float pxa[NCH], pxb[NCH];
-  if constexpr (!TWINE) {
-    eu_f2 sx, sy;
-    const eu_i2 hit = eu_coord2<PRJ>(s, r00, sx, sy, atab);
-    eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
-  } else {
-    // deriv_stepper (stepper.h:1591-1715) + twine_t::eval (twining.h:128-263)
-    const eu_ray2 r10 = eu_rays2(p.form, p.norm_mode, rowt, p.col + 2 * p.width,
-                                 p.col + 3 * p.width, xa, xbc);
-    const eu_ray2 r01 = eu_rays2(p.form, p.norm_mode, rowt + EU_ROW_VARIANT, p.col, p.col + p.width, xa, xbc);
-    const eu_f2 dxx = r10.x - r00.x, dxy = r10.y - r00.y, dxz = r10.z - r00.z;
-    const eu_f2 dyx = r01.x - r00.x, dyy = r01.y - r00.y, dyz = r01.z - r00.z;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) { pxa[c] = 0.0f; pxb[c] = 0.0f; }
-    eu_cptr taps = (eu_cptr)p.taps;
-    for (int k = 0; k < p.ntaps; k++) {
-      const float cx = taps[3 * k], cy = taps[3 * k + 1], cw = taps[3 * k + 2];
-      eu_ray2 rk;
-      rk.x = r00.x + cx * dxx + cy * dyx;
-      rk.y = r00.y + cx * dxy + cy * dyy;
-      rk.z = r00.z + cx * dxz + cy * dyz;
-      eu_f2 sx, sy;
-      const eu_i2 hit = eu_coord2<PRJ>(s, rk, sx, sy, atab);
-      float qa[NCH], qb[NCH];
-      eu_eval2<NCH, DEG>(s, sx, sy, hit, qa, qb);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) { pxa[c] = pxa[c] + cw * qa[c]; pxb[c] = pxb[c] + cw * qb[c]; }
-    }
-  }
+  eu_pixels2<NCH, DEG, PRJ, TWINE>(p, r00,
+      [&](eu_ray2 &r10, eu_ray2 &r01) __attribute__((always_inline)) {
+        r10 = eu_rays2(p.form, p.norm_mode, rowt, p.col + 2 * p.width, p.col + 3 * p.width, xa, xbc);
+        r01 = eu_rays2(p.form, p.norm_mode, rowt + EU_ROW_VARIANT, p.col, p.col + p.width, xa, xbc);
+      },
+      [](eu_i2 &, eu_f2, eu_f2) __attribute__((always_inline)) {}, atab, pxa, pxb);
 
   float *o = p.out + (long long)(y - p.row_begin) * p.out_stride;
   eu_put<NCH>(o, xa, pxa);

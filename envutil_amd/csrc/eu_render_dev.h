@@ -761,4 +761,82 @@ __device__ __forceinline__ void eu_stepper(const eu_render_params &p, const floa
   }
 }
 
+// ---------------------------------------------------------------------------
+// the general pixel path, one pixel per lane: from the centre ray to the stored pixel. The one copy behind
+// eu_render_kernel, eu_views_kernel and eu_rays_kernel.
+//   p           eu_render_params or eu_rays_params, whole: src, nch_out, taps, ntaps
+//   act         environment::eval: eu_env_act below, or the ray form's guarded one (eu_render_rays.hip).
+//               act.miss: the lane stores zeros (constant false where there is no such lane)
+//   neighbours  (ax, ay, az, bx, by, bz): r10 and r01 of a twined job (deriv_stepper, stepper.h:1591-1715),
+//               from stepper tables or from registers; called once, in front of the branch on nch_out
+// ---------------------------------------------------------------------------
+
+struct eu_env_act {
+  static constexpr bool miss = false;
+  template <int NCH, int DEG>
+  __device__ __forceinline__ void eval(const eu_src_dev &s, float rx, float ry, float rz, float *px) const
+  {
+    eu_environment<NCH, DEG>(s, rx, ry, rz, px);
+  }
+  template <int NCH, int DEG>
+  __device__ __forceinline__ void repix(const eu_src_dev &s, int out_n, float rx, float ry, float rz, float *px) const
+  {
+    eu_environment_repix<NCH, DEG>(s, out_n, rx, ry, rz, px);
+  }
+};
+
+template <int NCH, int DEG, bool TWINE, class P, class ACT, class NB>
+__device__ __forceinline__ void eu_pixel(const P &p, const ACT &act, float rx, float ry, float rz,
+                                         const NB &neighbours, float *dst, int x)
+{
+  // twine_t::eval (twining.h:128-263), differencing branch
+  float dxx = 0.0f, dxy = 0.0f, dxz = 0.0f, dyx = 0.0f, dyy = 0.0f, dyz = 0.0f;
+  if constexpr (TWINE) {
+    float ax, ay, az, bx, by, bz;
+    neighbours(ax, ay, az, bx, by, bz);
+    dxx = ax - rx; dxy = ay - ry; dxz = az - rz;
+    dyx = bx - rx; dyy = by - ry; dyz = bz - rz;
+  }
+  if (p.nch_out != NCH) {
+    // channel adaption (repix_t): the source has NCH channels, the target nch_out
+    const int on = p.nch_out;
+    float q4[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    if constexpr (!TWINE) {
+      act.template repix<NCH, DEG>(p.src, on, rx, ry, rz, acc);
+    } else {
+      for (int k = 0; k < p.ntaps; k++) {
+        float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
+        act.template repix<NCH, DEG>(p.src, on, rx + cx * dxx + cy * dyx, ry + cx * dxy + cy * dyy,
+                                     rz + cx * dxz + cy * dyz, q4);
+        for (int c = 0; c < on; c++) acc[c] = acc[c] + cw * q4[c];
+      }
+    }
+    float *o4 = dst + (long long)x * on;
+    for (int c = 0; c < on; c++) o4[c] = act.miss ? 0.0f : acc[c];
+    return;
+  }
+  float px[NCH];
+  if constexpr (!TWINE) {
+    act.template eval<NCH, DEG>(p.src, rx, ry, rz, px);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NCH; c++) px[c] = 0.0f;
+    for (int k = 0; k < p.ntaps; k++) {
+      float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
+      float kx = rx + cx * dxx + cy * dyx;
+      float ky = ry + cx * dxy + cy * dyy;
+      float kz = rz + cx * dxz + cy * dyz;
+      float q[NCH];
+      act.template eval<NCH, DEG>(p.src, kx, ky, kz, q);
+#pragma unroll
+      for (int c = 0; c < NCH; c++) px[c] = px[c] + cw * q[c];
+    }
+    // a missed lane was no hit at every evaluation: the sum of the taps' zeros, whatever the weights. The
+    // select stays behind the loop (register notes)
+#pragma unroll
+    for (int c = 0; c < NCH; c++) px[c] = act.miss ? 0.0f : px[c];
+  }
+  eu_put<NCH>(dst, x, px);
+}
+
 #endif

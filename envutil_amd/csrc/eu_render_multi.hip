@@ -34,7 +34,7 @@ __device__ unsigned long long eu_multi_stamp_acc[1024 * 4];      // sharded by w
 // GEN: some facet of the job is stepped by generic_stepper (translation, --single); only the run-time-degree
 // variants are instantiated with it
 // BIG: alpha compositing of more than 64 facets (eu_synopsis_big)
-template <int NCH, int DEG, bool PLUS, bool HDR = false, bool GEN = false, bool BIG = false>
+template <int NCH, int DEG, bool PLUS, bool HDR, bool GEN, bool BIG>
 __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const eu_multi_params p)
 {
   extern __shared__ float eu_dyn_lds[];
@@ -77,43 +77,16 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
 }
 
 template <int NCH, bool PLUS>
-static int launch_multi_n(const eu_multi_params &p, int degree, hipStream_t st)
-{
-  dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS)), block(256);
-  // alpha compositing keeps z (and, for up to EU_MULTI_KEEP facets, the source
-  // coordinate) of every facet per thread in LDS
-  if (PLUS && !p.hdr && p.nfct > EU_MULTI_MAXF) {
-    if constexpr (PLUS) {
-      eu_multi_params q = p;           // the one instantiation serves jobs with and without generic-stepper facets
-      hipLaunchKernelGGL((eu_render_multi_kernel<NCH, -1, true, false, true, true>), grid, block, 0, st, q);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+struct launch_multi {
+  const eu_multi_params &p;
+  hipStream_t st;
+  template <int DEG, bool HDR, bool GEN, bool BIG>
+  void go(size_t lds) const
+  {
+    dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS)), block(256);
+    hipLaunchKernelGGL((eu_render_multi_kernel<NCH, DEG, PLUS, HDR, GEN, BIG>), grid, block, lds, st, p);
   }
-  const size_t lds = PLUS && !p.hdr ? (size_t)(p.nfct <= EU_MULTI_KEEP ? 3 : 1) * p.nfct * 256 * sizeof(float) : 0;
-  if (p.gen) {
-    if (p.hdr) hipLaunchKernelGGL((eu_render_multi_kernel<NCH, -1, PLUS, true, true>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((eu_render_multi_kernel<NCH, -1, PLUS, false, true>), grid, block, lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (p.hdr) {
-    switch (degree) {
-      case 0: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 0, PLUS, true>), grid, block, lds, st, p); break;
-      case 1: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 1, PLUS, true>), grid, block, lds, st, p); break;
-      case 2: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 2, PLUS, true>), grid, block, lds, st, p); break;
-      case 3: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 3, PLUS, true>), grid, block, lds, st, p); break;
-      default: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, -1, PLUS, true>), grid, block, lds, st, p); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  switch (degree) {
-    case 0: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 0, PLUS>), grid, block, lds, st, p); break;
-    case 1: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 1, PLUS>), grid, block, lds, st, p); break;
-    case 2: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 2, PLUS>), grid, block, lds, st, p); break;
-    case 3: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, 3, PLUS>), grid, block, lds, st, p); break;
-    default: hipLaunchKernelGGL((eu_render_multi_kernel<NCH, -1, PLUS>), grid, block, lds, st, p); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+};
 
 #endif  // EU_MULTI_NCH
 
@@ -137,7 +110,7 @@ extern "C" int EU_CAT(eu_launch_render_multi_nch, EU_MULTI_NCH)(const eu_multi_p
                                                                void *stream)
 {
   constexpr bool plus = EU_MULTI_NCH == 2 || EU_MULTI_NCH == 4;
-  return launch_multi_n<EU_MULTI_NCH, plus>(*p, degree, (hipStream_t)stream);
+  return eu_multi_ladder<plus>(*p, degree, launch_multi<EU_MULTI_NCH, plus>{ *p, (hipStream_t)stream });
 }
 #else
 extern "C" int eu_launch_render_multi(const eu_multi_params *pp, int degree, void *stream)

@@ -1,8 +1,9 @@
 // `act` and `put` without a stepper: the source is evaluated at rays the caller supplies
 // (eu_hip_render_rays). What the render kernels obtain from the stepper tables is here a coalesced read
 // of an array; everything behind it - coordinate stage, gates, b-spline, brighten, channel adaption, the
-// twining loop - is the render kernels' own device code in the render kernels' order, so the rays of a
-// job give that job's frame bit for bit. Compiled with -ffp-contract=off like them.
+// twining loop - is the render kernels' own device code in the render kernels' order (eu_pixel in
+// eu_render_dev.h, eu_pixels2 in eu_packed_dev.h: the one copy of each pixel path), so the rays of a job
+// give that job's frame bit for bit. Compiled with -ffp-contract=off like them.
 //
 //   eu_rays_kernel<NCH, DEG, TWINE>        one ray or ninepack per lane; every mount and degree (DEG -1:
 //                                          run-time degree), channel adaption, --mask_for sources
@@ -85,27 +86,29 @@ __device__ __forceinline__ void eu_forward_if(bool miss, float *in)
 }
 
 // environment::eval (eu_environment / eu_environment_repix) with the coordinate guard of eu_ray_guard.h
-// between its two halves
-template <int NCH, int DEG>
-__device__ __forceinline__ void eu_rays_act(const eu_src_dev &s, bool miss, float rx, float ry, float rz, float *px)
-{
-  float sx, sy;
-  int face;
-  bool hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
-  hit = hit && eu_coord_finite(sx, sy) && !miss;
-  eu_environment_at<NCH, DEG>(s, hit, sx, sy, px);
-}
-
-template <int NCH, int DEG>
-__device__ __forceinline__ void eu_rays_act_repix(const eu_src_dev &s, int out_n, float rx, float ry, float rz,
-                                                  float *px)
-{
-  float sx, sy;
-  int face;
-  bool hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
-  hit = hit && eu_coord_finite(sx, sy);
-  eu_environment_repix_at<NCH, DEG>(s, out_n, hit, sx, sy, px);
-}
+// between its two halves: the act eu_pixel (eu_render_dev.h) takes for the ray form. A missed lane counts
+// as no hit in eval; repix evaluates it as the forward ray, and eu_pixel stores zeros for it
+struct eu_rays_act {
+  bool miss;
+  template <int NCH, int DEG>
+  __device__ __forceinline__ void eval(const eu_src_dev &s, float rx, float ry, float rz, float *px) const
+  {
+    float sx, sy;
+    int face;
+    bool hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    hit = hit && eu_coord_finite(sx, sy) && !miss;
+    eu_environment_at<NCH, DEG>(s, hit, sx, sy, px);
+  }
+  template <int NCH, int DEG>
+  __device__ __forceinline__ void repix(const eu_src_dev &s, int out_n, float rx, float ry, float rz, float *px) const
+  {
+    float sx, sy;
+    int face;
+    bool hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    hit = hit && eu_coord_finite(sx, sy);
+    eu_environment_repix_at<NCH, DEG>(s, out_n, hit, sx, sy, px);
+  }
+};
 
 // ---------------------------------------------------------------------------
 // general form
@@ -141,52 +144,13 @@ __global__ __launch_bounds__(256) void eu_rays_kernel(const eu_rays_params p)
   const int x = x0 + lane;
   float *dst = p.out + (long long)y * p.out_stride;
 
-  if (p.nch_out != NCH) {
-    // channel adaption (repix_t): the source has NCH channels, the output nch_out
-    const int on = p.nch_out;
-    float q4[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    if constexpr (!TWINE) {
-      eu_rays_act_repix<NCH, DEG>(p.src, on, rx, ry, rz, acc);
-    } else {
-      const float dxx = in[3] - rx, dxy = in[4] - ry, dxz = in[5] - rz;
-      const float dyx = in[6] - rx, dyy = in[7] - ry, dyz = in[8] - rz;
-      for (int k = 0; k < p.ntaps; k++) {
-        float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-        eu_rays_act_repix<NCH, DEG>(p.src, on, rx + cx * dxx + cy * dyx, ry + cx * dxy + cy * dyy,
-                                    rz + cx * dxz + cy * dyz, q4);
-        for (int c = 0; c < on; c++) acc[c] = acc[c] + cw * q4[c];
-      }
-    }
-    float *o4 = dst + (long long)x * on;
-    for (int c = 0; c < on; c++) o4[c] = miss ? 0.0f : acc[c];
-    return;
-  }
-  float px[NCH];
-  if constexpr (!TWINE) {
-    eu_rays_act<NCH, DEG>(p.src, miss, rx, ry, rz, px);
-  } else {
-    // twine_t::eval (twining.h:128-263), differencing branch
-    const float dxx = in[3] - rx, dxy = in[4] - ry, dxz = in[5] - rz;
-    const float dyx = in[6] - rx, dyy = in[7] - ry, dyz = in[8] - rz;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) px[c] = 0.0f;
-    for (int k = 0; k < p.ntaps; k++) {
-      float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-      float kx = rx + cx * dxx + cy * dyx;
-      float ky = ry + cx * dxy + cy * dyy;
-      float kz = rz + cx * dxz + cy * dyz;
-      float q[NCH];
-      eu_rays_act<NCH, DEG>(p.src, miss, kx, ky, kz, q);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) px[c] = px[c] + cw * q[c];
-    }
-  }
-  // a miss was no hit at the evaluation: zeros; under twining the sum of the taps' zeros, whatever the weights
-  if constexpr (TWINE) {
-#pragma unroll
-    for (int c = 0; c < NCH; c++) px[c] = miss ? 0.0f : px[c];
-  }
-  eu_put<NCH>(dst, x, px);
+  eu_pixel<NCH, DEG, TWINE>(p, eu_rays_act{ miss }, rx, ry, rz,
+      [&](float &ax, float &ay, float &az, float &bx, float &by, float &bz) __attribute__((always_inline)) {
+        if constexpr (TWINE) {      // the ninepack's r10 and r01
+          ax = in[3]; ay = in[4]; az = in[5];
+          bx = in[6]; by = in[7]; bz = in[8];
+        }
+      }, dst, x);
 }
 
 // ---------------------------------------------------------------------------
@@ -217,7 +181,6 @@ __global__ __launch_bounds__(256) void eu_rays2_kernel(const eu_rays_params p)
   const bool vb = lane + 64 < n;
   const int kb = vb ? lane + 64 : lane;       // a lane without a second ray evaluates its first twice
   const float *src = p.rays + (long long)y * p.ray_stride + (long long)x0 * NIN;
-  const eu_src_dev &s = p.src;
   float a[NIN], b[NIN];
   if constexpr (TWINE) {
     float *slice = pack + wave * 128 * 9;
@@ -240,35 +203,18 @@ __global__ __launch_bounds__(256) void eu_rays2_kernel(const eu_rays_params p)
   r00.x = (eu_f2){ a[0], b[0] }; r00.y = (eu_f2){ a[1], b[1] }; r00.z = (eu_f2){ a[2], b[2] };
 
   float pxa[NCH], pxb[NCH];
-  if constexpr (!TWINE) {
-    eu_f2 sx, sy;
-    eu_i2 hit = eu_coord2<PRJ>(s, r00, sx, sy, atab);
-    hit = hit & eu_coord_finite2(sx, sy);
-    hit.x = miss_a ? 0 : hit.x; hit.y = miss_b ? 0 : hit.y;
-    eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
-  } else {
-    // twine_t::eval (twining.h:128-263), differencing branch
-    const eu_f2 dxx = (eu_f2){ a[3], b[3] } - r00.x, dxy = (eu_f2){ a[4], b[4] } - r00.y, dxz = (eu_f2){ a[5], b[5] } - r00.z;
-    const eu_f2 dyx = (eu_f2){ a[6], b[6] } - r00.x, dyy = (eu_f2){ a[7], b[7] } - r00.y, dyz = (eu_f2){ a[8], b[8] } - r00.z;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) { pxa[c] = 0.0f; pxb[c] = 0.0f; }
-    eu_cptr taps = (eu_cptr)p.taps;
-    for (int k = 0; k < p.ntaps; k++) {
-      const float cx = taps[3 * k], cy = taps[3 * k + 1], cw = taps[3 * k + 2];
-      eu_ray2 rk;
-      rk.x = r00.x + cx * dxx + cy * dyx;
-      rk.y = r00.y + cx * dxy + cy * dyy;
-      rk.z = r00.z + cx * dxz + cy * dyz;
-      eu_f2 sx, sy;
-      eu_i2 hit = eu_coord2<PRJ>(s, rk, sx, sy, atab);
-      hit = hit & eu_coord_finite2(sx, sy);
-      hit.x = miss_a ? 0 : hit.x; hit.y = miss_b ? 0 : hit.y;
-      float qa[NCH], qb[NCH];
-      eu_eval2<NCH, DEG>(s, sx, sy, hit, qa, qb);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) { pxa[c] = pxa[c] + cw * qa[c]; pxb[c] = pxb[c] + cw * qb[c]; }
-    }
-  }
+  eu_pixels2<NCH, DEG, PRJ, TWINE>(p, r00,
+      [&](eu_ray2 &r10, eu_ray2 &r01) __attribute__((always_inline)) {
+        if constexpr (TWINE) {      // the ninepacks' r10 and r01
+          r10.x = (eu_f2){ a[3], b[3] }; r10.y = (eu_f2){ a[4], b[4] }; r10.z = (eu_f2){ a[5], b[5] };
+          r01.x = (eu_f2){ a[6], b[6] }; r01.y = (eu_f2){ a[7], b[7] }; r01.z = (eu_f2){ a[8], b[8] };
+        }
+      },
+      // a missed lane is no hit BEFORE the evaluation (the register notes above eu_forward_if)
+      [&](eu_i2 &hit, eu_f2 sx, eu_f2 sy) __attribute__((always_inline)) {
+        hit = hit & eu_coord_finite2(sx, sy);
+        hit.x = miss_a ? 0 : hit.x; hit.y = miss_b ? 0 : hit.y;
+      }, atab, pxa, pxb);
   if constexpr (TWINE) {          // the sum of the taps' zeros, whatever the weights
 #pragma unroll
     for (int c = 0; c < NCH; c++) { pxa[c] = miss_a ? 0.0f : pxa[c]; pxb[c] = miss_b ? 0.0f : pxb[c]; }

@@ -7,12 +7,14 @@
 //                                           [H][EU_ROW_FLOATS]: the loops of eu::build_stepper_tables
 //                                           (eu_setup_math.h), same operations in the same order, sinf / cosf /
 //                                           tanf through eu_sinf / eu_cosf / eu_tanf (eu_math.h: glibc's bits)
-//   eu_views_kernel<NCH, DEG, TWINE>        one pixel per lane, eu_render_kernel's pixel path
-//   eu_views2_kernel<NCH, DEG, PRJ, TWINE>  two per lane, eu_render2_kernel's pixel path (row strips)
+//   eu_views_kernel<NCH, DEG, TWINE>        one pixel per lane: eu_pixel (eu_render_dev.h), the pixel path
+//                                           eu_render_kernel and eu_rays_kernel run too
+//   eu_views2_kernel<NCH, DEG, PRJ, TWINE>  two per lane in row strips: eu_pixels2 (eu_packed_dev.h), the pixel path
+//                                           of eu_render2_kernel and eu_rays2_kernel
 //
-// The render kernels are kernels of their own that call the device functions the existing kernels call; those
-// kernels' code is untouched. Every workgroup offsets col, row and out by its view and walks its view's tiles
-// with eu_xcd_tile: gridDim.x is eu_xcd_grid(), a multiple of 8, so workgroup (x, y) still runs on XCD x % 8.
+// What the render kernels have of their own is where a view's tables and frame are: every workgroup offsets col,
+// row and out by its view and walks its view's tiles with eu_xcd_tile: gridDim.x is eu_xcd_grid(), a multiple of
+// 8, so workgroup (x, y) still runs on XCD x % 8.
 // Compiled with -ffp-contract=off like every kernel file.
 #include <hip/hip_runtime.h>
 #include "eu_packed_dev.h"
@@ -148,7 +150,7 @@ extern "C" int eu_launch_view_tables(const eu_view_dev *views, int nviews, int p
 }
 
 // ---------------------------------------------------------------------------
-// general form: eu_render_kernel's pixel path (whole frames: no stages, no row bands)
+// general form (whole frames: no stages, no row bands)
 // ---------------------------------------------------------------------------
 
 template <int NCH, int DEG, bool TWINE>
@@ -170,59 +172,15 @@ __global__ __launch_bounds__(256) void eu_views_kernel(const eu_render_params p,
   eu_stepper<false>(p.form, p.norm_mode, col0, col1, rowt, x, rx, ry, rz);
 
   float *dst = p.out + view * vs.out + (long long)y * p.out_stride;
-  if (p.nch_out != NCH) {
-    // channel adaption (repix_t): the source has NCH channels, the target nch_out
-    const int on = p.nch_out;
-    float q4[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    if constexpr (!TWINE) {
-      eu_environment_repix<NCH, DEG>(p.src, on, rx, ry, rz, acc);
-    } else {
-      const float *col2 = col0 + 2 * p.width, *col3 = col0 + 3 * p.width;
-      float ax, ay, az, bx, by, bz;
-      eu_stepper<false>(p.form, p.norm_mode, col2, col3, rowt, x, ax, ay, az);
-      eu_stepper<false>(p.form, p.norm_mode, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);
-      float dxx = ax - rx, dxy = ay - ry, dxz = az - rz;
-      float dyx = bx - rx, dyy = by - ry, dyz = bz - rz;
-      for (int k = 0; k < p.ntaps; k++) {
-        float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-        eu_environment_repix<NCH, DEG>(p.src, on, rx + cx * dxx + cy * dyx, ry + cx * dxy + cy * dyy,
-                                       rz + cx * dxz + cy * dyz, q4);
-        for (int c = 0; c < on; c++) acc[c] = acc[c] + cw * q4[c];
-      }
-    }
-    float *o4 = dst + (long long)x * on;
-    for (int c = 0; c < on; c++) o4[c] = acc[c];
-    return;
-  }
-  float px[NCH];
-  if constexpr (!TWINE) {
-    eu_environment<NCH, DEG>(p.src, rx, ry, rz, px);
-  } else {
-    // deriv_stepper (stepper.h:1591-1715) + twine_t::eval (twining.h:128-263)
-    const float *col2 = col0 + 2 * p.width, *col3 = col0 + 3 * p.width;
-    float ax, ay, az, bx, by, bz;
-    eu_stepper<false>(p.form, p.norm_mode, col2, col3, rowt, x, ax, ay, az);                    // r10: x-biased
-    eu_stepper<false>(p.form, p.norm_mode, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);   // r01: y-biased
-    float dxx = ax - rx, dxy = ay - ry, dxz = az - rz;
-    float dyx = bx - rx, dyy = by - ry, dyz = bz - rz;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) px[c] = 0.0f;
-    for (int k = 0; k < p.ntaps; k++) {
-      float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
-      float kx = rx + cx * dxx + cy * dyx;
-      float ky = ry + cx * dxy + cy * dyy;
-      float kz = rz + cx * dxz + cy * dyz;
-      float q[NCH];
-      eu_environment<NCH, DEG>(p.src, kx, ky, kz, q);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) px[c] = px[c] + cw * q[c];
-    }
-  }
-  eu_put<NCH>(dst, x, px);
+  eu_pixel<NCH, DEG, TWINE>(p, eu_env_act(), rx, ry, rz,
+      [&](float &ax, float &ay, float &az, float &bx, float &by, float &bz) __attribute__((always_inline)) {
+        eu_stepper<false>(p.form, p.norm_mode, col0 + 2 * p.width, col0 + 3 * p.width, rowt, x, ax, ay, az);
+        eu_stepper<false>(p.form, p.norm_mode, col0, col1, rowt + EU_ROW_VARIANT, x, bx, by, bz);
+      }, dst, x);
 }
 
 // ---------------------------------------------------------------------------
-// packed form: eu_render2_kernel's pixel path
+// packed form
 // ---------------------------------------------------------------------------
 
 template <int NCH, int DEG, int PRJ, bool TWINE>
@@ -245,7 +203,6 @@ __global__ __launch_bounds__(256) void eu_views2_kernel(const eu_render_params p
   if (xa >= p.width) return;
   const bool vb = xb < p.width;
   const int xbc = vb ? xb : xa;
-  const eu_src_dev &s = p.src;
 
   const long long view = blockIdx.y;
   const float *col = p.col + view * vs.col;
@@ -253,33 +210,12 @@ __global__ __launch_bounds__(256) void eu_views2_kernel(const eu_render_params p
   const eu_ray2 r00 = eu_rays2(p.form, p.norm_mode, rowt, col, col + p.width, xa, xbc);
 
   float pxa[NCH], pxb[NCH];
-  if constexpr (!TWINE) {
-    eu_f2 sx, sy;
-    const eu_i2 hit = eu_coord2<PRJ>(s, r00, sx, sy, atab);
-    eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
-  } else {
-    // deriv_stepper (stepper.h:1591-1715) + twine_t::eval (twining.h:128-263)
-    const eu_ray2 r10 = eu_rays2(p.form, p.norm_mode, rowt, col + 2 * p.width, col + 3 * p.width, xa, xbc);
-    const eu_ray2 r01 = eu_rays2(p.form, p.norm_mode, rowt + EU_ROW_VARIANT, col, col + p.width, xa, xbc);
-    const eu_f2 dxx = r10.x - r00.x, dxy = r10.y - r00.y, dxz = r10.z - r00.z;
-    const eu_f2 dyx = r01.x - r00.x, dyy = r01.y - r00.y, dyz = r01.z - r00.z;
-#pragma unroll
-    for (int c = 0; c < NCH; c++) { pxa[c] = 0.0f; pxb[c] = 0.0f; }
-    eu_cptr taps = (eu_cptr)p.taps;
-    for (int k = 0; k < p.ntaps; k++) {
-      const float cx = taps[3 * k], cy = taps[3 * k + 1], cw = taps[3 * k + 2];
-      eu_ray2 rk;
-      rk.x = r00.x + cx * dxx + cy * dyx;
-      rk.y = r00.y + cx * dxy + cy * dyy;
-      rk.z = r00.z + cx * dxz + cy * dyz;
-      eu_f2 sx, sy;
-      const eu_i2 hit = eu_coord2<PRJ>(s, rk, sx, sy, atab);
-      float qa[NCH], qb[NCH];
-      eu_eval2<NCH, DEG>(s, sx, sy, hit, qa, qb);
-#pragma unroll
-      for (int c = 0; c < NCH; c++) { pxa[c] = pxa[c] + cw * qa[c]; pxb[c] = pxb[c] + cw * qb[c]; }
-    }
-  }
+  eu_pixels2<NCH, DEG, PRJ, TWINE>(p, r00,
+      [&](eu_ray2 &r10, eu_ray2 &r01) __attribute__((always_inline)) {
+        r10 = eu_rays2(p.form, p.norm_mode, rowt, col + 2 * p.width, col + 3 * p.width, xa, xbc);
+        r01 = eu_rays2(p.form, p.norm_mode, rowt + EU_ROW_VARIANT, col, col + p.width, xa, xbc);
+      },
+      [](eu_i2 &, eu_f2, eu_f2) __attribute__((always_inline)) {}, atab, pxa, pxb);
 
   float *o = p.out + view * vs.out + (long long)y * p.out_stride;
   eu_put<NCH>(o, xa, pxa);

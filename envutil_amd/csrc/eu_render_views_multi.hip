@@ -10,6 +10,14 @@
 // It calls the device functions of eu_multi_dev.h with GEN = false (a facet with translation is refused: it is
 // stepped by the generic stepper, whose tf3d_t is host work per view) and without early-miss tables. The
 // strides are kernel arguments and blockIdx.y is wave-uniform, so the three offsets are scalar arithmetic.
+// The instantiation of a job is chosen by eu_multi_ladder (eu_multi_dev.h), as for eu_render_multi_kernel.
+//
+// Why the body is written out here and in eu_render_multi.hip, and not one device function called by both: every
+// kernel of the two families is held at 96 registers by EU_MULTI_OCC and spills, and where the allocator puts
+// the spills moved with the body in a function. With the parameter block taken by reference, three
+// instantiations of eu_render_multi_kernel and four of this kernel had 16-32 bytes more scratch per lane; by
+// value eu_views_multi_kernel<3, 2, hdr> had 260 bytes for 244, and the 64-view jobs of tools/views_multi_time.py
+// ran 2 % (RGB) and 1 % (RGBA) slower in each of three runs. A change to the body is made in both files.
 // gridDim.x is eu_xcd_grid(), a multiple of 8: workgroup (x, y) still runs on XCD x % 8.
 // The Makefile compiles this file once per channel count (EU_MULTI_NCH), like eu_render_multi.hip, and once
 // without for the dispatcher. Compiled with -ffp-contract=off like every kernel file.
@@ -22,7 +30,7 @@
 
 #ifdef EU_MULTI_NCH
 
-template <int NCH, int DEG, bool PLUS, bool HDR = false, bool BIG = false>
+template <int NCH, int DEG, bool PLUS, bool HDR, bool BIG>
 __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const eu_multi_params p0, const eu_view_strides vs)
 {
   extern __shared__ float eu_dyn_lds[];
@@ -70,45 +78,27 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
   eu_put<NCH>(p.out + (long long)(px.y - p.row_begin) * p.out_stride, px.x, out);
 }
 
-// the instantiation launch_multi_n (eu_render_multi.hip) chooses for the job, without the generic stepper's
+// GEN falls away: the one kernel of each (DEG, HDR, BIG)
 template <int NCH, bool PLUS>
-static int launch_views_multi_n(const eu_multi_params &p, const eu_view_strides &vs, int nviews, int degree, hipStream_t st)
-{
-  dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS), (unsigned)nviews), block(256);
-  if (PLUS && !p.hdr && p.nfct > EU_MULTI_MAXF) {
-    if constexpr (PLUS)
-      hipLaunchKernelGGL((eu_views_multi_kernel<NCH, -1, true, false, true>), grid, block, 0, st, p, vs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+struct launch_views_multi {
+  const eu_multi_params &p;
+  const eu_view_strides &vs;
+  int nviews;
+  hipStream_t st;
+  template <int DEG, bool HDR, bool GEN, bool BIG>
+  void go(size_t lds) const
+  {
+    dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS), (unsigned)nviews), block(256);
+    hipLaunchKernelGGL((eu_views_multi_kernel<NCH, DEG, PLUS, HDR, BIG>), grid, block, lds, st, p, vs);
   }
-  // alpha compositing keeps z (and, for up to EU_MULTI_KEEP facets, the source coordinate) of every facet per
-  // thread in LDS
-  const size_t lds = PLUS && !p.hdr ? (size_t)(p.nfct <= EU_MULTI_KEEP ? 3 : 1) * p.nfct * 256 * sizeof(float) : 0;
-  if (p.hdr) {
-    switch (degree) {
-      case 0: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 0, PLUS, true>), grid, block, lds, st, p, vs); break;
-      case 1: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 1, PLUS, true>), grid, block, lds, st, p, vs); break;
-      case 2: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 2, PLUS, true>), grid, block, lds, st, p, vs); break;
-      case 3: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 3, PLUS, true>), grid, block, lds, st, p, vs); break;
-      default: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, -1, PLUS, true>), grid, block, lds, st, p, vs); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  switch (degree) {
-    case 0: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 0, PLUS>), grid, block, lds, st, p, vs); break;
-    case 1: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 1, PLUS>), grid, block, lds, st, p, vs); break;
-    case 2: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 2, PLUS>), grid, block, lds, st, p, vs); break;
-    case 3: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, 3, PLUS>), grid, block, lds, st, p, vs); break;
-    default: hipLaunchKernelGGL((eu_views_multi_kernel<NCH, -1, PLUS>), grid, block, lds, st, p, vs); break;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+};
 
 // this translation unit carries the kernels of ONE channel count
 extern "C" int EU_CAT(eu_launch_render_views_multi_nch, EU_MULTI_NCH)(const eu_multi_params *p, const eu_view_strides *vs,
                                                                      int nviews, int degree, void *stream)
 {
   constexpr bool plus = EU_MULTI_NCH == 2 || EU_MULTI_NCH == 4;
-  return launch_views_multi_n<EU_MULTI_NCH, plus>(*p, *vs, nviews, degree, (hipStream_t)stream);
+  return eu_multi_ladder<plus>(*p, degree, launch_views_multi<EU_MULTI_NCH, plus>{ *p, *vs, nviews, (hipStream_t)stream });
 }
 
 #else

@@ -109,6 +109,16 @@ def test_seventy_two_facets(nch):
     check_views(rect24(nch) * 3, (ea.SPHERICAL, 96, 48, 360.0), f"72 facets, {nch} channels", spline_degree=1)
 
 
+def test_seventy_two_facets_twined():
+    """eu_synopsis_big under the twine loop: 72 RGBA facets of 16 x 16 (four sets of six, every facet three times
+    over), a 65 x 5 target - one live lane in the second tile - twine 2, two views"""
+    gs = []
+    for k in range(4):
+        gs += facet_set(euo.RECTILINEAR, 16, 16, 70.0 + 5 * k, 4, 1, seed=40 + k)[1]
+    check_views(gs * 3, (ea.SPHERICAL, 65, 5, 360.0), "72 facets twined", views=views_of(360.0)[:2], spline_degree=1,
+                twine=2)
+
+
 # ---- targets ----------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("nch", [3, 4])

@@ -84,6 +84,17 @@ def test_single_translated_facet_bit_exact(tprj, tw, th, hf, twine):
 
 
 @pytest.mark.gpu
+def test_translated_facet_twined_with_channel_adaption():
+    """the general kernel with the generic stepper, twined, through its channel adaption branch: a 4-channel
+    facet of 64 x 32, degree 1, on a 2-channel lat/lon target of 130 x 9 (a second 64-pixel tile with two lanes)"""
+    o, g = facet(euo.RECTILINEAR, 64, 32, 70.0, 4, 1, TR, True, yaw=12, pitch=-5, roll=3, brighten=1.2)
+    a = ea.arguments(ea.SPHERICAL, 130, 9, 360.0, yaw=20, pitch=7, roll=-4, spline_degree=1, twine=2)
+    ref = jobs.oracle_render(a, o, nch=2)
+    assert ref.shape == (9, 130, 2) and (ref[:, :, 0] != 0).any() and (ref[:, :, 0] == 0).any()
+    assert_bits(ea.render(a, g, 2), ref, "translated facet, twined, 4 -> 2 channels")
+
+
+@pytest.mark.gpu
 def test_translation_without_plane_rotation_and_with_lens(tmp_path):
     o, g = facet(euo.RECTILINEAR, 140, 100, 60.0, 4, 1, dict(x=-0.2, z=-0.1), True, yaw=-8,
                  lens=dict(a=0.01, b=-0.02, c=0.01, h=3.0, v=-2.0))
