@@ -41,6 +41,22 @@ namespace {
 thread_local std::string g_err;
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
+// A temporary device allocation of n elements: freed when it goes out of scope (eu_dev_buf, eu_launch.h, is the
+// buffer that stays). Whoever queues work on it synchronises before that.
+template <class T> struct eu_dev_tmp {
+  T *p = nullptr;
+  eu_dev_tmp() = default;
+  eu_dev_tmp(const eu_dev_tmp &) = delete;
+  eu_dev_tmp &operator=(const eu_dev_tmp &) = delete;
+  ~eu_dev_tmp() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n)
+  {
+    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+};
+
 struct context {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -245,21 +261,39 @@ int check_facet(const eu_facet *f)
   return EU_OK;
 }
 
+// a handle without a container: the facet, the degree and the channel count; nullptr: no host memory
+eu_source *bare_source(const eu_facet *fct, int spline_degree)
+{
+  eu_source *s = new (std::nothrow) eu_source;
+  if (!s) return nullptr;
+  memset(s, 0, sizeof *s);
+  s->fct = *fct;
+  s->degree = spline_degree;
+  s->nch = fct->nchannels;
+  return s;
+}
+
+// the handle and its container (not the copies on other device slots: eu_hip_source_release)
+void destroy_source(eu_source *s)
+{
+  if (!s) return;
+  if (s->dev) (void)hipFree(s->dev);
+  delete s;
+}
+
 // allocates the eu_source and its container for the facet
 int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int support_min,
                int tile_size, eu_source **out)
 {
   if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "spline degree out of range");
-  eu_source *s = new (std::nothrow) eu_source;
+  eu_source *s = bare_source(fct, spline_degree);
   if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
-  memset(s, 0, sizeof *s);
-  s->fct = *fct;
-  s->degree = spline_degree;
-  s->nch = fct->nchannels;
-  if (eu_cube_source(fct->projection)) {
+  const bool cube = eu_cube_source(fct->projection);
+  eu::metrics m {};
+  if (cube) {
     // IR image: container == core, REFLECT x REFLECT (cubemap.h:576-583)
-    eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+    m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
     // The support frame is all the margin the IR has: a ray at a face's edge picks up at left_frame - 0.5, and a
     // spline of degree d reaches d / 2 + 1 texels beyond that. With less frame than that (--support_min below its
     // default of 8 AND a small --tile_size) the reference reads outside its IR array (README.md:1553: the frame
@@ -268,7 +302,7 @@ int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int sup
     // 1 / 2 - where the oracle and the device each read their own memory in front of the array.
     const long need = spline_degree / 2 + 1;
     if (m.left_frame_px + m.inherent_px < need || m.right_frame_px + m.inherent_px < need) {
-      delete s;
+      destroy_source(s);
       return fail(EU_ERR_ARGUMENT, "cubemap support frame (--support_min / --tile_size) too small for the spline degree");
     }
     s->geom.shape[0] = s->geom.core[0] = m.section_px;
@@ -284,11 +318,11 @@ int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int sup
   // 64-texel instructions, up to 3 rows and 63 texels past a tile's box (never evaluated)
   const size_t slack = (size_t)4 * s->geom.shape[0] * s->nch + 64 * 4;
   hipError_t e = hipMalloc((void **)&s->dev, (s->nfloats + slack) * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(s->dev + s->nfloats, 0, slack * sizeof(float));
-  if (e != hipSuccess) { delete s; return fail(EU_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+  if (e != hipSuccess) s->dev = nullptr;
+  else e = hipMemset(s->dev + s->nfloats, 0, slack * sizeof(float));
+  if (e != hipSuccess) { destroy_source(s); return fail(EU_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
   fill_src_dev(s);
-  if (eu_cube_source(fct->projection)) {
-    eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  if (cube) {
     s->sd.refc_md = (float)m.refc_md;
     s->sd.model_to_px = (float)m.model_to_px;
     s->sd.section_px = (int)m.section_px;
@@ -304,6 +338,15 @@ void source_bcs(const eu_facet *f, int *bc0, int *bc1)
   if ((f->projection == EU_SPHERICAL || f->projection == EU_CYLINDRICAL)
       && std::fabs(f->hfov - 2.0 * M_PI) < .000001)
     *bc0 = EU_BC_PERIODIC;
+}
+
+// the prefilter source_t picks (environment.h:905-936): a full spherical image gets the two-axis periodic
+// scheme, everything else bspline::prefilter(). A stronger test than source_bcs', and a separate one.
+// (a full-sphere image smaller than its frame - 2 x 1, 4 x 2, 6 x 3 for degree 3 - takes the sequential forms of
+// the pole rows and of the horizontal bracing: eu_setup.hip, pole_rows_seq_kernel / brace_seq_kernel)
+bool full_sphere(const eu_facet *f)
+{
+  return f->projection == EU_SPHERICAL && std::fabs(f->hfov - 2.0 * M_PI) < .000001 && f->width == 2 * f->height;
 }
 
 // the processed frame: the whole target or its crop window (store_cropped)
@@ -393,6 +436,46 @@ int build_inv_planar(const eu_target *t, eu_inv_planar *q)
   return EU_OK;
 }
 
+// the tap table as the kernels read it: x and y pre-multiplied by the bias 4.0 (twine_t ctor, twining.h:106-121)
+std::vector<float> biased_taps(const float *taps, int ntaps)
+{
+  std::vector<float> v(taps, taps + 3 * (size_t)ntaps);
+  for (int k = 0; k < ntaps; k++)
+    for (int a = 0; a < 2; a++) v[3 * k + a] *= 4.0f;
+  return v;
+}
+
+// The key of a target's cached plan for nsrc facets, everything the stepper tables depend on: the target without
+// the fields that only say which part of the frame a call renders and how it is stored (the tables cover the
+// whole frame), [the number of facets - the multi-facet cache's keys only,] the facets' orientations, the taps.
+std::vector<unsigned char> plan_key_of(const eu_target *t, eu_source *const *srcs, int nsrc, bool multi)
+{
+  const size_t ntap_bytes = 3 * sizeof(float) * (size_t)t->ntaps;
+  std::vector<unsigned char> key(sizeof(eu_target) + (multi ? sizeof(int) : 0) + (size_t)nsrc * 3 * sizeof(double) + ntap_bytes);
+  eu_target tk = *t;
+  tk.taps = nullptr; tk.single = nullptr; tk.row_begin = 0; tk.row_end = 0; tk.stage = 0; tk.nchannels = 0; tk.out_format = 0;
+  tk.band_rows = 0; tk.band_count = 0; tk.band_index = 0;
+  unsigned char *q = key.data();
+  memcpy(q, &tk, sizeof tk); q += sizeof tk;
+  if (multi) { memcpy(q, &nsrc, sizeof(int)); q += sizeof(int); }
+  for (int f = 0; f < nsrc; f++) {
+    double fo[3] = { srcs[f]->fct.yaw, srcs[f]->fct.pitch, srcs[f]->fct.roll };
+    memcpy(q, fo, sizeof fo); q += sizeof fo;
+  }
+  if (t->ntaps > 0) memcpy(q, t->taps, ntap_bytes);
+  return key;
+}
+
+// the frame and band fields eu_render_params and eu_multi_params share (p zeroed: no bands)
+template <class P> void fill_frame(const eu_target *t, P *p)
+{
+  p->width = frame_w(t); p->height = frame_h(t);
+  p->row_begin = t->row_begin; p->row_end = t->row_end;
+  if (t->band_count > 1) {
+    p->band_shift = band_shift_of(t->band_rows); p->band_count = t->band_count; p->band_index = t->band_index;
+  }
+}
+
 int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *out_dev,
                  size_t row_stride_bytes, const eu_switches &sw, eu_render_params *p)
 {
@@ -418,17 +501,7 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
     return fail(EU_ERR_UNSUPPORTED, "generic stepper (translation, --single): no planar-to-ray functor for this target projection");
   eu_inv_planar inv;
   { int rci = build_inv_planar(t, &inv); if (rci) return rci; }
-  std::vector<unsigned char> key(sizeof(eu_target) + 3 * sizeof(double) + 3 * sizeof(float) * (size_t)t->ntaps);
-  {
-    eu_target tk = *t;
-    tk.taps = nullptr; tk.single = nullptr; tk.row_begin = 0; tk.row_end = 0; tk.stage = 0; tk.nchannels = 0; tk.out_format = 0;
-    tk.band_rows = 0; tk.band_count = 0; tk.band_index = 0;     // the tables cover the whole frame
-    unsigned char *q = key.data();
-    memcpy(q, &tk, sizeof tk); q += sizeof tk;
-    double fo[3] = { s->fct.yaw, s->fct.pitch, s->fct.roll };
-    memcpy(q, fo, sizeof fo); q += sizeof fo;
-    if (twine) memcpy(q, t->taps, 3 * sizeof(float) * (size_t)t->ntaps);
-  }
+  std::vector<unsigned char> key = plan_key_of(t, srcs, 1, false);
   int form = g.plan_form, norm_mode = g.plan_norm;
   if (key != g.plan_key) {
     eu::stepper_tables tb;
@@ -440,11 +513,8 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
     HIPCHK(g.row.reserve(tb.row.size()));
     HIPCHK(hipMemcpyAsync(g.col.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipMemcpyAsync(g.row.p, tb.row.data(), tb.row.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    std::vector<float> taps;
+    const std::vector<float> taps = biased_taps(t->taps, t->ntaps);
     if (twine) {
-      // twine_t ctor: x, y pre-multiplied by the bias 4.0 (twining.h:106-121)
-      taps.assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
-      for (int k = 0; k < t->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
       HIPCHK(g.taps.reserve(taps.size()));
       HIPCHK(hipMemcpyAsync(g.taps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     }
@@ -463,11 +533,7 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
   }
   memset(p, 0, sizeof *p);
   p->tab_finite = g.tab_finite;
-  p->width = frame_w(t); p->height = frame_h(t);
-  p->row_begin = t->row_begin; p->row_end = t->row_end;
-  if (t->band_count > 1) {
-    p->band_shift = band_shift_of(t->band_rows); p->band_count = t->band_count; p->band_index = t->band_index;
-  }
+  fill_frame(t, p);
   p->form = form; p->norm_mode = norm_mode;
   if (gen.on) {                // the tables (planar x per column, planar y per row) are the same
     p->form = EU_FORM_GENERIC;
@@ -559,21 +625,7 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     if (srcs[f]->degree != s0->degree) return fail(EU_ERR_ARGUMENT, "facets must share the spline degree");
   }
   const bool twine = t->ntaps > 0;
-  std::vector<unsigned char> key(sizeof(eu_target) + (size_t)nsrc * 3 * sizeof(double)
-                                 + 3 * sizeof(float) * (size_t)t->ntaps + sizeof(int));
-  {
-    eu_target tk = *t;
-    tk.taps = nullptr; tk.single = nullptr; tk.row_begin = 0; tk.row_end = 0; tk.stage = 0; tk.nchannels = 0; tk.out_format = 0;
-    tk.band_rows = 0; tk.band_count = 0; tk.band_index = 0;     // the tables cover the whole frame
-    unsigned char *q = key.data();
-    memcpy(q, &tk, sizeof tk); q += sizeof tk;
-    memcpy(q, &nsrc, sizeof(int)); q += sizeof(int);
-    for (int f = 0; f < nsrc; f++) {
-      double fo[3] = { srcs[f]->fct.yaw, srcs[f]->fct.pitch, srcs[f]->fct.roll };
-      memcpy(q, fo, sizeof fo); q += sizeof fo;
-    }
-    if (twine) memcpy(q, t->taps, 3 * sizeof(float) * (size_t)t->ntaps);
-  }
+  std::vector<unsigned char> key = plan_key_of(t, srcs, nsrc, true);
   if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));   // g.msrc and the tables are rewritten below
   if (key != g.mplan_key) {
     eu::mat3 r_cam = eu::make_r3(t->roll, t->pitch, t->yaw, false);
@@ -590,10 +642,8 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     HIPCHK(g.mrow.reserve(rows.size()));
     HIPCHK(hipMemcpyAsync(g.mcol.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipMemcpyAsync(g.mrow.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
-    std::vector<float> taps;
+    const std::vector<float> taps = biased_taps(t->taps, t->ntaps);
     if (twine) {
-      taps.assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
-      for (int k = 0; k < t->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
       HIPCHK(g.mtaps.reserve(taps.size()));
       HIPCHK(hipMemcpyAsync(g.mtaps.p, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     }
@@ -641,10 +691,7 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
   p->gen = any_generic ? g.mgen.p : nullptr;
   p->rej = any_rej ? g.mrej.p : nullptr;
   p->inv = inv;
-  p->width = frame_w(t); p->height = frame_h(t); p->row_begin = t->row_begin; p->row_end = t->row_end;
-  if (t->band_count > 1) {
-    p->band_shift = band_shift_of(t->band_rows); p->band_count = t->band_count; p->band_index = t->band_index;
-  }
+  fill_frame(t, p);
   p->form = g.mplan_form; p->norm_mode = g.mplan_norm; p->twine = twine; p->ntaps = t->ntaps;
   p->nch = t->nchannels; p->nfct = nsrc; p->plus = (t->nchannels == 2 || t->nchannels == 4);
   p->hdr = t->synopsis == EU_SYN_HDR_MERGE;
@@ -827,6 +874,154 @@ int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
   return EU_OK;
 }
 
+// ---- the load pipeline: pixels -> braced, prefiltered container ------------------------------------------
+
+// where a loader's pixels come from
+enum feed_kind {
+  FEED_HOST_FLOATS,      // host floats at the facet's channel count, no edit: copied straight to the destination
+  FEED_EDITED_FLOATS,    // floats on the host (staged on the device first) or on the device, through the edit
+  FEED_SAMPLES           // 8- or 16-bit samples on the host (uploaded behind their tables) or on the device, decoded there
+};
+struct load_feed {
+  feed_kind kind;
+  const char *who;             // the entry point, as messages name it
+  const void *data;            // the floats or the samples
+  bool on_device;              // data lies in device memory
+  int src_ch;                  // channels of data: the facet's, or one less
+  const eu_facet_edit *edit;   // masks and crop (FEED_HOST_FLOATS: none)
+  bool alter;                  // the edit's kernel runs: FEED_EDITED_FLOATS whenever the edit changes something (a gained
+                               // channel too), FEED_SAMPLES for masks or a crop (the decoder writes a gained channel itself)
+  const eu_samples *smp;       // FEED_SAMPLES: bits, byte order, tables
+};
+
+// One load pipeline with three feeds. Written once: the source and its container (source_bcs, new_source), the plane
+// the pixels arrive in - the facet's window as the core of the container, or the stack of a cubemap's six faces in
+// scratch -, the clearing of a flat container, the finish (cube build, or the prefilter full_sphere() picks), the one
+// synchronisation, and the error precedence: the message the plan upload or a kernel launch set, then the HIP error,
+// then "device set-up stage failed". The feed is all that differs. Host floats: one H2D copy into the plane (1-D
+// into the faces, 2-D into the core), no staging, no kernel. Floats through the edit: host pixels are staged on the
+// device at their own channel count; upload_alpha_plan + eu_launch_facet_alpha write the plane, or - an edit that
+// changes nothing, pixels on the device - a 2-D D2D copy. Integer samples: both tables and, behind them, the samples
+// of a host image go into one device block; eu_launch_decode writes the plane, or - with masks or a crop - a dense
+// buffer that eu_launch_facet_alpha then reads. Scratch is freed by scope, after the synchronisation.
+// The entry points make their own argument checks, in their own order, and find the device (ensure_init).
+int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
+                const load_feed &feed, eu_source **out)
+{
+  int rc, bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  const std::string who(feed.who);
+  const int nch = s->nch, src_ch = feed.src_ch, iir_stream = eu_read_switches().iir_stream;
+  const bool cube = eu_cube_source(fct->projection);
+  eu::metrics m {};
+  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  const eu_container &gm = s->geom;
+  const int w = cube ? int(m.face_px) : int(gm.core[0]), h = cube ? int(6 * m.face_px) : int(gm.core[1]);
+  const size_t npix = size_t(w) * size_t(h);
+  eu_dev_tmp<float> staged, faces;   // floats in front of the edit, at src_ch channels; the faces of a cubemap
+  eu_dev_tmp<char> block;            // samples: both tables and, behind them, the samples of a host image, as they are
+  std::vector<float> tabs;
+  const void *src = feed.data;
+  hipError_t e = hipSuccess;
+  int prc = 0;
+  // what the feed brings to the device first
+  if (feed.kind == FEED_SAMPLES) {
+    const size_t ntab = size_t(1) << feed.smp->bits, nbytes = npix * size_t(src_ch) * size_t(feed.smp->bits / 8);
+    try {
+      tabs.assign(feed.smp->colour_table, feed.smp->colour_table + ntab);
+      const float *at = feed.smp->alpha_table ? feed.smp->alpha_table : feed.smp->colour_table;
+      tabs.insert(tabs.end(), at, at + ntab);
+    } catch (...) { destroy_source(s); return fail(EU_ERR_MEMORY, who + ": host memory"); }
+    const size_t tab_bytes = tabs.size() * sizeof(float);
+    e = block.alloc(tab_bytes + (feed.on_device ? 0 : nbytes));
+    if (e == hipSuccess) e = hipMemcpyAsync(block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess && !feed.on_device) {
+      e = hipMemcpyAsync(block.p + tab_bytes, feed.data, nbytes, hipMemcpyHostToDevice, g.stream);
+      src = block.p + tab_bytes;
+    }
+    if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
+  } else if (feed.kind == FEED_EDITED_FLOATS && !feed.on_device) {
+    e = staged.alloc(npix * src_ch);
+    if (e == hipSuccess) e = hipMemcpyAsync(staged.p, feed.data, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    src = staged.p;
+  }
+  // the plane: w x h pixels of nch floats at dst, rows dst_pitch pixels apart
+  if (e == hipSuccess && cube) e = faces.alloc(npix * nch);
+  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
+  float *dst = cube ? faces.p : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
+  const size_t dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
+  const size_t row_bytes = size_t(w) * nch * sizeof(float), pitch_bytes = dst_pitch * nch * sizeof(float);
+  if (e == hipSuccess) {
+    eu_alpha_params p {};            // the edit, where it runs: src (src_ch channels, dense) -> the plane
+    p.src = static_cast<const float *>(src); p.dst = dst;
+    p.src_pitch = size_t(w); p.dst_pitch = dst_pitch;
+    p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
+    if (feed.kind == FEED_HOST_FLOATS) {
+      e = cube ? hipMemcpyAsync(dst, src, npix * nch * sizeof(float), hipMemcpyHostToDevice, g.stream)
+               : hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyHostToDevice, g.stream);
+    } else if (feed.kind == FEED_EDITED_FLOATS) {
+      if (!feed.alter)
+        e = hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyDeviceToDevice, g.stream);
+    } else {
+      // samples -> floats: straight into the plane, or into the dense buffer the edit reads as it reads
+      // pixels_on_device input (the channel a facet gains is then the edit's work)
+      eu_decode_params d {};
+      d.src = src; d.tables = reinterpret_cast<const float *>(block.p);
+      d.dst = feed.alter ? staged.p : dst;
+      d.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
+      d.w = w; d.h = h; d.bits = feed.smp->bits; d.big_endian = feed.smp->big_endian != 0;
+      d.nch = feed.alter ? src_ch : nch; d.src_ch = src_ch;
+      if (eu_launch_decode(&d, g.stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged.p;
+    }
+    if (feed.alter && !prc) {
+      prc = upload_alpha_plan(feed.edit, w, h, &p);
+      if (!prc && eu_launch_facet_alpha(&p, g.stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+    }
+  }
+  // the finish: the IR image of a cubemap from its faces, or prefilter + brace of the container (a core narrower
+  // than the spline's frame on an axis is braced slice by slice in zimt's order, eu_setup.hip: brace_seq_kernel)
+  if (e == hipSuccess && !prc)
+    rc = cube ? eu_launch_cubemap_build(faces.p, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
+                                        m.refc_md, m.model_to_px, prefilter_degree, iir_stream, g.stream)
+              : eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, full_sphere(fct), iir_stream, g.stream);
+  const hipError_t e2 = hipStreamSynchronize(g.stream);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess || rc || prc) {
+    destroy_source(s);
+    if (prc) return prc;           // the plan's upload or a kernel launch: the message is set
+    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
+    return fail(rc, "device set-up stage failed");
+  }
+  *out = s;
+  return EU_OK;
+}
+
+// mean GPU time of `iters` calls of once() on g.stream between two events, after one untimed call (which builds
+// whatever the first call builds: a plan's tables, derived copies)
+template <class F> int time_on_stream(F once, int iters, float *mean_ms)
+{
+  int rc;
+  if ((rc = once())) return rc;
+  struct events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  HIPCHK(hipEventCreate(&ev.a));
+  HIPCHK(hipEventCreate(&ev.b));
+  HIPCHK(hipEventRecord(ev.a, g.stream));
+  for (int i = 0; i < iters; i++)
+    if ((rc = once())) return rc;
+  HIPCHK(hipEventRecord(ev.b, g.stream));
+  HIPCHK(hipEventSynchronize(ev.b));
+  float ms = 0.0f;
+  HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+  *mean_ms = ms / iters;
+  return EU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -929,7 +1124,7 @@ int eu_hip_source_adopt(const eu_facet *fct, const float *container, int spline_
   eu_source *s = nullptr;
   if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
   hipError_t e = hipMemcpy(s->dev, container, s->nfloats * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(s->dev); delete s; return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }
+  if (e != hipSuccess) { destroy_source(s); return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }
   *out = s;
   return EU_OK;
 }
@@ -943,56 +1138,8 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
-  int bc0, bc1;
-  source_bcs(fct, &bc0, &bc1);
-  eu_source *s = nullptr;
-  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
-  // (a core narrower than the spline's frame on an axis is braced slice by slice in zimt's order,
-  // eu_setup.hip: brace_seq_kernel)
-  const int nch = s->nch, iir_stream = eu_read_switches().iir_stream;
-  hipError_t e = hipSuccess;
-  if (eu_cube_source(fct->projection)) {
-    eu::metrics m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
-    size_t nface = (size_t)6 * m.face_px * m.face_px * nch;
-    float *faces = nullptr;
-    e = hipMalloc((void **)&faces, nface * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(faces, pixels, nface * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) {
-      rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px,
-                                   m.right_frame_px, m.refc_md, m.model_to_px, prefilter_degree,
-                                   iir_stream, g.stream);
-      e = hipStreamSynchronize(g.stream);
-    }
-    if (faces) (void)hipFree(faces);
-  } else {
-    // pixels -> core of the container (2-D strided copy), then prefilter + brace
-    const eu_container &gm = s->geom;
-    e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
-    if (e == hipSuccess)
-      e = hipMemcpy2DAsync(s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch,
-                           (size_t)gm.shape[0] * nch * sizeof(float), pixels,
-                           (size_t)gm.core[0] * nch * sizeof(float),
-                           (size_t)gm.core[0] * nch * sizeof(float), (size_t)gm.core[1],
-                           hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) {
-      // source_t ctor, environment.h:905-936: full spherical images get the
-      // two-axis periodic scheme, everything else bspline::prefilter()
-      int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
-                      && fct->width == 2 * fct->height;
-      // (a full-sphere image smaller than its frame - 2 x 1, 4 x 2, 6 x 3 for degree 3 - takes the sequential forms of
-      // the pole rows and of the horizontal bracing: eu_setup.hip, pole_rows_seq_kernel / brace_seq_kernel)
-      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
-      e = hipStreamSynchronize(g.stream);
-    }
-  }
-  if (e != hipSuccess || rc) {
-    (void)hipFree(s->dev);
-    delete s;
-    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
-    return fail(rc, "device set-up stage failed");
-  }
-  *out = s;
-  return EU_OK;
+  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
 int eu_hip_facet_alpha_rows(int width, int height, const eu_mask_polygon *polygons, int npolygons, int crop_kind,
@@ -1062,69 +1209,8 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
     return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
                               tile_size, out);
   if ((rc = ensure_init())) return rc;
-  int bc0, bc1;
-  source_bcs(fct, &bc0, &bc1);
-  eu_source *s = nullptr;
-  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
-  const int nch = s->nch, src_ch = edit->pixel_channels, iir_stream = eu_read_switches().iir_stream;
-  const bool cube = eu_cube_source(fct->projection);
-  eu::metrics m {};
-  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
-  // the plane of the edit: the facet's window; cubemaps: the stack of six faces
-  const int w = cube ? int(m.face_px) : int(s->geom.core[0]), h = cube ? int(6 * m.face_px) : int(s->geom.core[1]);
-  const size_t npix = size_t(w) * size_t(h);
-  float *staged = nullptr, *faces = nullptr;     // host pixels at their own channel count; the faces of a cubemap
-  int prc = 0;
-  hipError_t e = hipSuccess;
-  const float *src = static_cast<const float *>(pixels);
-  if (!on_device) {
-    e = hipMalloc((void **)&staged, npix * src_ch * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(staged, pixels, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    src = staged;
-  }
-  if (e == hipSuccess && cube) e = hipMalloc((void **)&faces, npix * nch * sizeof(float));
-  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
-  if (e == hipSuccess) {
-    // pixels -> faces / core of the container through the edit (in place of the plain load's strided copy)
-    const eu_container &gm = s->geom;
-    eu_alpha_params p {};
-    p.src = src;
-    p.dst = cube ? faces : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
-    p.src_pitch = size_t(w);
-    p.dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
-    p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
-    if (asked) {
-      prc = upload_alpha_plan(edit, w, h, &p);
-      if (!prc && eu_launch_facet_alpha(&p, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_edited: kernel launch failed");
-    } else {
-      e = hipMemcpy2DAsync(p.dst, p.dst_pitch * nch * sizeof(float), src, size_t(w) * nch * sizeof(float),
-                           size_t(w) * nch * sizeof(float), size_t(h), hipMemcpyDeviceToDevice, g.stream);
-    }
-  }
-  if (e == hipSuccess && !prc) {
-    if (cube) {
-      rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
-                                   m.refc_md, m.model_to_px, prefilter_degree, iir_stream, g.stream);
-    } else {
-      // as eu_hip_source_load: full spherical images get the two-axis periodic scheme
-      int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
-                      && fct->width == 2 * fct->height;
-      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
-    }
-  }
-  const hipError_t e2 = hipStreamSynchronize(g.stream);
-  if (e == hipSuccess) e = e2;
-  if (staged) (void)hipFree(staged);
-  if (faces) (void)hipFree(faces);
-  if (e != hipSuccess || rc || prc) {
-    (void)hipFree(s->dev);
-    delete s;
-    if (prc) return prc;           // the plan's upload or the edit's launch: the message is set
-    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
-    return fail(rc, "device set-up stage failed");
-  }
-  *out = s;
-  return EU_OK;
+  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
 int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
@@ -1148,85 +1234,9 @@ int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
-  int bc0, bc1;
-  source_bcs(fct, &bc0, &bc1);
-  eu_source *s = nullptr;
-  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
-  const int nch = s->nch, src_ch = smp->pixel_channels, iir_stream = eu_read_switches().iir_stream;
   const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
-  const bool cube = eu_cube_source(fct->projection);
-  eu::metrics m {};
-  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
-  const int w = cube ? int(m.face_px) : int(s->geom.core[0]), h = cube ? int(6 * m.face_px) : int(s->geom.core[1]);
-  const size_t npix = size_t(w) * size_t(h), ntab = size_t(1) << smp->bits;
-  const size_t nbytes = npix * size_t(src_ch) * size_t(smp->bits / 8);
-  // both tables in one block, and behind them the samples of a host image, as they are
-  std::vector<float> tabs;
-  try {
-    tabs.assign(smp->colour_table, smp->colour_table + ntab);
-    const float *at = smp->alpha_table ? smp->alpha_table : smp->colour_table;
-    tabs.insert(tabs.end(), at, at + ntab);
-  } catch (...) { (void)hipFree(s->dev); delete s; return fail(EU_ERR_MEMORY, "source_load_samples: host memory"); }
-  char *block = nullptr;
-  float *staged = nullptr, *faces = nullptr;     // decoded pixels in front of the edit; the faces of a cubemap
-  int prc = 0;
-  hipError_t e = hipMalloc((void **)&block, tabs.size() * sizeof(float) + (smp->on_device ? 0 : nbytes));
-  if (e == hipSuccess) e = hipMemcpyAsync(block, tabs.data(), tabs.size() * sizeof(float), hipMemcpyHostToDevice, g.stream);
-  const void *samples = smp->data;
-  if (e == hipSuccess && !smp->on_device) {
-    e = hipMemcpyAsync(block + tabs.size() * sizeof(float), smp->data, nbytes, hipMemcpyHostToDevice, g.stream);
-    samples = block + tabs.size() * sizeof(float);
-  }
-  if (e == hipSuccess && edited) e = hipMalloc((void **)&staged, npix * src_ch * sizeof(float));
-  if (e == hipSuccess && cube) e = hipMalloc((void **)&faces, npix * nch * sizeof(float));
-  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), g.stream);
-  if (e == hipSuccess) {
-    const eu_container &gm = s->geom;
-    float *dst = cube ? faces : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
-    const size_t dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
-    // samples -> floats: straight into the faces / the core of the container, or - with masks or a crop - into a
-    // dense buffer that the edit reads as it reads pixels_on_device input (the channel a facet gains is then its work)
-    eu_decode_params d {};
-    d.src = samples; d.tables = reinterpret_cast<const float *>(block);
-    d.dst = edited ? staged : dst;
-    d.dst_pitch = edited ? size_t(w) : dst_pitch;
-    d.w = w; d.h = h; d.bits = smp->bits; d.big_endian = smp->big_endian != 0;
-    d.nch = edited ? src_ch : nch; d.src_ch = src_ch;
-    if (eu_launch_decode(&d, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_samples: kernel launch failed");
-    if (!prc && edited) {
-      eu_alpha_params p {};
-      p.src = staged; p.dst = dst;
-      p.src_pitch = size_t(w); p.dst_pitch = dst_pitch;
-      p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
-      prc = upload_alpha_plan(&ed, w, h, &p);
-      if (!prc && eu_launch_facet_alpha(&p, g.stream)) prc = fail(EU_ERR_NO_DEVICE, "source_load_samples: kernel launch failed");
-    }
-  }
-  if (e == hipSuccess && !prc) {
-    if (cube) {
-      rc = eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
-                                   m.refc_md, m.model_to_px, prefilter_degree, iir_stream, g.stream);
-    } else {
-      // as eu_hip_source_load: full spherical images get the two-axis periodic scheme
-      int spherical = fct->projection == EU_SPHERICAL && std::fabs(fct->hfov - 2.0 * M_PI) < .000001
-                      && fct->width == 2 * fct->height;
-      rc = eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, spherical, iir_stream, g.stream);
-    }
-  }
-  const hipError_t e2 = hipStreamSynchronize(g.stream);
-  if (e == hipSuccess) e = e2;
-  if (block) (void)hipFree(block);
-  if (staged) (void)hipFree(staged);
-  if (faces) (void)hipFree(faces);
-  if (e != hipSuccess || rc || prc) {
-    (void)hipFree(s->dev);
-    delete s;
-    if (prc) return prc;
-    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
-    return fail(rc, "device set-up stage failed");
-  }
-  *out = s;
-  return EU_OK;
+  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
 int eu_hip_source_alloc(const eu_facet *fct, int spline_degree, int support_min, int tile_size,
@@ -1289,13 +1299,8 @@ int eu_hip_source_info(const eu_source *src, eu_container *geom, int *nch)
 int eu_hip_source_release(eu_source *src)
 {
   if (!src) return EU_OK;
-  for (int k = 0; k < EU_MAX_SLOTS; k++)
-    if (src->replica[k]) {
-      if (src->replica[k]->dev) (void)hipFree(src->replica[k]->dev);
-      delete src->replica[k];
-    }
-  if (src->dev) (void)hipFree(src->dev);
-  delete src;
+  for (int k = 0; k < EU_MAX_SLOTS; k++) destroy_source(src->replica[k]);
+  destroy_source(src);
   return EU_OK;
 }
 
@@ -1454,7 +1459,7 @@ int replica_of(eu_source *src, int k, eu_source **out)
         e = hipMemcpyPeerAsync(r->dev, ctx_[k].device, src->dev, ctx_[src->slot].device, src->nfloats * sizeof(float), g.stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) { if (r->dev) (void)hipFree(r->dev); delete r; return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }
+    if (e != hipSuccess) { destroy_source(r); return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }
     // the evaluator parameters are the original's (same geometry, same verified constants) on another base
     r->sd.base = r->dev + (src->sd.base - src->dev);
     src->replica[k] = r;
@@ -1643,12 +1648,11 @@ static int check_rays(const eu_rays *r, const eu_source *src, const float *out, 
   return EU_OK;
 }
 
-// the tap table on the device, x and y premultiplied by the bias 4.0 (twine_t ctor, twining.h:106-121)
+// the tap table on the device (biased_taps)
 static int upload_ray_taps(const eu_rays *r)
 {
   if (r->ninputs != 9) return EU_OK;
-  std::vector<float> taps(r->taps, r->taps + 3 * (size_t)r->ntaps);
-  for (int k = 0; k < r->ntaps; k++) { taps[3 * k] *= 4.0f; taps[3 * k + 1] *= 4.0f; }
+  std::vector<float> taps = biased_taps(r->taps, r->ntaps);
   if (g.rtaps.p && taps.size() == g.rtaps_host.size() &&
       !memcmp(taps.data(), g.rtaps_host.data(), taps.size() * sizeof(float)))
     return EU_OK;
@@ -1745,23 +1749,7 @@ int eu_hip_render_rays_timed(const eu_rays *r, eu_source *src, float *out_dev, s
     return launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out_dev, out_row_stride_bytes, r->width, r->height,
                        g.stream);
   };
-  if ((rc = once())) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct guard {
-    hipEvent_t &a, &b;
-    ~guard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } events { e0, e1 };
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, g.stream));
-  for (int i = 0; i < iters; i++)
-    if ((rc = once())) return rc;
-  HIPCHK(hipEventRecord(e1, g.stream));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.0f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  *mean_ms = ms / iters;
-  return EU_OK;
+  return time_on_stream(once, iters, mean_ms);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1831,13 +1819,12 @@ static int check_views_supported(const char *who, const eu_target *t, const eu_v
   return check_views_biatan6(t, views, nviews);
 }
 
-// the tap table on the device, x and y premultiplied by the bias 4.0 (twine_t ctor, twining.h:106-121);
-// true in *changed when the buffer was rewritten (on `st`, from *keep: the caller synchronises)
+// the tap table on the device (biased_taps); where the buffer is rewritten that happens on `st`, from *keep: the
+// caller synchronises
 static int upload_view_taps(const eu_target *t, hipStream_t st, std::vector<float> *keep)
 {
   if (t->ntaps <= 0) return EU_OK;
-  keep->assign(t->taps, t->taps + 3 * (size_t)t->ntaps);
-  for (int k = 0; k < t->ntaps; k++) { (*keep)[3 * k] *= 4.0f; (*keep)[3 * k + 1] *= 4.0f; }
+  *keep = biased_taps(t->taps, t->ntaps);
   if (g.vtaps.p && keep->size() == g.vtaps_host.size() &&
       !memcmp(keep->data(), g.vtaps_host.data(), keep->size() * sizeof(float)))
     return EU_OK;
@@ -2103,10 +2090,8 @@ int eu_hip_diag_host_source(const eu_facet *fct, int spline_degree, eu_source **
   int rc;
   if ((rc = check_facet(fct))) return rc;
   if (!out) return fail(EU_ERR_ARGUMENT, "null argument");
-  eu_source *s = new (std::nothrow) eu_source;
+  eu_source *s = bare_source(fct, spline_degree);
   if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
-  memset(s, 0, sizeof *s);
-  s->fct = *fct; s->degree = spline_degree; s->nch = fct->nchannels;
   *out = s;
   return EU_OK;
 }
@@ -2128,24 +2113,9 @@ int eu_hip_render_timed(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   if (!srcs || nsrc < 1 || !trg || !out_dev) return fail(EU_ERR_ARGUMENT, "no source / no output");
   if ((rc = check_target(trg))) return rc;
   const eu_switches sw = eu_read_switches();
-  // one untimed launch builds the plan (stepper tables, derived copies)
-  if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, sw, g.stream))) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct guard {
-    hipEvent_t &a, &b;
-    ~guard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } events { e0, e1 };
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, g.stream));
-  for (int i = 0; i < iters; i++)
-    if ((rc = render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, sw, g.stream))) return rc;
-  HIPCHK(hipEventRecord(e1, g.stream));
-  HIPCHK(hipEventSynchronize(e1));
-  float ms = 0.0f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  *mean_ms = ms / iters;
-  return EU_OK;
+  // (the untimed launch builds the plan: stepper tables, derived copies)
+  auto once = [&]() { return render_on_device(trg, srcs, nsrc, out_dev, out_row_stride_bytes, sw, g.stream); };
+  return time_on_stream(once, iters, mean_ms);
 }
 
 // DIAGNOSTIC (not declared in eu_hip.h): phase stamps of the headline path,
@@ -2159,14 +2129,13 @@ int eu_hip_diag_stamps(const eu_target *trg, eu_source *const *srcs, int nsrc, f
   eu_render_params p;
   if ((rc = build_params(trg, srcs, nsrc, out_dev, out_row_stride_bytes, eu_read_switches(), &p))) return rc;
   if (p.nch != 3 || p.src.degree != 3 || p.twine) return fail(EU_ERR_ARGUMENT, "diag: NCH 3, degree 3, no twining");
-  unsigned long long *d = nullptr;
-  struct guard { unsigned long long *&q; ~guard() { if (q) (void)hipFree(q); } } buf { d };
-  HIPCHK(hipMalloc((void **)&d, nwaves * 8 * sizeof(unsigned long long)));
-  HIPCHK(hipMemsetAsync(d, 0, nwaves * 8 * sizeof(unsigned long long), g.stream));
+  eu_dev_tmp<unsigned long long> d;
+  HIPCHK(d.alloc(nwaves * 8));
+  HIPCHK(hipMemsetAsync(d.p, 0, nwaves * 8 * sizeof(unsigned long long), g.stream));
   for (int i = 0; i < 3; i++)
-    if (eu_launch_diag(&p, d, g.stream)) return fail(EU_ERR_NO_DEVICE, "diag launch failed");
+    if (eu_launch_diag(&p, d.p, g.stream)) return fail(EU_ERR_NO_DEVICE, "diag launch failed");
   HIPCHK(hipStreamSynchronize(g.stream));
-  HIPCHK(hipMemcpy(host_stamps, d, nwaves * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host_stamps, d.p, nwaves * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return EU_OK;
 }
 
@@ -2179,9 +2148,9 @@ int eu_hip_diag_source_coordinates(const eu_source *src, const float *rays, long
   if ((rc = ensure_init())) return rc;
   if (!src || !rays || !out || n < 0) return fail(EU_ERR_ARGUMENT, "null argument");
   if (n == 0) return EU_OK;
-  float *d = nullptr;
-  struct guard { float *&q; ~guard() { if (q) (void)hipFree(q); } } buf { d };
-  HIPCHK(hipMalloc((void **)&d, (size_t)n * 6 * sizeof(float)));
+  eu_dev_tmp<float> buf;
+  HIPCHK(buf.alloc((size_t)n * 6));
+  float *d = buf.p;
   HIPCHK(hipMemcpy(d, rays, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
   const int lrc = eu_launch_diag_coords(&src->sd, d, n, variant, d + (size_t)n * 3, g.stream);
   if (lrc > 0) return fail(EU_ERR_UNSUPPORTED, "the packed forms cover lat/lon, cubemap and biatan6 sources");
@@ -2196,13 +2165,12 @@ int eu_hip_selftest_math(unsigned long long seed, int blocks, int iters, unsigne
 {
   int rc;
   if ((rc = ensure_init())) return rc;
-  unsigned long long *d = nullptr;
-  struct guard { unsigned long long *&q; ~guard() { if (q) (void)hipFree(q); } } buf { d };
-  HIPCHK(hipMalloc((void **)&d, 4 * sizeof(unsigned long long)));
-  HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), g.stream));
-  if (eu_launch_selftest(seed, blocks, iters, d, g.stream)) return fail(EU_ERR_NO_DEVICE, "selftest launch failed");
+  eu_dev_tmp<unsigned long long> d;
+  HIPCHK(d.alloc(4));
+  HIPCHK(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), g.stream));
+  if (eu_launch_selftest(seed, blocks, iters, d.p, g.stream)) return fail(EU_ERR_NO_DEVICE, "selftest launch failed");
   HIPCHK(hipStreamSynchronize(g.stream));
-  HIPCHK(hipMemcpy(bad4, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bad4, d.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return EU_OK;
 }
 

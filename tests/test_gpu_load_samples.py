@@ -196,6 +196,64 @@ def test_many_workgroups():
     check(flat_facet(1024, 512, 4), make_samples(512, 1024, 4, 16, 2), 16, 3, "1024 x 512 x 4, 16 bit", True)
 
 
+FEED_CASES = {
+    # name: (facet, plane width, plane height) - the smallest shapes at which the loader's branches differ
+    "window": (lambda: ea.facet_spec(ea.RECTILINEAR, 300, 200, 80.0, nchannels=4, window=(131, 77, 40, 30)), 131, 77),
+    "fullsphere": (lambda: ea.facet_spec(ea.SPHERICAL, 6, 3, 360.0, nchannels=4), 6, 3),
+    "cubemap": (lambda: ea.facet_spec(ea.CUBEMAP, 64, 384, 90.0, nchannels=4), 64, 384),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FEED_CASES))
+def test_every_feed_builds_the_same_container(name):
+    """One load pipeline, three feeds, five ways in: host floats and a device float tensor (through the edit), host
+    and device uint8 samples, host big-endian uint16 samples of the same values with a 65536-entry table that starts
+    with the 8-bit one. 3-channel input, 4-channel facet, degree 3. With a mask polygon and an elliptic crop all five
+    containers are, bit for bit, Source.load of the floats widened and edited on the host; without an edit (the facet
+    only gains its channel) they are the plain load of the widened floats, the sixth feed. The container's pitch
+    differs from the plane's (window), the periodic prefilter with the sequential pole rows and brace runs
+    (fullsphere), the face scratch and the cube build are used (cubemap)."""
+    import torch
+    make_facet, w, h = FEED_CASES[name]
+    fct = make_facet()
+    s = make_samples(h, w, 3, 8, 7 * w + h)
+    colour, _ = tables(8)
+    colour16 = np.concatenate([colour, tables(16)[0][256:]])
+    assert colour16.shape == (65536,) and (bits_of(colour16[:256]) == bits_of(colour)).all()
+    floats = np.ascontiguousarray(colour[s], np.float32)
+    wide = np.concatenate([floats, np.ones((h, w, 1), np.float32)], 2)
+    s16 = s.astype(np.uint16).byteswap()                   # the same values, 16 bit, stored high byte first
+    poly = [(np.array([0.2, 0.7, 0.5], np.float32) * w, np.array([0.2, 0.3, 0.8], np.float32) * h)]
+    crop = (w // 10, w - w // 8, h // 9, h - h // 7)
+    ran = 0
+    for edit in (dict(masks=poly, crop=crop, crop_kind=2), {}):
+        prepared = wide.copy()
+        if edit:
+            ea.facet_alpha(prepared, poly, crop, 2)        # the library's host function, in place
+            assert (prepared != wide).any(), "the edit changes something"
+        want = ea.Source.load(fct, prepared, 3)            # eu_hip_source_load
+        feeds = [
+            ("host floats", lambda: ea.Source.load(fct, floats, 3, **edit)),
+            ("device floats", lambda: ea.Source.load(fct, torch.from_numpy(floats).to("cuda:0"), 3, **edit)),
+            ("host uint8", lambda: ea.Source.load_samples(fct, s, colour, spline_degree=3, **edit)),
+            ("device uint8", lambda: ea.Source.load_samples(fct, torch.from_numpy(s).to("cuda:0"), colour,
+                                                            spline_degree=3, **edit)),
+            ("host uint16, big-endian", lambda: ea.Source.load_samples(fct, s16, colour16, big_endian=True,
+                                                                       spline_degree=3, **edit)),
+        ]
+        if not edit:
+            feeds.append(("plain load of the widened floats", lambda: ea.Source.load(fct, wide, 3)))
+        first = None
+        for what, load in feeds:
+            got = load()
+            same_container(got, want, (name, "edited" if edit else "channel gain", what))
+            if first is not None:
+                same_container(got, first, (name, what, "against", feeds[0][0]))
+            first = first or got
+            ran += 1
+    assert ran == 11
+
+
 def test_render():
     """spherical 256 x 128 to a 64-wide cubemap, degree 3: the same frame from either source"""
     colour, alpha = tables(8)
