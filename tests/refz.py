@@ -2,7 +2,8 @@
 headers compiled in place from a reference checkout (oracle/Makefile, REF). Only
 present where that checkout is; tests marked 'ref' compare with it live there, and
 elsewhere with the SHA-256 of its results recorded in tests/golden/ref_digests.json and,
-for the steppers, tests/golden/stepper_digests.json (same())."""
+for the steppers, tests/golden/stepper_digests.json, for the pixel value classes (tests/pixel_values.py)
+tests/golden/pixel_value_digests.json (same())."""
 import ctypes as C
 import hashlib
 import json
@@ -15,6 +16,8 @@ LIB = os.path.join(ROOT, "oracle", "_ref", "libref_zimt.so")
 DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")
 # the digests of the steppers' results (keys "stepper_...", tests/test_stepper_pinned.py) have a file of their own
 STEPPER_DIGESTS = os.path.join(ROOT, "tests", "golden", "stepper_digests.json")
+# ... and those of the pixel value classes (keys "pixval_...", tests/test_oracle_pixel_values.py)
+PIXEL_DIGESTS = os.path.join(ROOT, "tests", "golden", "pixel_value_digests.json")
 RECORDING = False       # tests/golden/make_ref_digests.py: collect into RECORDED, skip the check against DIGESTS
 RECORDED = {}
 
@@ -34,19 +37,31 @@ def digest(a):
 _digests = None
 
 
-def same(key, ours, reference, symbol=None):
+def one_nan(a):
+    """a float32 copy in which every NaN is the one pattern 0x7fc00000"""
+    a = np.array(a, np.float32, order="C")
+    a.view(np.uint32)[np.isnan(a)] = 0x7FC00000
+    return a
+
+
+def same(key, ours, reference, symbol=None, any_nan=False):
     """True when `ours` is bit for bit the reference's result: `reference()` (a call into the library) where
     the library is built (and exports `symbol`, if one is named) - and then its digest must be the one recorded
-    under `key` - else the recorded digest"""
+    under `key` - else the recorded digest. any_nan (data with non-finite values only): every NaN of both sides
+    becomes one pattern first - where the NaNs are is compared and digested, which bits they carry is not"""
     global _digests
     if _digests is None:
         _digests = {}
-        for path in (DIGESTS, STEPPER_DIGESTS):
+        for path in (DIGESTS, STEPPER_DIGESTS, PIXEL_DIGESTS):
             if os.path.exists(path):
                 _digests.update(json.load(open(path)))
+    if any_nan:
+        ours = one_nan(ours)
     if not available(symbol):
         return digest(ours) == _digests[key]
     ref = np.ascontiguousarray(reference(), np.float32)
+    if any_nan:
+        ref = one_nan(ref)
     RECORDED[key] = digest(ref)
     assert RECORDING or _digests.get(key) == RECORDED[key], f"the digest recorded under tests/golden for {key} is stale"
     ours = np.ascontiguousarray(ours, np.float32)

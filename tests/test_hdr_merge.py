@@ -42,8 +42,9 @@ def f32(x):
     return np.asarray(x, np.float32)
 
 
-def numpy_hdr_merge(px, brightens, nch):
-    """the synopsis from the facets' pixels px[f] (H, W, nch), float32 operation by operation"""
+def numpy_hdr_merge(px, brightens, nch, with_qsum=False):
+    """the synopsis from the facets' pixels px[f] (H, W, nch), float32 operation by operation; with_qsum: and the
+    sum of the qualities it divides by"""
     lowest, highest, low, high = np.float32(100000.0), np.float32(-1.0), -1, -1
     for f, b in enumerate(brightens):
         b = np.float32(b)
@@ -83,7 +84,7 @@ def numpy_hdr_merge(px, brightens, nch):
             if alpha:
                 t = f32(t * trg[:, :, nch - 1])
             trg[:, :, c] = t
-    return trg
+    return (trg, qsum) if with_qsum else trg
 
 
 @pytest.mark.parametrize("nch", [1, 2, 3, 4])
