@@ -148,6 +148,8 @@ def lib():
     L.eu_hip_source_update_facet.argtypes = [vp, vp]
     L.eu_hip_source_release.argtypes = [vp]
     L.eu_hip_render.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
+    L.eu_hip_render_samples.argtypes = [vp, vp, i32, vp, vp, C.c_size_t, i32, vp]
+    L.eu_hip_encode_samples.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_init_devices.argtypes = [vp, i32]
     L.eu_hip_render_devices.argtypes = [vp, vp, i32, vp, C.c_size_t, i32]
     L.eu_hip_device_strips.argtypes = [vp, vp, i32, vp, vp]
@@ -655,6 +657,157 @@ def render(args, sources, nchannels=None, row_begin=0, row_end=None, stage=0, ou
     arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
     _check(lib().eu_hip_render(C.byref(t), arr, len(sources), out.ctypes.data_as(C.c_void_p),
                                w * och * 4, 0, None))
+    return out
+
+
+class Encode(C.Structure):
+    """struct eu_encode"""
+    _fields_ = [("bits", C.c_int32), ("big_endian", C.c_int32),
+                ("colour_steps", C.c_void_p), ("alpha_steps", C.c_void_p)]
+
+
+def _float_keys(v):
+    """float32 -> uint32 keys in the order of the floats' values (-inf lowest, +inf highest of the numbers)"""
+    u = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _key_floats(k):
+    k = np.ascontiguousarray(k, np.uint32)
+    return np.where(k & np.uint32(0x80000000), k & np.uint32(0x7fffffff), ~k).astype(np.uint32).view(np.float32)
+
+
+def sample_steps(bits=8, maxval=None):
+    """The step table (eu_encode) of the linear default: steps[k] is the smallest float32 v whose code
+    Q(v) = trunc(clip(v, 0, 1) * maxval + 0.5), evaluated in float32 (NaN: 0), is >= k - found by bisection over
+    the float32 bit patterns from -inf to +inf, with that very expression; steps[0] is -inf, entries above maxval
+    are NaN. 1 << bits float32 values; maxval defaults to 255 / 65535."""
+    if bits not in (8, 16):
+        raise EuError("sample_steps: bits is 8 or 16")
+    n = 1 << bits
+    maxval = n - 1 if maxval is None else int(maxval)
+    if not 1 <= maxval < n:
+        raise EuError(f"sample_steps: maxval is 1 .. {n - 1}")
+    mv, half = np.float32(maxval), np.float32(0.5)
+
+    def q(v):
+        with np.errstate(invalid="ignore"):
+            c = np.minimum(np.maximum(v, np.float32(0)), np.float32(1))
+            return (c * mv + half).astype(np.uint32)
+
+    want = np.arange(1, maxval + 1, dtype=np.uint32)
+    lo = np.full(maxval, _float_keys(np.float32(-np.inf))[()], np.uint64)
+    hi = np.full(maxval, _float_keys(np.float32(np.inf))[()], np.uint64)
+    while (lo < hi).any():
+        mid = (lo + hi) // 2
+        up = q(_key_floats(mid.astype(np.uint32))) >= want
+        hi = np.where(up, mid, hi)
+        lo = np.where(up, lo, mid + 1)
+    steps = np.full(n, np.nan, np.float32)
+    steps[0] = -np.inf
+    steps[1:maxval + 1] = _key_floats(lo.astype(np.uint32))
+    return steps
+
+
+_SAMPLE_DTYPE = {8: np.uint8, 16: np.uint16}
+
+
+def _encode_struct(who, bits, colour_steps, alpha_steps, maxval, big_endian):
+    """(eu_encode, arrays it points into); without tables the linear default of sample_steps(bits, maxval)"""
+    if bits not in (8, 16):
+        raise EuError(f"{who}: bits is 8 or 16")
+    n = 1 << bits
+    if colour_steps is None:
+        colour_steps = sample_steps(bits, maxval)
+    elif maxval is not None:
+        raise EuError(f"{who}: maxval belongs to the default table; a table of the caller's says its own")
+    tabs = [np.ascontiguousarray(t, np.float32) for t in (colour_steps, alpha_steps) if t is not None]
+    if any(t.shape != (n,) for t in tabs):
+        raise EuError(f"{who}: a step table for {bits}-bit samples has {n} entries")
+    e = Encode(bits, int(bool(big_endian)), tabs[0].ctypes.data, tabs[1].ctypes.data if len(tabs) > 1 else None)
+    return e, tabs
+
+
+def _sample_rows(who, a, shape, bits):
+    """`a`, (rows, width, channels) samples of `bits` bits, numpy or torch on the device, dense pixels, rows possibly
+    padded: (address, row stride in bytes, on_device)"""
+    if tuple(a.shape) != tuple(shape):
+        raise EuError(f"{who}: out has shape {tuple(a.shape)}, expected {tuple(shape)}")
+    size = bits // 8
+    if _is_torch(a):
+        import torch
+        if not a.is_cuda or a.dtype != {8: torch.uint8, 16: torch.uint16}[bits]:
+            raise EuError(f"{who}: out is uint{bits} and on the device")
+        st = tuple(v * size for v in a.stride())
+        on_device, ptr = True, a.data_ptr()
+    else:
+        if not isinstance(a, np.ndarray) or a.dtype.newbyteorder("=") != np.dtype(_SAMPLE_DTYPE[bits]):
+            raise EuError(f"{who}: out is a uint{bits} array")
+        st, on_device, ptr = tuple(a.strides), False, a.ctypes.data
+    rows, w, c = shape
+    if rows and w and c and (st[2] != size or st[1] != size * c or (rows > 1 and st[0] < w * c * size)):
+        raise EuError(f"{who}: out has dense pixels; only its rows may be padded")
+    if on_device:
+        import torch
+        torch.cuda.current_stream(a.device).synchronize()
+    return ptr, (st[0] if rows > 1 else w * c * size), on_device
+
+
+def encode_samples(frame, colour_steps=None, alpha_steps=None, bits=8, maxval=None, big_endian=False, out=None,
+                   stream=None):
+    """eu_hip_encode_samples: float pixels to 8- or 16-bit samples on the device. `frame`: float32, shape
+    (..., channels) with 1..4 channels, a numpy array or a torch tensor on the library's device (_grid's layouts:
+    contiguous, or three axes with padded rows) - the result of render(), render_rays() or render_views().
+    colour_steps / alpha_steps: float32 step tables of 1 << bits entries (eu_hip.h: eu_encode; alpha_steps is for
+    the last of 2 or 4 channels, None: the colour table); without tables the linear default sample_steps(bits,
+    maxval), which equals (clip(v, 0, 1) * maxval + 0.5).astype(...) evaluated in float32. big_endian: 16-bit
+    samples are written high byte first, as PNM / PAM files hold them. Returns samples of the frame's shape: a new
+    numpy array for a numpy frame, a new torch tensor on the device for a torch frame, or `out` (numpy or torch,
+    rows may be padded). With frame and out on the device the call is asynchronous on `stream` (a hipStream_t
+    address; None: the library's stream) until sync()."""
+    if not _is_torch(frame) and not (isinstance(frame, np.ndarray) and frame.dtype == np.float32):
+        frame = np.ascontiguousarray(frame, np.float32)
+    if frame.ndim < 1 or not 1 <= frame.shape[-1] <= 4:
+        raise EuError("encode_samples: a frame has shape (..., channels), 1 to 4 channels")
+    e, keep = _encode_struct("encode_samples", bits, colour_steps, alpha_steps, maxval, big_endian)
+    fptr, fstride, f_dev, lead, width, height = _grid(frame, "frame")
+    nch = frame.shape[-1]
+    if out is None:
+        if f_dev:
+            import torch
+            out = torch.empty(tuple(frame.shape), dtype={8: torch.uint8, 16: torch.uint16}[bits], device=frame.device)
+        else:
+            out = np.zeros(frame.shape, _SAMPLE_DTYPE[bits])
+    if tuple(out.shape) != tuple(frame.shape):
+        raise EuError(f"encode_samples: out has shape {tuple(out.shape)}, expected {tuple(frame.shape)}")
+    flat = out if out.ndim == 3 and tuple(out.shape[:2]) == (height, width) else out.reshape(height, width, nch)
+    optr, ostride, o_dev = _sample_rows("encode_samples", flat, (height, width, nch), bits)
+    _check(lib().eu_hip_encode_samples(C.c_void_p(fptr), fstride, int(f_dev), width, height, nch, C.byref(e),
+                                       C.c_void_p(optr), ostride, int(o_dev), C.c_void_p(stream) if stream else None))
+    return out
+
+
+def render_samples(args, sources, nchannels=None, row_begin=0, row_end=None, colour_steps=None, alpha_steps=None,
+                   bits=8, maxval=None, big_endian=False, out=None, band=None, stream=None):
+    """eu_hip_render_samples: render() with the encode behind it on the device - (rows, width, nch) uint8 / uint16,
+    byte for byte encode_samples(render(...), ...) with the same tables, without the float frame leaving the device.
+    Tables, bits, maxval and big_endian as encode_samples. Returns a new numpy array, or `out` (numpy, or a torch
+    tensor of that dtype on the library's device; rows may be padded); with `out` on the device the call is
+    asynchronous on `stream` until sync(). Float frames only: no stage output, not a tethered job."""
+    if not isinstance(sources, (list, tuple)):
+        sources = [sources]
+    if args.tethered:
+        raise EuError("render_samples: a tethered job has its own format (render)")
+    nch = nchannels or sources[0].fct.nchannels
+    t = args.target(nch, row_begin, row_end, 0, band)
+    rows, w = t.row_end - t.row_begin, args.out_width
+    e, keep = _encode_struct("render_samples", bits, colour_steps, alpha_steps, maxval, big_endian)
+    if out is None:
+        out = np.zeros((rows, w, nch), _SAMPLE_DTYPE[bits])
+    optr, ostride, o_dev = _sample_rows("render_samples", out, (rows, w, nch), bits)
+    arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
+    _check(lib().eu_hip_render_samples(C.byref(t), arr, len(sources), C.byref(e), C.c_void_p(optr), ostride, int(o_dev),
+                                       C.c_void_p(stream) if stream else None))
     return out
 
 

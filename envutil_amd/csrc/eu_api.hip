@@ -16,6 +16,7 @@
 #include "eu_imageprep.h"
 #include "eu_alpha.h"
 #include "eu_decode.h"
+#include "eu_encode.h"
 #include "eu_math2.h"
 #include "eu_launch.h"
 #include "eu_ray_guard.h"
@@ -105,6 +106,13 @@ struct context {
   std::vector<float> vtaps_host;                  // what vtaps holds
   hipStream_t views_user = nullptr;               // the stream the last call worked on with these buffers (last_user is
                                                   // one slot for all entry points: a render in between overwrites it)
+  // eu_hip_encode_samples / eu_hip_render_samples: the step tables on the device (colour, then alpha), the host copy
+  // they were uploaded from - it stays, so that an upload queued on a stream never reads a caller's memory after the
+  // call, and equal tables are not sent again - and the staging of a host frame and of a host output
+  eu_dev_buf<float> esteps, eframe;
+  eu_dev_buf<uint32_t> eout;
+  std::vector<float> esteps_host;
+  hipStream_t encode_user = nullptr;              // the stream the last call worked on with these buffers (as views_user)
   eu_dev_buf<int32_t> aplan;                      // row plan of the last device alpha edit
   hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
@@ -1304,11 +1312,11 @@ int eu_hip_source_release(eu_source *src)
   return EU_OK;
 }
 
-// one job, everything on the device: float pixels straight into out_dev, or -
-// tethered - float pixels into the library's frame buffer followed by the
-// to_screen_t pass that writes the packed words to out_dev
+// one job, everything on the device: float pixels straight into out_dev, or float pixels into the library's
+// frame buffer followed by a post-pass that writes out_dev - tethered, the to_screen_t pass and its packed words;
+// with `enc` (its tables are in g.esteps: upload_steps), the encode to integer samples
 static int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev,
-                            size_t stride_bytes, const eu_switches &sw, hipStream_t st)
+                            size_t stride_bytes, const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr)
 {
   int rc;
   const bool multi = nsrc > 1;
@@ -1317,8 +1325,10 @@ static int render_on_device(const eu_target *trg, eu_source *const *srcs, int ns
   float *fout = out_dev;
   size_t fstride = stride_bytes;
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
-  if (screen) {
-    if (!g.lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
+  if (screen || enc) {
+    if (screen && !g.lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
+    // an encode queued on another stream may still read the frame buffer (upload_steps has waited where enc is set)
+    if (g.encode_user && g.encode_user != st) HIPCHK(hipStreamSynchronize(g.encode_user));
     tf.out_format = EU_OUT_FLOAT;
     fstride = (size_t)frame_w(trg) * trg->nchannels * sizeof(float);
     HIPCHK(g.scr.reserve(rows * frame_w(trg) * trg->nchannels));
@@ -1339,6 +1349,135 @@ static int render_on_device(const eu_target *trg, eu_source *const *srcs, int ns
                           (long long)(stride_bytes / sizeof(unsigned)), frame_w(trg), (int)rows,
                           trg->nchannels, g.lut, st))
     return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+  if (enc && rows) {
+    eu_encode_params ep {};
+    ep.src = fout; ep.src_stride_bytes = fstride;
+    ep.dst = out_dev; ep.dst_stride_bytes = stride_bytes;
+    ep.tables = g.esteps.p;
+    ep.w = frame_w(trg); ep.h = (int)rows; ep.nch = trg->nchannels;
+    ep.bits = enc->bits; ep.big_endian = enc->big_endian;
+    if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+  }
+  return EU_OK;
+}
+
+// ---- integer samples on the way out (eu_encode.hip) -------------------------------------------------------------
+// a step table as eu_hip.h defines it: steps[1 .. m] free of NaN and non-decreasing, m >= 1, NaN behind m
+static int check_steps(const float *s, int bits, const char *who, const char *which)
+{
+  const int n = 1 << bits;
+  const std::string head = std::string(who) + ": " + which + " steps: ";
+  if (std::isnan(s[1])) return fail(EU_ERR_ARGUMENT, head + "entry 1 is NaN, a table has at least one code above 0");
+  int m = 1;
+  for (; m + 1 < n && !std::isnan(s[m + 1]); m++)
+    if (s[m + 1] < s[m]) return fail(EU_ERR_ARGUMENT, head + "entry " + std::to_string(m + 1) + " is smaller than the one before it");
+  for (int k = m + 1; k < n; k++)
+    if (!std::isnan(s[k]))
+      return fail(EU_ERR_ARGUMENT, head + "entry " + std::to_string(k) + " is a number behind the NaN at entry " + std::to_string(m + 1));
+  return EU_OK;
+}
+
+// what both sample entry points ask of `enc` and `out`: rows of `width` pixels of `nch` samples
+static int check_encode(const char *who, const eu_encode *enc, int width, int nch, const void *out, size_t out_row_stride_bytes)
+{
+  const std::string head = std::string(who) + ": ";
+  if (!enc || !out) return fail(EU_ERR_ARGUMENT, head + "null argument");
+  if (enc->bits != 8 && enc->bits != 16) return fail(EU_ERR_ARGUMENT, head + "bits must be 8 or 16");
+  if (!enc->colour_steps) return fail(EU_ERR_ARGUMENT, head + "null colour steps");
+  if (nch < 1 || nch > 4) return fail(EU_ERR_ARGUMENT, head + "channels must be 1..4");
+  if (width < 0 || (size_t)width * nch > (size_t(1) << 28)) return fail(EU_ERR_ARGUMENT, head + "rows of 0 .. 2^28 samples");
+  if (out_row_stride_bytes < (size_t)width * nch * (enc->bits / 8)) return fail(EU_ERR_ARGUMENT, head + "row stride smaller than a row");
+  if (enc->bits == 16 && (reinterpret_cast<uintptr_t>(out) % 2 || out_row_stride_bytes % 2))
+    return fail(EU_ERR_ARGUMENT, head + "16-bit samples lie at even addresses: out and its row stride are multiples of 2");
+  int rc;
+  if ((rc = check_steps(enc->colour_steps, enc->bits, who, "colour"))) return rc;
+  if (enc->alpha_steps && (rc = check_steps(enc->alpha_steps, enc->bits, who, "alpha"))) return rc;
+  return EU_OK;
+}
+
+// The tables of `enc` into g.esteps, in front of the work this call queues on `st`. The buffers of the sample entry
+// points (tables, frame buffer, staging) are about to be used on `st`: the stream of the last call that used them
+// has to be through, as for the view buffers (wait_for_view_buffers). The upload reads the library's own host copy,
+// never the caller's memory; tables equal to the last ones are not sent again.
+static int upload_steps(const eu_encode *enc, hipStream_t st)
+{
+  if (g.encode_user && g.encode_user != st) HIPCHK(hipStreamSynchronize(g.encode_user));
+  g.encode_user = st;
+  const size_t n = size_t(1) << enc->bits;
+  const float *alpha = enc->alpha_steps ? enc->alpha_steps : enc->colour_steps;
+  if (g.esteps.p && g.esteps_host.size() == 2 * n && !memcmp(g.esteps_host.data(), enc->colour_steps, n * sizeof(float)) &&
+      !memcmp(g.esteps_host.data() + n, alpha, n * sizeof(float)))
+    return EU_OK;
+  // work queued on `st` earlier may still read the device tables, and their upload the host copy
+  HIPCHK(hipStreamSynchronize(st));
+  g.esteps_host.assign(enc->colour_steps, enc->colour_steps + n);
+  g.esteps_host.insert(g.esteps_host.end(), alpha, alpha + n);
+  hipError_t e = g.esteps.reserve(2 * n);
+  if (e == hipSuccess) e = hipMemcpyAsync(g.esteps.p, g.esteps_host.data(), 2 * n * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    g.esteps_host.clear();
+    return fail(EU_ERR_NO_DEVICE, std::string("step tables: ") + hipGetErrorString(e));
+  }
+  return EU_OK;
+}
+
+static int check_render_sources(const eu_target *trg, eu_source *const *srcs, int nsrc)
+{
+  if (nsrc > 1 && trg->stage) return fail(EU_ERR_ARGUMENT, "stage outputs exist for single-facet jobs only");
+  for (int f = 0; f < nsrc; f++) {
+    if (!srcs[f]) return fail(EU_ERR_HANDLE, "null source");
+    // a masking job adapts channel counts with mono_t, which knows 1 and 2 output channels only
+    // (environment.h:1339: the reference asserts)
+    if (srcs[f]->fct.mask_paint && srcs[f]->nch != trg->nchannels && trg->nchannels > 2 && !trg->stage)
+      return fail(EU_ERR_ARGUMENT, "--mask_for: facets whose channel count differs from the target's need a 1- or 2-channel target");
+  }
+  return EU_OK;
+}
+
+// The job of eu_hip_render and of eu_hip_render_samples behind their argument checks: `out` receives rows of
+// row_bytes bytes - floats or packed words, or, with `enc`, integer samples.
+static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out, size_t row_bytes,
+                        size_t out_row_stride_bytes, int out_on_device, void *stream, const eu_encode *enc)
+{
+  int rc;
+  hipStream_t st = stream ? (hipStream_t)stream : g.stream;
+  // g.last_user still names the PREVIOUS job's stream while this job is set up: build_params / build_multi wait
+  // for it before they rewrite tables that job may be reading (it used to be overwritten here, so a job on another
+  // stream rewrote the tables under the previous one: tests/test_gpu_round3_switches.py)
+  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
+  const eu_switches sw = eu_read_switches();
+  if (enc && (rc = upload_steps(enc, st))) return rc;
+  if (out_on_device) return render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc);
+  const size_t rows = (size_t)(trg->row_end - trg->row_begin);
+  if (!rows) return EU_OK;
+  HIPCHK(g.stage.reserve((rows * row_bytes + sizeof(float) - 1) / sizeof(float)));
+  // The frame goes to the host in up to four row chunks: every chunk is a launch of its own
+  // on `st`, and its copy (second stream, behind the chunk's event) runs while the later
+  // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
+  // whole cost, the kernels hide under the first copy. Samples: the encode runs behind each chunk's render,
+  // and the link carries a quarter or half of the bytes.
+  const size_t nchunk = rows >= 1024 ? 4 : 1;
+  if (!g.copy) HIPCHK(hipStreamCreateWithFlags(&g.copy, hipStreamNonBlocking));
+  for (size_t c = 0; c < 4; c++)
+    if (!g.chunk_done[c]) HIPCHK(hipEventCreateWithFlags(&g.chunk_done[c], hipEventDisableTiming));
+  const size_t per = ((rows + nchunk - 1) / nchunk + 7) / 8 * 8;
+  // whatever happens below, nothing of this call may still write into `out` or read g.stage.p when it returns
+  struct drain { hipStream_t a, b; ~drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain_on_exit{ g.copy, st };
+  for (size_t c = 0; c < nchunk; c++) {
+    const size_t a = std::min(rows, c * per), b = std::min(rows, (c + 1) * per);
+    if (a >= b) break;
+    eu_target tc = *trg;
+    tc.row_begin = trg->row_begin + (int)a;
+    tc.row_end = trg->row_begin + (int)b;
+    char *dst = (char *)g.stage.p + a * row_bytes;
+    if ((rc = render_on_device(&tc, srcs, nsrc, (float *)dst, row_bytes, sw, st, enc))) return rc;
+    HIPCHK(hipEventRecord(g.chunk_done[c], st));
+    HIPCHK(hipStreamWaitEvent(g.copy, g.chunk_done[c], 0));
+    HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, row_bytes,
+                            row_bytes, b - a, hipMemcpyDeviceToHost, g.copy));
+  }
+  HIPCHK(hipStreamSynchronize(g.copy));
+  HIPCHK(hipStreamSynchronize(st));
   return EU_OK;
 }
 
@@ -1355,49 +1494,80 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
   const size_t min_stride = (size_t)frame_w(trg) * och * sizeof(float);
   if (out_row_stride_bytes < min_stride) return fail(EU_ERR_ARGUMENT, "row stride smaller than a row");
   if (out_row_stride_bytes % sizeof(float)) return fail(EU_ERR_ARGUMENT, "row stride must be a multiple of 4 bytes");
-  if (nsrc > 1 && trg->stage) return fail(EU_ERR_ARGUMENT, "stage outputs exist for single-facet jobs only");
-  for (int f = 0; f < nsrc; f++) {
-    if (!srcs[f]) return fail(EU_ERR_HANDLE, "null source");
-    // a masking job adapts channel counts with mono_t, which knows 1 and 2 output channels only
-    // (environment.h:1339: the reference asserts)
-    if (srcs[f]->fct.mask_paint && srcs[f]->nch != trg->nchannels && trg->nchannels > 2 && !trg->stage)
-      return fail(EU_ERR_ARGUMENT, "--mask_for: facets whose channel count differs from the target's need a 1- or 2-channel target");
-  }
+  if ((rc = check_render_sources(trg, srcs, nsrc))) return rc;
+  return render_frame(trg, srcs, nsrc, out, min_stride, out_row_stride_bytes, out_on_device, stream, nullptr);
+}
+
+int eu_hip_render_samples(const eu_target *trg, eu_source *const *srcs, int nsrc, const eu_encode *enc, void *out,
+                          size_t out_row_stride_bytes, int out_on_device, void *stream)
+{
+  int rc;
+  if (!trg) return fail(EU_ERR_ARGUMENT, "render_samples: null target");
+  if (!srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "render_samples: no source / no output");
+  if ((rc = check_target(trg))) return rc;
+  if (trg->stage) return fail(EU_ERR_ARGUMENT, "render_samples: stage outputs are float only");
+  if (trg->out_format != EU_OUT_FLOAT) return fail(EU_ERR_ARGUMENT, "render_samples: EU_OUT_SRGBA8 is a format of its own, not a frame to encode");
+  if ((rc = check_encode("render_samples", enc, frame_w(trg), trg->nchannels, out, out_row_stride_bytes))) return rc;
+  if ((rc = check_render_sources(trg, srcs, nsrc))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (trg->row_end == trg->row_begin) return EU_OK;
+  const size_t row_bytes = (size_t)frame_w(trg) * trg->nchannels * (enc->bits / 8);
+  return render_frame(trg, srcs, nsrc, out, row_bytes, out_row_stride_bytes, out_on_device, stream, enc);
+}
+
+// bytes (frame and samples together) of one staged chunk of an eu_hip_encode_samples call with a host buffer
+#define EU_ENCODE_CHUNK_BYTES ((size_t)64 << 20)
+
+int eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int frame_on_device, int width, int height,
+                          int nchannels, const eu_encode *enc, void *out, size_t out_row_stride_bytes, int out_on_device,
+                          void *stream)
+{
+  int rc;
+  if (!frame) return fail(EU_ERR_ARGUMENT, "encode_samples: null argument");
+  if (height < 0) return fail(EU_ERR_ARGUMENT, "encode_samples: negative height");
+  if ((rc = check_encode("encode_samples", enc, width, nchannels, out, out_row_stride_bytes))) return rc;
+  const size_t in_row = (size_t)width * nchannels * sizeof(float), out_row = (size_t)width * nchannels * (enc->bits / 8);
+  if (frame_row_stride_bytes < in_row) return fail(EU_ERR_ARGUMENT, "encode_samples: frame row stride smaller than a row");
+  if (frame_row_stride_bytes % sizeof(float) || reinterpret_cast<uintptr_t>(frame) % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "encode_samples: the frame and its row stride are multiples of 4 bytes");
+  if (!width || !height) return EU_OK;
+  if ((rc = ensure_init())) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  // g.last_user still names the PREVIOUS job's stream while this job is set up: build_params / build_multi wait
-  // for it before they rewrite tables that job may be reading (it used to be overwritten here, so a job on another
-  // stream rewrote the tables under the previous one: tests/test_gpu_round3_switches.py)
   struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
-  const eu_switches sw = eu_read_switches();
-  if (out_on_device) return render_on_device(trg, srcs, nsrc, out, out_row_stride_bytes, sw, st);
-  const size_t rows = (size_t)(trg->row_end - trg->row_begin);
-  if (!rows) return EU_OK;
-  HIPCHK(g.stage.reserve(rows * frame_w(trg) * och));
-  // The frame goes to the host in up to four row chunks: every chunk is a launch of its own
-  // on `st`, and its copy (second stream, behind the chunk's event) runs while the later
-  // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
-  // whole cost, the kernels hide under the first copy.
-  const size_t nchunk = rows >= 1024 ? 4 : 1;
-  if (!g.copy) HIPCHK(hipStreamCreateWithFlags(&g.copy, hipStreamNonBlocking));
-  for (size_t c = 0; c < 4; c++)
-    if (!g.chunk_done[c]) HIPCHK(hipEventCreateWithFlags(&g.chunk_done[c], hipEventDisableTiming));
-  const size_t per = ((rows + nchunk - 1) / nchunk + 7) / 8 * 8;
-  // whatever happens below, nothing of this call may still write into `out` or read g.stage.p when it returns
-  struct drain { hipStream_t a, b; ~drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain_on_exit{ g.copy, st };
-  for (size_t c = 0; c < nchunk; c++) {
-    const size_t a = std::min(rows, c * per), b = std::min(rows, (c + 1) * per);
-    if (a >= b) break;
-    eu_target tc = *trg;
-    tc.row_begin = trg->row_begin + (int)a;
-    tc.row_end = trg->row_begin + (int)b;
-    float *dst = g.stage.p + a * frame_w(trg) * och;
-    if ((rc = render_on_device(&tc, srcs, nsrc, dst, min_stride, sw, st))) return rc;
-    HIPCHK(hipEventRecord(g.chunk_done[c], st));
-    HIPCHK(hipStreamWaitEvent(g.copy, g.chunk_done[c], 0));
-    HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, min_stride,
-                            min_stride, b - a, hipMemcpyDeviceToHost, g.copy));
+  if ((rc = upload_steps(enc, st))) return rc;
+  eu_encode_params ep {};
+  ep.tables = g.esteps.p;
+  ep.w = width; ep.nch = nchannels; ep.bits = enc->bits; ep.big_endian = enc->big_endian;
+  if (frame_on_device && out_on_device) {
+    ep.src = frame; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.dst = out; ep.dst_stride_bytes = out_row_stride_bytes;
+    ep.h = height;
+    if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    return EU_OK;
   }
-  HIPCHK(hipStreamSynchronize(g.copy));
+  // A host buffer on either side: the rows go through in chunks of bounded size - copy in, encode, copy out, in
+  // order on `st`; the call returns when `out` is complete
+  const int ch = (int)std::min<size_t>((size_t)height, std::max<size_t>(1, EU_ENCODE_CHUNK_BYTES / (in_row + out_row)));
+  if (!frame_on_device) HIPCHK(g.eframe.reserve((size_t)ch * width * nchannels));
+  if (!out_on_device) HIPCHK(g.eout.reserve(((size_t)ch * out_row + 3) / 4));
+  // whatever happens below, nothing of this call may still read `frame` or write `out` when it returns
+  struct drain { hipStream_t a; ~drain() { (void)hipStreamSynchronize(a); } } drain_on_exit{ st };
+  for (int y0 = 0; y0 < height; y0 += ch) {
+    const int h = std::min(ch, height - y0);
+    const char *fin = (const char *)frame + (size_t)y0 * frame_row_stride_bytes;
+    char *fout = (char *)out + (size_t)y0 * out_row_stride_bytes;
+    ep.src = (const float *)fin; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.dst = fout; ep.dst_stride_bytes = out_row_stride_bytes;
+    ep.h = h;
+    if (!frame_on_device) {
+      ep.src = g.eframe.p; ep.src_stride_bytes = in_row;
+      HIPCHK(hipMemcpy2DAsync(g.eframe.p, in_row, fin, frame_row_stride_bytes, in_row, (size_t)h, hipMemcpyHostToDevice, st));
+    }
+    if (!out_on_device) { ep.dst = g.eout.p; ep.dst_stride_bytes = out_row; }
+    if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    if (!out_on_device)
+      HIPCHK(hipMemcpy2DAsync(fout, out_row_stride_bytes, g.eout.p, out_row, out_row, (size_t)h, hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(hipStreamSynchronize(st));
   return EU_OK;
 }

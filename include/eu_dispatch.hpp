@@ -123,6 +123,12 @@ struct arguments : public facet_base
   int nfacets = 0;
   std::vector<facet_spec> facet_spec_v;
   float *p_output = nullptr;      // width x height x nchannels floats (crop size if store_cropped)
+  // the same frame as integer samples, encoded on the device (eu_hip_render_samples): when p_output_samples is set,
+  // payload() writes width x height x nchannels samples of output_encode.bits bits there instead of floats, through
+  // output_encode's step tables. --ray_map jobs and hosts with several GPUs (hip_dispatch::device_slots() > 1) keep
+  // the float route: payload() refuses p_output_samples for them, the caller asks before it chooses.
+  void *p_output_samples = nullptr;
+  eu_encode output_encode {};
   // PTO p-line crop (envutil_basic.h:684-687; envutil_payload.cc:440-474)
   bool store_cropped = false;
   int p_crop_x0 = 0, p_crop_x1 = 0, p_crop_y0 = 0, p_crop_y1 = 0;
@@ -239,11 +245,28 @@ struct hip_dispatch : public dispatch_base
     return e;
   }
 
+  // the device slots payload() tiles a frame over (made on first use)
+  static int device_slots()
+  {
+    static const int slots = [] {
+      int n = eu_hip_device_count();
+      if (const char *e = std::getenv("EU_HIP_DEVICES")) n = std::min(n, std::max(1, std::atoi(e)));
+      n = std::min(n, int(EU_MAX_SLOTS));
+      if (n > 1) {
+        std::vector<int> dev(size_t(n), 0);
+        for (int k = 0; k < n; k++) dev[size_t(k)] = k;
+        if (eu_hip_init_devices(dev.data(), n) != 0) n = 1;
+      }
+      return n;
+    }();
+    return slots;
+  }
+
   int payload(int nchannels, int ninputs, projection_t projection) const override
   {
     if (projection != args.projection) return EU_ERR_ARGUMENT;
     if ((ninputs == 9) != !args.twine_spread.empty()) return EU_ERR_ARGUMENT;
-    if (args.tethered ? !args.p_screen_data : !args.p_output) return EU_ERR_ARGUMENT;
+    if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples) return EU_ERR_ARGUMENT;
     // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
     if (args.synopsis != "panorama" && args.synopsis != "hdr_merge") return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
@@ -298,7 +321,8 @@ struct hip_dispatch : public dispatch_base
       srcs.push_back(it->second);
     }
     if (args.p_ray_map) {
-      // `act` alone at the caller's rays: no stepper, no target geometry, no twining
+      // `act` alone at the caller's rays: no stepper, no target geometry, no twining; float output
+      if (!args.p_output) return EU_ERR_ARGUMENT;
       if (srcs.size() != 1 || ninputs != 3 || args.tethered || args.ray_map_width <= 0 || args.ray_map_height <= 0)
         return EU_ERR_ARGUMENT;
       eu_rays r {};
@@ -331,17 +355,7 @@ struct hip_dispatch : public dispatch_base
     // a node with several GPUs: the output rows tiled over all of them behind the same call (one device slot
     // per GPU, the sources replicated by peer copies on first use; eu_hip.h: eu_hip_render_devices).
     // EU_HIP_DEVICES=n limits the slots, =1 keeps the single-device path.
-    static const int slots = [] {
-      int n = eu_hip_device_count();
-      if (const char *e = std::getenv("EU_HIP_DEVICES")) n = std::min(n, std::max(1, std::atoi(e)));
-      n = std::min(n, int(EU_MAX_SLOTS));
-      if (n > 1) {
-        std::vector<int> dev(size_t(n), 0);
-        for (int k = 0; k < n; k++) dev[size_t(k)] = k;
-        if (eu_hip_init_devices(dev.data(), n) != 0) n = 1;
-      }
-      return n;
-    }();
+    const int slots = device_slots();
     if (args.tethered) {
       t.out_format = EU_OUT_SRGBA8;
       if (slots > 1)
@@ -349,6 +363,12 @@ struct hip_dispatch : public dispatch_base
                                      size_t(w) * sizeof(uint32_t), 0);
       return eu_hip_render(&t, srcs.data(), int(srcs.size()), (float *)args.p_screen_data,
                            size_t(w) * sizeof(uint32_t), 0, nullptr);
+    }
+    if (args.p_output_samples) {
+      // integer samples: encoded on the device behind the render, a quarter or half of the float frame's bytes
+      if (slots > 1) return EU_ERR_ARGUMENT;
+      return eu_hip_render_samples(&t, srcs.data(), int(srcs.size()), &args.output_encode, args.p_output_samples,
+                                   size_t(w) * nchannels * size_t(args.output_encode.bits / 8), 0, nullptr);
     }
     if (slots > 1)
       return eu_hip_render_devices(&t, srcs.data(), int(srcs.size()), args.p_output,

@@ -431,6 +431,47 @@ int  eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int n
 int  eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src, float *col_dev_built,
                         float *row_dev_built, float *col_host_built, float *row_host_built);
 
+/* ---- the way out as integer samples ------------------------------------------ */
+/* Float pixels to 8- or 16-bit samples ON THE DEVICE (eu_encode.hip), the mirror of eu_hip_source_load_samples: a
+ * frame leaves as a quarter or half of its float bytes, and the host does no per-sample work. The library knows
+ * no colour spaces and no maxval; a TABLE says it all. With steps = colour_steps, or alpha_steps for the last
+ * channel of 2 or 4:
+ *   code(v) = the number of k in 1 .. (1 << bits) - 1 with v >= steps[k]            (steps[0] is ignored)
+ * A valid table has steps[1 .. m] free of NaN and non-decreasing, m >= 1, and NaN in every entry behind m: codes
+ * above a file's maxval = m are then never produced. Equal neighbours are allowed (a code is skipped). A NaN pixel
+ * fails every compare and is code 0; +inf is code m. Because the code a float becomes by clamp / scale / round
+ * behind a transfer curve is a non-decreasing step function of the float, a host finds steps[k] - the smallest
+ * float whose code is >= k - by bisection over the very expression its float route applies
+ * (include/eu_image_io.hpp: encode_steps), and the device's samples are that route's, bit for bit. */
+typedef struct eu_encode {
+  int32_t bits;              /* 8: uint8_t, 16: uint16_t */
+  int32_t big_endian;        /* bits 16: high byte first, as PNM / PAM store it; 0: host order */
+  const float *colour_steps; /* host, 1 << bits floats */
+  const float *alpha_steps;  /* host, 1 << bits floats: the LAST channel of 2 or 4; NULL: colour_steps for it too */
+} eu_encode;
+/* Any float frame of width x height pixels of nchannels floats, rows frame_row_stride_bytes apart: host memory
+ * (staged to the device in bounded chunks) or, with frame_on_device, device memory read where it lies - the output
+ * of eu_hip_render or eu_hip_render_rays, the N * H rows of an eu_hip_render_views result. `out` receives width *
+ * nchannels samples per row, rows out_row_stride_bytes apart; rows start at any byte (bits 16: any even byte), and
+ * no byte outside the samples of a row is written. With frame and `out` both on the device the call is asynchronous
+ * on `stream` (NULL: the library's) until eu_hip_sync(); otherwise it returns when `out` is complete. The tables go
+ * up in front of the kernel into a buffer of the call's own; the library waits for the stream of the last call that
+ * used it before it rewrites it. EU_ERR_ARGUMENT, before a device is looked for: null pointers, bits other than 8
+ * or 16, nchannels outside 1..4, negative sizes, a stride smaller than a row, float strides that are no multiple of
+ * 4, a 16-bit `out` or stride at an odd byte, an invalid table. width == 0 or height == 0 is EU_OK and writes
+ * nothing. */
+int  eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int frame_on_device,
+                           int width, int height, int nchannels, const eu_encode *enc,
+                           void *out, size_t out_row_stride_bytes, int out_on_device, void *stream);
+/* eu_hip_render with the encode behind it: every job eu_hip_render runs (single- and multi-facet, crops, row_begin /
+ * row_end, bands), `out` receiving what eu_hip_encode_samples makes of that job's float frame, byte for byte. The
+ * float frame goes to the library's frame buffer and never leaves the device; with a host `out` the pipeline of up
+ * to four row chunks is eu_hip_render's, the encode running behind each chunk's render and the copy moving samples.
+ * EU_ERR_ARGUMENT, before a device is looked for: what eu_hip_render and eu_hip_encode_samples refuse, stage != 0
+ * and EU_OUT_SRGBA8. */
+int  eu_hip_render_samples(const eu_target *trg, eu_source *const *srcs, int nsrc, const eu_encode *enc,
+                           void *out, size_t out_row_stride_bytes, int out_on_device, void *stream);
+
 /* device memory helpers for hosts without a HIP binding of their own */
 int  eu_hip_malloc(void **p, size_t bytes);
 int  eu_hip_free(void *p);

@@ -33,6 +33,10 @@
 // sample_tables() the float each sample value becomes on the way read_image() + convert_colour() take it -
 // what eu_hip_source_load_samples wants, which widens and linearises on the device.
 //
+// The way out mirrors it: encode_steps() returns the step tables that tell which sample a float becomes on the way
+// convert_colour() + write_one() take it - what eu_hip_render_samples wants - and write_samples() writes samples
+// that were encoded on the device into the file write_one writes.
+//
 // Header-only, host code, no dependency on the HIP library.
 #ifndef EU_IMAGE_IO_HPP
 #define EU_IMAGE_IO_HPP
@@ -393,6 +397,102 @@ inline bool sample_tables(int bits, int maxval, const std::string &from, const s
   return true;
 }
 
+// The code a float becomes in an integer file (OpenImageIO's float -> unsigned conversion): clamp to [0, 1], scale
+// by maxval, add 0.5, truncate; NaN fails both tests of the clamp and is written as 0. The ONE statement of the
+// quantiser, for write_one and encode_steps.
+inline unsigned quantise_sample(float v, int maxval)
+{
+  v = v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v;
+  return v == v ? unsigned(v * float(maxval) + 0.5f) : 0u;
+}
+
+// float bit patterns in the order of their values: key(-inf) < ... < key(-0) < key(+0) < ... < key(+inf)
+inline uint32_t float_key(float v)
+{
+  uint32_t u;
+  std::memcpy(&u, &v, 4);
+  return u & 0x80000000u ? ~u : u | 0x80000000u;
+}
+inline float key_float(uint32_t k)
+{
+  const uint32_t u = k & 0x80000000u ? k & 0x7fffffffu : ~k;
+  float v;
+  std::memcpy(&v, &u, 4);
+  return v;
+}
+
+// The way out as tables, the mirror of sample_tables: the code Q(v) that convert_colour (`from` -> `to`) followed by
+// write_one's quantiser gives a float is a non-decreasing step function of v, so it is told by its steps - steps[k]
+// is the smallest float with Q >= k, found by bisection over the float keys from -inf to +inf with the very
+// expressions the float route applies (convert_sample, quantise_sample); steps[0] = -inf, and every k > maxval is NaN
+// (eu_hip.h: eu_encode). Q(v) is then the number of k >= 1 with v >= steps[k], which is all eu_hip_encode_samples
+// evaluates. alpha: the same without a curve.
+// Each branch of a transfer curve is monotone if powf is; where two branches meet the code may DROP (to_linear of
+// Rec709 falls from 0.018 to about 0.01794 at 0.081: four codes at maxval 65535, none at 255), and no table can
+// tell such a function. So the builder evaluates Q on the floats either side of every joint - 0.04045f, 0.081f and
+// the smallest v whose to_linear reaches 0.0031308f / 0.018f - and returns false, with a message naming the pair of
+// floats, if the code drops there: the caller then keeps the float route. The tables are filled in either case.
+inline bool encode_steps(int bits, int maxval, const std::string &from, const std::string &to, std::vector<float> &colour,
+                         std::vector<float> &alpha, std::string &err)
+{
+  if ((bits != 8 && bits != 16) || maxval < 1 || maxval >= (1 << bits)) { err = "encode steps: 8 or 16 bits, maxval within them"; return false; }
+  colour_class a, b;
+  bool same;
+  if (!colour_pair(from, to, a, b, same, err)) return false;
+  const size_t n = size_t(1) << bits;
+  const float nan = std::nanf("");
+  const uint32_t lo_key = float_key(-HUGE_VALF), hi_key = float_key(HUGE_VALF);
+  auto q_colour = [&](float v) { return quantise_sample(same ? v : convert_sample(a, b, v), maxval); };
+  auto q_alpha = [&](float v) { return quantise_sample(v, maxval); };
+  auto build = [&](std::vector<float> &steps, auto q) {
+    steps.assign(n, nan);
+    steps[0] = -HUGE_VALF;
+    uint32_t lo = lo_key;
+    for (unsigned k = 1; k <= unsigned(maxval); k++) {
+      // the smallest key in [lo, hi] whose code is >= k; it is not below the step before it
+      uint32_t l = lo, h = hi_key;
+      if (q(key_float(h)) < k) return false;
+      while (l < h) {
+        const uint32_t m = l + (h - l) / 2;
+        if (q(key_float(m)) >= k) h = m; else l = m + 1;
+      }
+      steps[k] = key_float(l);
+      lo = l;
+    }
+    return true;
+  };
+  if (!build(colour, q_colour) || !build(alpha, q_alpha)) { err = "encode steps: " + from + " -> " + to + " does not reach code " + std::to_string(maxval); return false; }
+  if (same) return true;
+  // the joints: of `from`'s curve in v, of `to`'s curve where to_linear(from, v) reaches its threshold
+  std::vector<float> joints;
+  if (a == CSP_SRGB) joints.push_back(0.04045f);
+  if (a == CSP_REC709) joints.push_back(0.081f);
+  if (b == CSP_SRGB || b == CSP_REC709) {
+    const float reach = b == CSP_SRGB ? 0.0031308f : 0.018f;
+    uint32_t l = float_key(0.0f), h = float_key(1.0f);
+    while (l < h) {
+      const uint32_t m = l + (h - l) / 2;
+      if (to_linear(a, key_float(m)) >= reach) h = m; else l = m + 1;
+    }
+    joints.push_back(key_float(l));
+  }
+  for (float j : joints) {
+    const uint32_t kj = float_key(j);
+    for (uint32_t k = kj - 4; k < kj + 4; k++) {
+      const float v0 = key_float(k), v1 = key_float(k + 1);
+      const unsigned c0 = q_colour(v0), c1 = q_colour(v1);
+      if (c1 < c0) {
+        char msg[256];
+        std::snprintf(msg, sizeof msg, "encode steps: %s -> %s at maxval %d is no step function: %.9g has code %u, %.9g code %u",
+                      from.c_str(), to.c_str(), maxval, double(v0), c0, double(v1), c1);
+        err = msg;
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
 inline bool read_image(const std::string &name, std::vector<float> &pixels, int &width, int &height,
                        int &nchannels, std::string &err)
 {
@@ -458,6 +558,31 @@ inline bool read_samples(const std::string &name, std::vector<uint8_t> &samples,
   return true;
 }
 
+// the header of a PNM (P5 / P6) or PAM (P7) file, the metadata as comment lines: for write_one and write_samples
+inline void write_pnm_header(FILE *f, bool pam, int width, int height, int nch, int maxval, const metadata *meta)
+{
+  if (pam) {
+    static const char *const tt[5] = { "", "GRAYSCALE", "GRAYSCALE_ALPHA", "RGB", "RGB_ALPHA" };
+    std::fprintf(f, "P7\n");
+    if (meta && !meta->projection.empty()) std::fprintf(f, "# Projection: %s\n# Hfov: %.9g\n", meta->projection.c_str(), meta->hfov);
+    std::fprintf(f, "WIDTH %d\nHEIGHT %d\nDEPTH %d\nMAXVAL %d\nTUPLTYPE %s\nENDHDR\n", width, height, nch, maxval, tt[nch]);
+  } else {
+    std::fprintf(f, "%s\n", nch == 1 ? "P5" : "P6");
+    if (meta && !meta->projection.empty()) std::fprintf(f, "# Projection: %s\n# Hfov: %.9g\n", meta->projection.c_str(), meta->hfov);
+    std::fprintf(f, "%d %d\n%d\n", width, height, maxval);
+  }
+}
+
+// What write_one makes of a PNM / PAM name, as (bits, maxval): .pgm / .ppm / .pnm hold 8-bit samples, .pam 16-bit
+// ones, big endian. False for every other name - those files take floats.
+inline bool sample_format(const std::string &name, int &bits, int &maxval)
+{
+  const std::string ext = lower_ext(name);
+  if (ext == "pam") { bits = 16; maxval = 65535; return true; }
+  if (ext == "pgm" || ext == "ppm" || ext == "pnm") { bits = 8; maxval = 255; return true; }
+  return false;
+}
+
 inline bool write_one(const std::string &name, const float *src, int width, int height, int nch, std::string &err,
                       const metadata *meta = nullptr)
 {
@@ -497,23 +622,12 @@ inline bool write_one(const std::string &name, const float *src, int width, int 
     const bool pam = ext == "pam";
     if (!pam && nch != 1 && nch != 3) { std::fclose(f); err = name + ": PNM holds 1 or 3 channels; use .pam or .pfm"; return false; }
     const int maxval = pam ? 65535 : 255;
-    if (pam) {
-      static const char *const tt[5] = { "", "GRAYSCALE", "GRAYSCALE_ALPHA", "RGB", "RGB_ALPHA" };
-      std::fprintf(f, "P7\n");
-      if (meta && !meta->projection.empty()) std::fprintf(f, "# Projection: %s\n# Hfov: %.9g\n", meta->projection.c_str(), meta->hfov);
-      std::fprintf(f, "WIDTH %d\nHEIGHT %d\nDEPTH %d\nMAXVAL %d\nTUPLTYPE %s\nENDHDR\n", width, height, nch, maxval, tt[nch]);
-    } else {
-      std::fprintf(f, "%s\n", nch == 1 ? "P5" : "P6");
-      if (meta && !meta->projection.empty()) std::fprintf(f, "# Projection: %s\n# Hfov: %.9g\n", meta->projection.c_str(), meta->hfov);
-      std::fprintf(f, "%d %d\n%d\n", width, height, maxval);
-    }
+    write_pnm_header(f, pam, width, height, nch, maxval, meta);
     std::vector<uint8_t> buf(row * (pam ? 2 : 1));
     for (int y = 0; y < height && ok; y++) {
       const float *s = src + size_t(y) * row;
       for (size_t i = 0; i < row; i++) {
-        float v = s[i];
-        v = v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v;      // NaN fails both tests and is written as 0 below
-        const unsigned q = v == v ? unsigned(v * float(maxval) + 0.5f) : 0u;
+        const unsigned q = quantise_sample(s[i], maxval);
         if (pam) { buf[2 * i] = uint8_t(q >> 8); buf[2 * i + 1] = uint8_t(q & 255u); }
         else buf[i] = uint8_t(q);
       }
@@ -545,6 +659,45 @@ inline bool write_image(const std::string &name, const float *src, int width, in
     return true;
   }
   return write_one(name, src, width, height, nch, err, meta);
+}
+
+// write_one for samples that are already encoded (eu_hip_render_samples): `src` holds width * nch samples per row
+// in the file's own form - bytes for PNM, big-endian shorts for PAM (sample_format) - and the file is, header and
+// metadata included, the one write_one writes from the floats those samples were made of.
+inline bool write_samples_one(const std::string &name, const uint8_t *src, int width, int height, int nch, std::string &err,
+                              const metadata *meta = nullptr)
+{
+  int bits = 0, maxval = 0;
+  if (!sample_format(name, bits, maxval)) { err = name + ": samples go to .pgm, .ppm, .pnm or .pam"; return false; }
+  const bool pam = bits == 16;
+  if (!pam && nch != 1 && nch != 3) { err = name + ": PNM holds 1 or 3 channels; use .pam or .pfm"; return false; }
+  FILE *f = std::fopen(name.c_str(), "wb");
+  if (!f) { err = "cannot create " + name; return false; }
+  write_pnm_header(f, pam, width, height, nch, maxval, meta);
+  const size_t n = size_t(width) * height * nch * size_t(bits / 8);
+  bool ok = std::fwrite(src, 1, n, f) == n;
+  ok = std::fclose(f) == 0 && ok;
+  if (!ok) err = name + ": write failed";
+  return ok;
+}
+
+// write_image for samples: six face files for a cubemap target and a format string, else one file
+inline bool write_samples(const std::string &name, const uint8_t *src, int width, int height, int nch,
+                          bool cubemap, std::string &err, const metadata *meta = nullptr)
+{
+  std::vector<std::string> faces;
+  if (cubemap && name.find('%') != std::string::npos && cubeface_names(name, faces)) {
+    if (height != 6 * width) { err = "a cubemap is 1:6"; return false; }
+    int bits = 0, maxval = 0;
+    if (!sample_format(name, bits, maxval)) { err = name + ": samples go to .pgm, .ppm, .pnm or .pam"; return false; }
+    metadata face_meta;
+    if (meta) { face_meta.projection = "rectilinear"; face_meta.hfov = meta->hfov; }
+    for (int i = 0; i < 6; i++)
+      if (!write_samples_one(faces[size_t(i)], src + size_t(i) * width * width * nch * size_t(bits / 8), width, width, nch, err,
+                             meta ? &face_meta : nullptr)) return false;
+    return true;
+  }
+  return write_samples_one(name, src, width, height, nch, err, meta);
 }
 
 }  // namespace io

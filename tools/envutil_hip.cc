@@ -74,6 +74,56 @@ static int run_payload(const std::string &output)
   if (args.store_cropped) { ow = args.p_crop_x1 - args.p_crop_x0; oh = args.p_crop_y1 - args.p_crop_y0; }
   const bool ray_map = args.p_ray_map != nullptr;            // --ray_map: the output has the map's size
   if (ray_map) { ow = args.ray_map_width; oh = args.ray_map_height; }
+  std::string err;
+  const bool cube = (args.projection == CUBEMAP || args.projection == BIATAN6) && !args.store_cropped && !ray_map;
+  // save_array attaches the target's projection and hfov (degrees) to the file (envutil_basic.h:770-772)
+  io::metadata meta;
+  meta.projection = projection_name[args.projection];
+  meta.hfov = (180.0 / M_PI) * args.hfov;
+
+  // A PNM / PAM output leaves the device as the file's samples (eu_hip_render_samples): the step tables say, for
+  // the way from the working colour space to the output's and the file's maxval, which sample a float becomes by
+  // convert_colour + write_one below - the same bytes, without the float download and the host's pass over them.
+  // A table the builder refuses (a curve whose code drops at a joint), --ray_map and several devices keep that route.
+  int bits = 0, maxval = 0;
+  if (io::sample_format(output, bits, maxval) && !ray_map && !args.tethered && hip_dispatch::device_slots() == 1) {
+    // (the tables of a pair of colour spaces are kept: the jobs of a pipe-mode session share them)
+    struct step_tables { bool ok; std::string why; std::vector<float> colour, alpha; };
+    static std::map<std::string, step_tables> kept;
+    const std::string key = std::to_string(bits) + "/" + args.working_colour_space + "/" + args.colour_space;
+    auto it = kept.find(key);
+    if (it == kept.end()) {
+      step_tables t;
+      t.ok = io::encode_steps(bits, maxval, args.working_colour_space, args.colour_space, t.colour, t.alpha, t.why);
+      it = kept.emplace(key, std::move(t)).first;
+    }
+    const std::vector<float> &colour_steps = it->second.colour, &alpha_steps = it->second.alpha;
+    const std::string &why = it->second.why;
+    if (it->second.ok) {
+      std::vector<uint8_t> samples(size_t(ow) * oh * args.nchannels * size_t(bits / 8));
+      args.output_encode.bits = bits;
+      args.output_encode.big_endian = 1;                     // as PNM / PAM store 16-bit samples
+      args.output_encode.colour_steps = colour_steps.data();
+      args.output_encode.alpha_steps = alpha_steps.data();
+      args.p_output_samples = samples.data();
+      const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
+      args.p_output_samples = nullptr;
+      args.output_encode = eu_encode {};
+      if (rc != 0) {
+        std::fprintf(stderr, "envutil_hip: render failed (%d): %s\n", rc, eu_hip_last_error());
+        return 1;
+      }
+      if (!io::write_samples(output, samples.data(), ow, oh, args.nchannels, cube, err, &meta)) {
+        std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+        return 1;
+      }
+      if (args.verbose)
+        std::printf("saved %s (%d x %d x %d): %d-bit samples, encoded on the device\n", output.c_str(), ow, oh, args.nchannels, bits);
+      return 0;
+    }
+    if (args.verbose) std::printf("%s: float pixels, encoded on the host (%s)\n", output.c_str(), why.c_str());
+  }
+
   std::vector<float> out(size_t(ow) * oh * args.nchannels);
   args.p_output = out.data();
   const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
@@ -82,12 +132,6 @@ static int run_payload(const std::string &output)
     std::fprintf(stderr, "envutil_hip: render failed (%d): %s\n", rc, eu_hip_last_error());
     return 1;
   }
-  std::string err;
-  const bool cube = (args.projection == CUBEMAP || args.projection == BIATAN6) && !args.store_cropped && !ray_map;
-  // save_array attaches the target's projection and hfov (degrees) to the file (envutil_basic.h:770-772)
-  io::metadata meta;
-  meta.projection = projection_name[args.projection];
-  meta.hfov = (180.0 / M_PI) * args.hfov;
   // save_array: from the working colour space to the output's where they differ (envutil_basic.h:786-812)
   if (!io::convert_colour(out.data(), size_t(ow) * oh, args.nchannels, args.working_colour_space, args.colour_space, err)) {
     std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
