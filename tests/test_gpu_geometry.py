@@ -18,6 +18,7 @@ import pytest
 import envutil_amd as ea
 import euo
 import jobs
+from definitions64 import cube_ray, extent, planar_to_ray, rot, target_rays_f64, unit
 from test_gpu_parity import make_pair
 
 pytestmark = pytest.mark.gpu
@@ -94,75 +95,11 @@ def test_edge_rays_source_coordinate_bit_exact(prj, w, h, hfov):
         assert not flagged[ordinary].any()
 
 
-# ---------------------------------------------------------------------------
-# float64 formulations, written from the definitions
-# ---------------------------------------------------------------------------
-
-def rot(roll, pitch, yaw):
-    """camera orientation: yaw to the right about DOWN, pitch upward about RIGHT, roll clockwise
-    about FORWARD, applied roll first (column vectors): R = Ry(yaw) Rx(pitch) Rz(roll)"""
-    cy, sy, cp, sp, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll), math.sin(roll)
-    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
-    rz = np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
-    return ry @ rx @ rz
-
-
-def planar_to_ray(prj, px, py):
-    """pixel-centre planar coordinates -> ray (RIGHT, DOWN, FORWARD), float64"""
-    if prj == ea.SPHERICAL:
-        return np.stack([np.cos(py) * np.sin(px), np.sin(py), np.cos(py) * np.cos(px)], -1)
-    if prj == ea.CYLINDRICAL:
-        return np.stack([np.sin(px), py, np.cos(px)], -1)
-    if prj == ea.RECTILINEAR:
-        return np.stack([px, py, np.ones_like(px)], -1)
-    r = np.hypot(px, py)
-    theta = r if prj == ea.FISHEYE else 2.0 * np.arctan(r / 2.0)       # stereographic: r = 2 tan(theta / 2)
-    phi = np.arctan2(px, py)                                           # from the DOWN axis towards RIGHT
-    return np.stack([np.sin(theta) * np.sin(phi), np.sin(theta) * np.cos(phi), np.cos(theta)], -1)
-
-
-def cube_ray(face, in0, in1):
-    """in-face coordinates in [-1, 1] -> ray; faces LEFT0 RIGHT1 TOP2 BOTTOM3 FRONT4 BACK5"""
-    one = np.ones_like(in0)
-    table = [(-one, in1, in0), (one, in1, -in0), (-in0, -one, -in1), (-in0, one, in1), (in0, in1, one), (-in0, in1, -one)]
-    out = np.zeros(in0.shape + (3,))
-    for f, (x, y, z) in enumerate(table):
-        m = face == f
-        out[m] = np.stack([x, y, z], -1)[m]
-    return out
-
-
-def unit(v):
-    return v / np.linalg.norm(v, axis=-1, keepdims=True)
-
-
-def extent(prj, w, h, hfov):
-    """half extents from the definitions: the planar x of a ray hfov / 2 to the right, square pixels"""
-    t = hfov / 2.0
-    x1 = {ea.SPHERICAL: t, ea.CYLINDRICAL: t, ea.FISHEYE: t, ea.RECTILINEAR: math.tan(t),
-          ea.STEREOGRAPHIC: 2.0 * math.tan(t / 2.0), ea.CUBEMAP: math.tan(t), ea.BIATAN6: math.tan(t)}[prj]
-    return x1, x1 * h / w
-
+# the float64 formulations, written from the definitions, live in tests/definitions64.py
 
 TARGETS = [(ea.SPHERICAL, 120, 60, 360.0), (ea.CYLINDRICAL, 100, 50, 200.0), (ea.RECTILINEAR, 90, 70, 95.0),
            (ea.STEREOGRAPHIC, 80, 80, 200.0), (ea.FISHEYE, 80, 60, 180.0), (ea.CUBEMAP, 24, 144, 90.0),
            (ea.BIATAN6, 24, 144, 90.0)]
-
-
-def target_rays_f64(prj, w, h, hfov_deg):
-    x1, y1 = extent(prj, w, h, math.radians(hfov_deg))
-    xs = -x1 + (np.arange(w) + 0.5) * (2 * x1 / w)
-    ys = -y1 + (np.arange(h) + 0.5) * (2 * y1 / h)
-    px, py = np.meshgrid(xs, ys)
-    if prj in (ea.CUBEMAP, ea.BIATAN6):
-        face = (np.arange(h) // w)[:, None] + np.zeros((1, w), int)
-        in1 = py + (5 - 2 * face) * x1          # the face's own vertical coordinate in [-x1, x1]
-        in0 = px
-        if prj == ea.BIATAN6:
-            in0, in1 = np.tan(in0 * math.pi / 4.0), np.tan(in1 * math.pi / 4.0)
-        return cube_ray(face, in0, in1)
-    return planar_to_ray(prj, px, py)
 
 
 @pytest.mark.parametrize("tprj,tw,th,thfov", TARGETS)
