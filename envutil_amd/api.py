@@ -1015,7 +1015,7 @@ def launch_count():
 
 
 def sync():
-    """eu_hip_sync: wait for the library's stream and the stream of the last asynchronous call"""
+    """eu_hip_sync: wait for the library's stream and for what every call so far has left on a caller's stream"""
     _check(lib().eu_hip_sync())
 
 

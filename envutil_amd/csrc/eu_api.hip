@@ -74,11 +74,14 @@ struct context {
   unsigned long long launches = 0;                // render kernel launches so far
   eu_src_dev seg_sd;
   eu_dev_buf<float> stage;                        // host-output staging
-  hipStream_t last_user = nullptr;                // caller's stream of the last render (eu_hip_sync waits on it too)
   eu_dev_buf<eu_generic> mgen;                    // multi-facet jobs: the translated facets' transformations
   float *inv_coef = nullptr;                      // --single: the inverse lens model's coefficients (eu_inv_planar)
-  hipEvent_t wl_done = nullptr;                   // behind the last staged launch pair (its work list is free again)
-  hipStream_t wl_stream = nullptr; bool wl_stream_set = false;
+  // who may still read the buffers that outlive a call, on a caller's stream ("Buffers that outlive a call")
+  eu_readers tables;                              // col/row/taps, mcol/mrow/mtaps/msrc/mrej/mgen, inv_coef, scr
+  eu_readers wl_pair;                             // wl and the staged kernels' cached plans: behind EVERY launch pair
+  eu_readers rays, views, encode, alpha;          // rtaps | vscal/vcol/vrow/vtaps/vsrc | esteps | aplan
+  bool encode_own = false;                        // the library's own stream has used scr or esteps since a caller's
+                                                  // stream last waited for it (it leaves no event: order_encoders)
   hipStream_t copy = nullptr;                     // D2H of a host-output frame, chunk by chunk
   hipEvent_t chunk_done[4] = { nullptr, nullptr, nullptr, nullptr };
   eu_dev_buf<int> wl;                             // eu_render4.hip work list (count, done, tile ids)
@@ -104,17 +107,13 @@ struct context {
   eu_dev_buf<float> vcol, vrow, vtaps, vstage;
   eu_dev_buf<eu_src_dev> vsrc;                    // eu_hip_render_views_multi: the facets' evaluator parameters
   std::vector<float> vtaps_host;                  // what vtaps holds
-  hipStream_t views_user = nullptr;               // the stream the last call worked on with these buffers (last_user is
-                                                  // one slot for all entry points: a render in between overwrites it)
   // eu_hip_encode_samples / eu_hip_render_samples: the step tables on the device (colour, then alpha), the host copy
   // they were uploaded from - it stays, so that an upload queued on a stream never reads a caller's memory after the
   // call, and equal tables are not sent again - and the staging of a host frame and of a host output
   eu_dev_buf<float> esteps, eframe;
   eu_dev_buf<uint32_t> eout;
   std::vector<float> esteps_host;
-  hipStream_t encode_user = nullptr;              // the stream the last call worked on with these buffers (as views_user)
   eu_dev_buf<int32_t> aplan;                      // row plan of the last device alpha edit
-  hipStream_t aplan_user = nullptr;               // the stream that edit runs on, while it may still read the plan
 };
 // One context per device SLOT. A process that never calls eu_hip_init_devices has one slot (one process per
 // GPU, the set-up bench.py's multi-rank runs use); eu_hip_init_devices makes a slot per listed device, and every
@@ -129,6 +128,19 @@ int nslots_ = 1, cur_slot_ = 0;
     if (e_ != hipSuccess)                                                     \
       return fail(EU_ERR_NO_DEVICE, std::string(#call ": ") + hipGetErrorString(e_)); \
   } while (0)
+
+// the end of a call with result `rc` that may have left work on a caller's stream (null: the library's own, no event)
+int note_caller(eu_readers &r, void *stream, int rc)
+{
+  const hipError_t e = stream ? r.note((hipStream_t)stream) : hipSuccess;
+  return rc || e == hipSuccess ? rc : fail(EU_ERR_NO_DEVICE, std::string("stream order: ") + hipGetErrorString(e));
+}
+
+// whatever happens after this, nothing of the call may still use the caller's host memory or a staging buffer when it returns
+struct drain {
+  hipStream_t a, b; bool on = true;
+  ~drain() { if (on) { (void)hipStreamSynchronize(a); if (b != a) (void)hipStreamSynchronize(b); } }
+};
 
 int set_slot(int k)
 {
@@ -433,7 +445,7 @@ int build_inv_planar(const eu_target *t, eu_inv_planar *q)
     std::vector<float> coef;
     if (!eu::make_inverse_lcp(f->a, f->b, f->c, std::sqrt(1 + aspect * aspect), 100, coef, q->rr_max))
       return fail(EU_ERR_ARGUMENT, "--single: the lens polynomial has no inverse over the facet (the reference asserts here)");
-    if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
+    HIPCHK(g.tables.host_wait());
     if (!g.inv_coef) HIPCHK(hipMalloc((void **)&g.inv_coef, 128 * sizeof(float)));
     HIPCHK(hipMemcpyAsync(g.inv_coef, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -515,8 +527,8 @@ int build_params(const eu_target *t, eu_source *const *srcs, int nsrc, float *ou
     eu::stepper_tables tb;
     if (!eu::build_stepper_tables(*t, basis, twine, twine, tb))
       return fail(EU_ERR_UNSUPPORTED, "no stepper for this target projection");
-    // a kernel of the previous job may still read the tables on the caller's stream
-    if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
+    // kernels of earlier jobs may still read the tables on callers' streams (the library's own has the copies behind them)
+    HIPCHK(g.tables.host_wait());
     HIPCHK(g.col.reserve(tb.col.size()));
     HIPCHK(g.row.reserve(tb.row.size()));
     HIPCHK(hipMemcpyAsync(g.col.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, g.stream));
@@ -634,7 +646,7 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
   }
   const bool twine = t->ntaps > 0;
   std::vector<unsigned char> key = plan_key_of(t, srcs, nsrc, true);
-  if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));   // g.msrc and the tables are rewritten below
+  HIPCHK(g.tables.host_wait());   // g.msrc and the tables are rewritten below
   if (key != g.mplan_key) {
     eu::mat3 r_cam = eu::make_r3(t->roll, t->pitch, t->yaw, false);
     std::vector<float> rows;
@@ -777,21 +789,17 @@ int launch_staged(const eu_render_params *p, const eu_switches &sw, hipStream_t 
   // smaller job behind a larger one finds the lists emptied by the larger one's last workgroup
   const size_t need = eu_render4_worklist_ints((size_t)ntiles);
   if (g.wl.cap < need) {
-    if (g.wl.reserve(need) != hipSuccess) return -1;
+    if (g.wl_pair.host_wait() != hipSuccess || g.wl.reserve(need) != hipSuccess) return -1;
     if (hipMemsetAsync(g.wl.p, 0, eu_render4_worklist_header_ints() * sizeof(int), st) != hipSuccess) { g.wl.cap = 0; return -1; }
   }
   eu_render_params q = *p;
   q.wl = g.wl.p;
-  // the work list and the persistent kernel's queues belong to ONE launch pair at a time: a job on another
-  // stream than the last staged job's waits for that job's event (same stream: stream order does it)
-  if (g.wl_stream_set && g.wl_stream != st && g.wl_done)
-    if (hipStreamWaitEvent(st, g.wl_done, 0) != hipSuccess) return -1;
+  // the work list, the persistent kernel's queues and the cached plans belong to ONE launch pair at a time: `st` waits
+  // for the pair before, the event moves behind this one - on any stream, for eu_hip_listed_tiles() the library's own too
+  if (g.wl_pair.order_after(st) != hipSuccess) return -1;
   const int rc = eu_launch_render4(&q, &sw, g.h_row.data(), g.h_row.size(), g.plan_gen, st, launches);
   if (rc || !*launches) return rc;
-  if (!g.wl_done && hipEventCreateWithFlags(&g.wl_done, hipEventDisableTiming) != hipSuccess) return -1;
-  if (hipEventRecord(g.wl_done, st) != hipSuccess) return -1;
-  g.wl_stream = st; g.wl_stream_set = true;
-  return 0;
+  return g.wl_pair.note(st) != hipSuccess ? -1 : 0;
 }
 
 // the packed kernel, one launch per run of rows that want the same work layout (eu_select.h: eu_split_runs)
@@ -871,8 +879,8 @@ int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
     plan.insert(plan.end(), row_start.begin(), row_start.end());
     plan.insert(plan.end(), spans.begin(), spans.end());
   } catch (...) { return fail(EU_ERR_MEMORY, "facet alpha: host memory"); }
-  // an earlier edit on a caller's stream may still read the buffer
-  if (g.aplan_user) { HIPCHK(hipStreamSynchronize(g.aplan_user)); g.aplan_user = nullptr; }
+  // an earlier edit may still read the buffer, on a caller's stream or on the library's own
+  HIPCHK(g.alpha.host_wait());
   HIPCHK(hipStreamSynchronize(g.stream));
   HIPCHK(g.aplan.reserve(plan.size() + 2));
   HIPCHK(hipMemcpy(g.aplan.p, plan.data(), plan.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -1197,8 +1205,7 @@ int eu_hip_facet_alpha_dev(void *pixels_dev, int width, int height, int nchannel
   p.w = width; p.h = height; p.nch = p.src_ch = nchannels;
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
   if (eu_launch_facet_alpha(&p, st)) return fail(EU_ERR_NO_DEVICE, "facet_alpha_dev: kernel launch failed");
-  if (stream) g.aplan_user = st;
-  return EU_OK;
+  return note_caller(g.alpha, stream, EU_OK);
 }
 
 int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
@@ -1312,6 +1319,18 @@ int eu_hip_source_release(eu_source *src)
   return EU_OK;
 }
 
+// `st` is about to use the frame buffer or the step tables, rewriting them or behind a rewrite: it goes behind every
+// earlier job that uses them. On a caller's stream such a job left an event - a render in g.tables, eu_hip_encode_samples
+// in g.encode. The library's own stream leaves none: a caller's stream waits for it by handle, once per change of sides.
+static int order_encoders(hipStream_t st)
+{
+  if (st == g.stream) g.encode_own = true;
+  else if (g.encode_own) { HIPCHK(hipStreamSynchronize(g.stream)); g.encode_own = false; }
+  HIPCHK(g.tables.order_after(st));
+  HIPCHK(g.encode.order_after(st));
+  return EU_OK;
+}
+
 // one job, everything on the device: float pixels straight into out_dev, or float pixels into the library's
 // frame buffer followed by a post-pass that writes out_dev - tethered, the to_screen_t pass and its packed words;
 // with `enc` (its tables are in g.esteps: upload_steps), the encode to integer samples
@@ -1327,10 +1346,11 @@ static int render_on_device(const eu_target *trg, eu_source *const *srcs, int ns
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (screen || enc) {
     if (screen && !g.lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
-    // an encode queued on another stream may still read the frame buffer (upload_steps has waited where enc is set)
-    if (g.encode_user && g.encode_user != st) HIPCHK(hipStreamSynchronize(g.encode_user));
+    // a post-pass queued on another stream may still read the frame buffer (upload_steps has ordered `st` where enc is set)
+    if (screen && (rc = order_encoders(st))) return rc;
     tf.out_format = EU_OUT_FLOAT;
     fstride = (size_t)frame_w(trg) * trg->nchannels * sizeof(float);
+    if (g.scr.cap < rows * frame_w(trg) * trg->nchannels) HIPCHK(g.tables.host_wait());      // reserve() will free it
     HIPCHK(g.scr.reserve(rows * frame_w(trg) * trg->nchannels));
     fout = g.scr.p;
   }
@@ -1396,19 +1416,18 @@ static int check_encode(const char *who, const eu_encode *enc, int width, int nc
 }
 
 // The tables of `enc` into g.esteps, in front of the work this call queues on `st`. The buffers of the sample entry
-// points (tables, frame buffer, staging) are about to be used on `st`: the stream of the last call that used them
-// has to be through, as for the view buffers (wait_for_view_buffers). The upload reads the library's own host copy,
-// never the caller's memory; tables equal to the last ones are not sent again.
+// points (tables, frame buffer) are about to be used on `st`: it goes behind the calls that used them before
+// (order_encoders). The upload reads the library's own host copy, never the caller's memory; tables equal to the last
+// ones are not sent again.
 static int upload_steps(const eu_encode *enc, hipStream_t st)
 {
-  if (g.encode_user && g.encode_user != st) HIPCHK(hipStreamSynchronize(g.encode_user));
-  g.encode_user = st;
+  { int rc = order_encoders(st); if (rc) return rc; }
   const size_t n = size_t(1) << enc->bits;
   const float *alpha = enc->alpha_steps ? enc->alpha_steps : enc->colour_steps;
   if (g.esteps.p && g.esteps_host.size() == 2 * n && !memcmp(g.esteps_host.data(), enc->colour_steps, n * sizeof(float)) &&
       !memcmp(g.esteps_host.data() + n, alpha, n * sizeof(float)))
     return EU_OK;
-  // work queued on `st` earlier may still read the device tables, and their upload the host copy
+  // earlier work may still read the device tables, and their upload the host copy: `st` is behind all of it
   HIPCHK(hipStreamSynchronize(st));
   g.esteps_host.assign(enc->colour_steps, enc->colour_steps + n);
   g.esteps_host.insert(g.esteps_host.end(), alpha, alpha + n);
@@ -1441,13 +1460,10 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
 {
   int rc;
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  // g.last_user still names the PREVIOUS job's stream while this job is set up: build_params / build_multi wait
-  // for it before they rewrite tables that job may be reading (it used to be overwritten here, so a job on another
-  // stream rewrote the tables under the previous one: tests/test_gpu_round3_switches.py)
-  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
   const eu_switches sw = eu_read_switches();
   if (enc && (rc = upload_steps(enc, st))) return rc;
-  if (out_on_device) return render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc);
+  if (out_on_device)
+    return note_caller(g.tables, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc));
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (!rows) return EU_OK;
   HIPCHK(g.stage.reserve((rows * row_bytes + sizeof(float) - 1) / sizeof(float)));
@@ -1461,8 +1477,7 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   for (size_t c = 0; c < 4; c++)
     if (!g.chunk_done[c]) HIPCHK(hipEventCreateWithFlags(&g.chunk_done[c], hipEventDisableTiming));
   const size_t per = ((rows + nchunk - 1) / nchunk + 7) / 8 * 8;
-  // whatever happens below, nothing of this call may still write into `out` or read g.stage.p when it returns
-  struct drain { hipStream_t a, b; ~drain() { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } } drain_on_exit{ g.copy, st };
+  drain drain_on_exit{ g.copy, st };      // a host output leaves nothing behind on `st`
   for (size_t c = 0; c < nchunk; c++) {
     const size_t a = std::min(rows, c * per), b = std::min(rows, (c + 1) * per);
     if (a >= b) break;
@@ -1533,7 +1548,6 @@ int eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int
   if (!width || !height) return EU_OK;
   if ((rc = ensure_init())) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
   if ((rc = upload_steps(enc, st))) return rc;
   eu_encode_params ep {};
   ep.tables = g.esteps.p;
@@ -1543,15 +1557,14 @@ int eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int
     ep.dst = out; ep.dst_stride_bytes = out_row_stride_bytes;
     ep.h = height;
     if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
-    return EU_OK;
+    return note_caller(g.encode, stream, EU_OK);
   }
   // A host buffer on either side: the rows go through in chunks of bounded size - copy in, encode, copy out, in
   // order on `st`; the call returns when `out` is complete
   const int ch = (int)std::min<size_t>((size_t)height, std::max<size_t>(1, EU_ENCODE_CHUNK_BYTES / (in_row + out_row)));
   if (!frame_on_device) HIPCHK(g.eframe.reserve((size_t)ch * width * nchannels));
   if (!out_on_device) HIPCHK(g.eout.reserve(((size_t)ch * out_row + 3) / 4));
-  // whatever happens below, nothing of this call may still read `frame` or write `out` when it returns
-  struct drain { hipStream_t a; ~drain() { (void)hipStreamSynchronize(a); } } drain_on_exit{ st };
+  drain drain_on_exit{ st, st };
   for (int y0 = 0; y0 < height; y0 += ch) {
     const int h = std::min(ch, height - y0);
     const char *fin = (const char *)frame + (size_t)y0 * frame_row_stride_bytes;
@@ -1777,9 +1790,8 @@ unsigned long long eu_hip_listed_tiles(void)
 {
   // the direct-gather kernel's last workgroup leaves the sum of the lists' counters in the header; the event
   // behind the pair is the library's own (the caller's stream may be gone by now)
-  if (!g.wl.p || !g.wl_stream_set || !g.wl_done) return 0;
   int n = 0;
-  if (hipEventSynchronize(g.wl_done) != hipSuccess) return 0;
+  if (!g.wl.p || !g.wl_pair.recorded || g.wl_pair.host_wait() != hipSuccess) return 0;
   if (hipMemcpy(&n, g.wl.p + EU4_WL_LISTED, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return n > 0 ? (unsigned long long)n : 0ull;
 }
@@ -1826,8 +1838,8 @@ static int upload_ray_taps(const eu_rays *r)
   if (g.rtaps.p && taps.size() == g.rtaps_host.size() &&
       !memcmp(taps.data(), g.rtaps_host.data(), taps.size() * sizeof(float)))
     return EU_OK;
-  // an earlier call on a caller's stream may still read the table
-  if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
+  // an earlier call may still read the table, on a caller's stream or on the library's own
+  HIPCHK(g.rays.host_wait());
   HIPCHK(hipStreamSynchronize(g.stream));
   g.rtaps_host.clear();
   HIPCHK(g.rtaps.reserve(taps.size()));
@@ -1866,9 +1878,9 @@ int eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out, size_t out_
   const eu_switches sw = eu_read_switches();
   if ((rc = upload_ray_taps(r))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
   if (r->rays_on_device && out_on_device)
-    return launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out, out_row_stride_bytes, r->width, r->height, st);
+    return note_caller(g.rays, stream, launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out, out_row_stride_bytes,
+                                                   r->width, r->height, st));
   // A host buffer on either side: the grid goes through in chunks of rows - a flat list in chunks of its one
   // row - of bounded size, copy in, launch, copy out, all in order on `st`; the call returns when `out` is complete
   const size_t in_px = (size_t)r->ninputs * sizeof(float), out_px = (size_t)r->nchannels * sizeof(float);
@@ -1878,8 +1890,7 @@ int eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out, size_t out_
   const int ch = flat ? 1 : (int)std::min<size_t>((size_t)r->height, std::max<size_t>(1, px_per_chunk / (size_t)r->width));
   if (!r->rays_on_device) HIPCHK(g.rstage.reserve((size_t)cw * ch * r->ninputs));
   if (!out_on_device) HIPCHK(g.stage.reserve((size_t)cw * ch * r->nchannels));
-  // whatever happens below, nothing of this call may still read `rays` or write `out` when it returns
-  struct drain { hipStream_t a; ~drain() { (void)hipStreamSynchronize(a); } } drain_on_exit{ st };
+  drain drain_on_exit{ st, st };
   for (int y0 = 0; y0 < r->height; y0 += ch)
     for (int x0 = 0; x0 < r->width; x0 += cw) {
       const int w = std::min(cw, r->width - x0), h = std::min(ch, r->height - y0);
@@ -2005,18 +2016,6 @@ static int upload_view_taps(const eu_target *t, hipStream_t st, std::vector<floa
   return EU_OK;
 }
 
-// The library's view buffers are about to be rewritten on `st`: whoever may still read them has to be through -
-// the stream of the last call that used THEM (views_user), and, as for every entry point, the previous call's
-// stream and the library's own. Work on `st` itself is ordered by the stream. Afterwards `st` is their user.
-static int wait_for_view_buffers(hipStream_t st)
-{
-  if (g.views_user && g.views_user != st) HIPCHK(hipStreamSynchronize(g.views_user));
-  if (g.last_user && g.last_user != st && g.last_user != g.views_user) HIPCHK(hipStreamSynchronize(g.last_user));
-  if (g.stream != st && g.stream != g.views_user) HIPCHK(hipStreamSynchronize(g.stream));
-  g.views_user = st;
-  return EU_OK;
-}
-
 // one block per (view, facet), [view][facet]: basis = rotate(r_cam(view), r_fct(facet)), as build_multi forms it
 static void view_scalar_blocks(const eu_target *t, const eu_view *views, int nviews, eu_source *const *srcs, int nsrc,
                                std::vector<eu_view_dev> &sc)
@@ -2071,7 +2070,6 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
       return fail(EU_ERR_HANDLE, multi ? "render_views_multi: a source has no container" : "render_views: the source has no container");
   const eu_switches sw = eu_read_switches();
   hipStream_t st = stream ? (hipStream_t)stream : g.stream;
-  struct note_stream { hipStream_t s; ~note_stream() { g.last_user = s; } } note_on_exit{ stream ? (hipStream_t)stream : nullptr };
 
   const int W = trg->width, H = trg->height;
   // one table block per (view, facet): the columns of a view are those of its first block
@@ -2088,9 +2086,11 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   if (multi)
     for (int f = 0; f < nsrc; f++) sd.push_back(srcs[f]->sd);
   std::vector<float> taps;
-  // whatever happens below, nothing of this call may still read the host vectors or write a host `out` when it returns
-  struct drain { hipStream_t a; bool on; ~drain() { if (on) (void)hipStreamSynchronize(a); } } drain_on_exit{ st, true };
-  if ((rc = wait_for_view_buffers(st))) return rc;
+  drain drain_on_exit{ st, st };          // the host vectors above are among what the call lets go of
+  // the view buffers are rewritten on `st`, and reserve() may free them: the view calls before this one have to be
+  // through, on callers' streams (the event) and on the library's own. The host waits, as it always has here
+  HIPCHK(g.views.host_wait());
+  if (stream) HIPCHK(hipStreamSynchronize(g.stream));
   HIPCHK(g.vcol.reserve(col_floats * per_chunk));
   HIPCHK(g.vrow.reserve(row_floats * per_chunk));
   if (!out_on_device) HIPCHK(g.vstage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
@@ -2101,7 +2101,6 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   if (multi) HIPCHK(hipMemcpyAsync(g.vsrc.p, sd.data(), sd.size() * sizeof(eu_src_dev), hipMemcpyHostToDevice, st));
   if ((rc = upload_view_taps(trg, st, &taps))) return rc;
   HIPCHK(hipStreamSynchronize(st));
-  drain_on_exit.on = !out_on_device;
 
   eu_view_strides vs;
   vs.col = (long long)col_floats; vs.row = (long long)row_floats;
@@ -2123,7 +2122,8 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
                                 hipMemcpyDeviceToHost, st));
   }
   if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
-  return EU_OK;
+  drain_on_exit.on = false;          // a device output stays queued: `st` goes on reading the view buffers
+  return note_caller(g.views, out_on_device ? stream : nullptr, EU_OK);
 }
 
 int eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
@@ -2237,8 +2237,7 @@ int eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src
   }
   std::vector<eu_view_dev> sc;
   view_scalar_blocks(trg, view, 1, &src, 1, sc);
-  if ((rc = wait_for_view_buffers(g.stream))) return rc;
-  struct note_stream { ~note_stream() { g.last_user = nullptr; } } note_on_exit;
+  HIPCHK(g.views.host_wait());
   HIPCHK(g.vcol.reserve(col_floats));
   HIPCHK(g.vrow.reserve(row_floats));
   HIPCHK(g.vscal.reserve(1));
@@ -2270,7 +2269,7 @@ int eu_hip_sync(void)
 {
   if (g.device < 0) return EU_OK;
   HIPCHK(hipStreamSynchronize(g.stream));
-  if (g.last_user) HIPCHK(hipStreamSynchronize(g.last_user));
+  for (const eu_readers *r : { &g.tables, &g.wl_pair, &g.rays, &g.views, &g.encode, &g.alpha }) HIPCHK(r->host_wait());
   return EU_OK;
 }
 

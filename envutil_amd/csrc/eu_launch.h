@@ -49,6 +49,28 @@ template <class T> struct eu_dev_buf {
   }
 };
 
+// Who may still read a family of such buffers on a CALLER's stream: one event of the library's own, recorded behind
+// every call that leaves work on such a stream, so no stream handle outlives the call that brought it. Whoever
+// rewrites the buffers waits first - the host (host_wait: a blocking copy, a reserve() that may free, a host copy
+// an upload still reads) or, where the rewrite is itself queued on a stream, that stream (order_after). The
+// library's own stream records nothing: it is waited for by handle.
+struct eu_readers {
+  hipEvent_t ev = nullptr;
+  bool recorded = false;
+  // One event serves any number of streams: `st` waits for the readers noted before it, then the event moves behind
+  // st's work, so the event's completion still means that ALL of them are through. The wait delays nothing this call
+  // queued, only what `st` gets later; for an event last recorded on `st` itself the runtime does nothing.
+  hipError_t note(hipStream_t st)
+  {
+    hipError_t e = ev ? order_after(st) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ev, st);
+    if (e == hipSuccess) recorded = true;
+    return e;
+  }
+  hipError_t host_wait() const { return recorded ? hipEventSynchronize(ev) : hipSuccess; }
+  hipError_t order_after(hipStream_t st) const { return recorded ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
+};
+
 // The render launchers return 0, or a negative value: -1 a HIP error, -2 a job outside the kernel's
 // coverage (eu_select.h decides before the call, so that is a bug of the caller).
 extern "C" {
@@ -56,7 +78,8 @@ int eu_launch_render(const eu_render_params *p, void *stream);
 int eu_launch_render2(const eu_render_params *p, const eu_switches *sw, void *stream);
 // h_row: the host copy of the plan's row table (whole frame), plan_gen: changes whenever the stepper tables
 // change. *launches: kernels launched for the job - 0 where the plan of a lat/lon job says that the
-// direct-gather kernels are faster (eu_staged_worth; the plan stays cached)
+// direct-gather kernels are faster (eu_staged_worth; the plan stays cached). The cached plans and p->wl belong to
+// one launch pair at a time: the caller has ordered `stream` behind the pair launched before (launch_staged)
 int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const float *h_row, size_t h_row_floats,
                       unsigned long long plan_gen, void *stream, int *launches);
 // path: an eu_ray_path, as eu_select_ray_path() chose it

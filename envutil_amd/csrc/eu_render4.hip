@@ -570,7 +570,6 @@ struct plan_cache {
   int l1_off[9] = {};
   int l1_ecols = 1;
   long long follower_tiles = 0;
-  hipStream_t last_stream = nullptr;   // where the plans were last read
 } g4s[EU_MAX_SLOTS];
 // one cache per device slot (eu_api.hip: eu_hip_init_devices)
 #define g4 (g4s[eu_current_slot()])
@@ -650,12 +649,11 @@ int eu4_build_plans(const eu_render_params &p, int tiles16, const eu_switches &s
     }
   }
   const int nplans = (int)(plans.size() / 4);
+  // the previous launch pair may still read the old plans, on this stream or on another: `st` is ordered behind it
+  // (eu_launch.h), so when `st` is through, that pair is
+  if (hipStreamSynchronize(st) != hipSuccess) return -1;
   if (g4.tileplan.reserve(tp.size()) != hipSuccess) return -1;
   if (g4.coltab.reserve(std::max<size_t>(1, nplans) * (size_t)p.width * EU4_COL_FLOATS) != hipSuccess) return -1;
-  // the previous launch may still read the old plans - on this stream or on the one the plans were last
-  // used on (the library's own stream and a caller's stream alternate)
-  if (hipStreamSynchronize(st) != hipSuccess) return -1;
-  if (g4.last_stream && g4.last_stream != st && hipStreamSynchronize(g4.last_stream) != hipSuccess) return -1;
   if (hipMemcpy(g4.tileplan.p, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return -1;
   g4.planned_rows = 0;
   for (int v : tp) g4.planned_rows += v >= 0;
@@ -827,7 +825,6 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
   eu4_fill_plan(w);
   eu4_followers_plan = g4.follower_tiles;
   eu4_boxtab_tiles_last = w.boxtab ? g4.boxtab_tiles : 0;
-  g4.last_stream = st;
 #ifdef EU5_STAMPS
   return launch4_stamped(p, w, st);
 #else

@@ -19,10 +19,13 @@
  * Threading: like the reference's payload (called on the main thread, global `args`), the
  * library is NOT re-entrant: one host thread at a time, one device per process (the first
  * eu_hip_init or the first call fixes it). A caller-supplied stream orders the KERNELS of a
- * render; the stepper tables of a job are uploaded synchronously before its launch, and the
- * library waits for the previous job's stream before it rewrites them, so jobs on different
- * streams never race on the library's own buffers. eu_hip_sync() waits for the library's
- * stream and for the stream of the last render.
+ * render; the stepper tables of a job are uploaded synchronously before its launch. Behind
+ * every call that leaves work on a caller's stream the library records an event of its own,
+ * and it waits for those events before it rewrites a buffer such work may read, so jobs on
+ * different streams never race on the library's own buffers. No stream handle is kept beyond
+ * the call that brought it: a stream may be destroyed once its own work is done.
+ * eu_hip_sync() waits for the library's stream and for everything any call so far has left
+ * on a caller's stream.
  */
 #ifndef EU_HIP_H
 #define EU_HIP_H
@@ -455,8 +458,8 @@ typedef struct eu_encode {
  * nchannels samples per row, rows out_row_stride_bytes apart; rows start at any byte (bits 16: any even byte), and
  * no byte outside the samples of a row is written. With frame and `out` both on the device the call is asynchronous
  * on `stream` (NULL: the library's) until eu_hip_sync(); otherwise it returns when `out` is complete. The tables go
- * up in front of the kernel into a buffer of the call's own; the library waits for the stream of the last call that
- * used it before it rewrites it. EU_ERR_ARGUMENT, before a device is looked for: null pointers, bits other than 8
+ * up in front of the kernel into a buffer of the call's own; the library orders the upload behind the calls that
+ * used it before, on whatever stream. EU_ERR_ARGUMENT, before a device is looked for: null pointers, bits other than 8
  * or 16, nchannels outside 1..4, negative sizes, a stride smaller than a row, float strides that are no multiple of
  * 4, a 16-bit `out` or stride at an odd byte, an invalid table. width == 0 or height == 0 is EU_OK and writes
  * nothing. */
