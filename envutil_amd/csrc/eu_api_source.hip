@@ -1,0 +1,619 @@
+// C ABI (include/eu_hip.h), host glue: sources - the handle and its container, the alpha edit, the load pipeline.
+
+#include "eu_context.h"
+#include "eu_setup_math.h"
+#include "eu_imageprep.h"
+#include "eu_alpha.h"
+#include "eu_decode.h"
+
+using namespace eu_host;
+
+namespace {
+
+// evaluator + mount parameters (eval.h:2039-2164, environment.h:594-633)
+void fill_src_dev(eu_source *s)
+{
+  eu_src_dev &d = s->sd;
+  const eu_facet &f = s->fct;
+  memset(&d, 0, sizeof d);
+  const eu_container &g0 = s->geom;
+  d.base = s->dev + ((size_t)g0.left[1] * g0.shape[0] + g0.left[0]) * s->nch;
+  d.es0 = s->nch;
+  d.es1 = (long long)s->nch * g0.shape[0];
+  d.prj = f.projection; d.nch = s->nch; d.degree = s->degree;
+  float lo[2], up[2]; int gt[2];
+  for (int a = 0; a < 2; a++) {
+    int bc = s->bc[a];
+    long double l = 0.0L, u = (long double)(g0.core[a] - 1);
+    if (bc == EU_BC_REFLECT || bc == EU_BC_PERIODIC) { l = -0.5L; u += 0.5L; }
+    lo[a] = (float)l; up[a] = (float)u;
+    if (g0.core[a] == 1) { bc = EU_BC_CONSTANT; lo[a] = up[a] = 0.0f; }
+    gt[a] = bc == EU_BC_PERIODIC ? 2 : (bc == EU_BC_MIRROR || bc == EU_BC_REFLECT) ? 1 : 0;
+  }
+  d.gate0 = gt[0]; d.gate1 = gt[1];
+  d.lower0 = lo[0]; d.upper0 = up[0]; d.lower1 = lo[1]; d.upper1 = up[1];
+  d.brighten = (float)f.brighten;
+  d.mask_paint = f.mask_paint;
+  d.recip_step = (float)(1.0 / f.step);
+  d.mask_all = eu_cube_source(f.projection) || (f.projection == EU_FISHEYE && f.hfov >= M_PI * 2.0);
+  eu::weight_matrix(s->degree, d.wm);
+  if (eu_cube_source(f.projection)) return;
+  double te[4], we[4];
+  eu::get_extent(f.projection, f.width, f.height, f.hfov, te);
+  double wx = te[1] - te[0], wy = te[3] - te[2];
+  // environment.h:617-633, including its use of total_width / window_width
+  // in the y terms
+  double px = double(f.window_x_offset) / f.width;
+  double py = double(f.window_y_offset) / f.width;
+  we[0] = te[0] + px * wx; we[2] = te[2] + py * wy;
+  px = double(f.window_x_offset + f.window_width) / f.width;
+  py = double(f.window_y_offset + f.window_width) / f.width;
+  we[1] = te[0] + px * wx; we[3] = te[2] + py * wy;
+  {
+    // process_geometry, envutil_basic.h:499-521; the planar functor is only
+    // installed when the radial polynomial is present (environment.h:1692-1695)
+    double dv = std::fabs(te[3] - te[2]) / 2.0, dh = std::fabs(te[1] - te[0]) / 2.0;
+    d.has_lcp = (f.a != 0.0 || f.b != 0.0 || f.c != 0.0);
+    d.has_shift = d.has_lcp && (f.h != 0.0 || f.v != 0.0);
+    d.has_shear = d.has_lcp && (f.shear_g != 0.0 || f.shear_t != 0.0);
+    d.lens_a = (float)f.a; d.lens_b = (float)f.b; d.lens_c = (float)f.c;
+    d.lens_d = 1.0f - (d.lens_a + d.lens_b + d.lens_c);
+    d.lens_s = (float)((dh < dv) ? dh : dv);
+    d.lens_h = (float)f.h; d.lens_v = (float)f.v;
+    d.shear_g = f.shear_g; d.shear_t = f.shear_t;
+  }
+  d.rej_cos = -2.0f;
+  if (f.projection == EU_RECTILINEAR) {
+    d.rej_cos = 0.0f;                      // the mask includes rz > 0 (environment.h:1135-1137)
+  } else if (f.projection == EU_FISHEYE && !d.has_shear) {
+    // radius after the lens polynomial: |c'| >= r * |sum(r / s)| - |shift|; outside the
+    // window for sure when its larger component (>= |c'| / sqrt 2) exceeds every edge
+    const double W = 1.001 * std::max(std::max(std::fabs(we[0]), std::fabs(we[1])),
+                                      std::max(std::fabs(we[2]), std::fabs(we[3])));
+    const double shift = d.has_shift ? std::hypot((double)d.lens_h, (double)d.lens_v) : 0.0;
+    auto outside = [&](double r) {
+      double sum = 1.0;
+      if (d.has_lcp) {
+        const double x = r / d.lens_s;
+        sum = d.lens_d + d.lens_c * x + d.lens_b * x * x + d.lens_a * x * x * x;
+      }
+      return (r * std::fabs(sum) - shift) / std::sqrt(2.0) > W;
+    };
+    // the smallest angle from which EVERY larger angle is outside
+    double r0 = -1.0;
+    for (double r = M_PI; r >= 0.0; r -= 1e-4) {
+      if (!outside(r)) break;
+      r0 = r;
+    }
+    if (r0 >= 0.0) d.rej_cos = (float)(std::cos(r0) - 1e-4);
+  }
+  d.tex_x0 = te[0]; d.tex_y0 = te[2];
+  d.ext_w = (float)(te[1] - te[0]); d.ext_h = (float)(te[3] - te[2]);
+  d.total_w = (float)f.width; d.total_h = (float)f.height;
+  d.win_x_off = (float)f.window_x_offset; d.win_y_off = (float)f.window_y_offset;
+  d.wex0 = (float)we[0]; d.wex1 = (float)we[1]; d.wex2 = (float)we[2]; d.wex3 = (float)we[3];
+  // hits have 0 <= coordinate - extent.x0 <= extent width: verify the cheap
+  // constant division over that whole range (twice the width for slack)
+  // atan2f returns values in [-0x1.921fb6p+1, 0x1.921fb6p+1]; lat = atan2f(d, s >= 0) in
+  // [-0x1.921fb6p+0, 0x1.921fb6p+0]
+  d.always_hit = f.projection == EU_SPHERICAL && d.wex0 <= -0x1.921fb6p+1f && d.wex1 >= 0x1.921fb6p+1f
+              && d.wex2 <= -0x1.921fb6p+0f && d.wex3 >= 0x1.921fb6p+0f;
+  d.rcp_ext_w = 1.0f / d.ext_w; d.rcp_ext_h = 1.0f / d.ext_h;
+  d.cdiv_ok = eu_verify_const_div(d.ext_w, 2.0f * d.ext_w, cur().stream)
+           && eu_verify_const_div(d.ext_h, 2.0f * d.ext_h, cur().stream);
+}
+
+int check_facet(const eu_facet *f)
+{
+  if (!f) return fail(EU_ERR_ARGUMENT, "null facet");
+  if (f->nchannels < 1 || f->nchannels > 4) return fail(EU_ERR_ARGUMENT, "nchannels must be 1..4");
+  if (f->mask_paint < 0 || f->mask_paint > 2) return fail(EU_ERR_ARGUMENT, "mask_paint must be 0, 1 or 2");
+  if (f->projection < 0 || f->projection > EU_BIATAN6) return fail(EU_ERR_ARGUMENT, "unknown source projection");
+  if (f->width <= 0 || f->height <= 0) return fail(EU_ERR_ARGUMENT, "empty source image");
+  return EU_OK;
+}
+
+// a handle without a container: the facet, the degree and the channel count; nullptr: no host memory
+eu_source *bare_source(const eu_facet *fct, int spline_degree)
+{
+  eu_source *s = new (std::nothrow) eu_source;
+  if (!s) return nullptr;
+  memset(s, 0, sizeof *s);
+  s->fct = *fct;
+  s->degree = spline_degree;
+  s->nch = fct->nchannels;
+  return s;
+}
+
+// allocates the eu_source and its container for the facet
+int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int support_min,
+               int tile_size, eu_source **out)
+{
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  eu_source *s = bare_source(fct, spline_degree);
+  if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
+  const bool cube = eu_cube_source(fct->projection);
+  eu::metrics m {};
+  if (cube) {
+    // IR image: container == core, REFLECT x REFLECT (cubemap.h:576-583)
+    m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+    // The support frame is all the margin the IR has: a ray at a face's edge picks up at left_frame - 0.5, and a
+    // spline of degree d reaches d / 2 + 1 texels beyond that. With less frame than that (--support_min below its
+    // default of 8 AND a small --tile_size) the reference reads outside its IR array (README.md:1553: the frame
+    // is there "so that interpolators needing support can operate without special-casing"); here the job is refused.
+    // Found by the randomised set-up test at seed 1033: biatan6, 45-pixel faces, degree 4, support 1, tile 16 - frame
+    // 1 / 2 - where the oracle and the device each read their own memory in front of the array.
+    const long need = spline_degree / 2 + 1;
+    if (m.left_frame_px + m.inherent_px < need || m.right_frame_px + m.inherent_px < need) {
+      destroy_source(s);
+      return fail(EU_ERR_ARGUMENT, "cubemap support frame (--support_min / --tile_size) too small for the spline degree");
+    }
+    s->geom.shape[0] = s->geom.core[0] = m.section_px;
+    s->geom.shape[1] = s->geom.core[1] = 6 * m.section_px;
+    s->geom.left[0] = s->geom.left[1] = s->geom.right[0] = s->geom.right[1] = 0;
+    s->bc[0] = s->bc[1] = EU_BC_REFLECT;
+  } else {
+    eu::container_geometry(spline_degree, bc0, bc1, fct->window_width, fct->window_height, &s->geom);
+    s->bc[0] = bc0; s->bc[1] = bc1;
+  }
+  s->nfloats = (size_t)s->geom.shape[0] * s->geom.shape[1] * s->nch;
+  // slack behind the container: the LDS-staging kernel (eu_render4.hip) fetches whole
+  // 64-texel instructions, up to 3 rows and 63 texels past a tile's box (never evaluated)
+  const size_t slack = (size_t)4 * s->geom.shape[0] * s->nch + 64 * 4;
+  hipError_t e = hipMalloc((void **)&s->dev, (s->nfloats + slack) * sizeof(float));
+  if (e != hipSuccess) s->dev = nullptr;
+  else e = hipMemset(s->dev + s->nfloats, 0, slack * sizeof(float));
+  if (e != hipSuccess) { destroy_source(s); return fail(EU_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+  fill_src_dev(s);
+  if (cube) {
+    s->sd.refc_md = (float)m.refc_md;
+    s->sd.model_to_px = (float)m.model_to_px;
+    s->sd.section_px = (int)m.section_px;
+  }
+  *out = s;
+  return EU_OK;
+}
+
+// boundary conditions source_t picks (environment.h:638-644)
+void source_bcs(const eu_facet *f, int *bc0, int *bc1)
+{
+  *bc0 = EU_BC_REFLECT; *bc1 = EU_BC_REFLECT;
+  if ((f->projection == EU_SPHERICAL || f->projection == EU_CYLINDRICAL)
+      && std::fabs(f->hfov - 2.0 * M_PI) < .000001)
+    *bc0 = EU_BC_PERIODIC;
+}
+
+// the prefilter source_t picks (environment.h:905-936): a full spherical image gets the two-axis periodic
+// scheme, everything else bspline::prefilter(). A stronger test than source_bcs', and a separate one.
+// (a full-sphere image smaller than its frame - 2 x 1, 4 x 2, 6 x 3 for degree 3 - takes the sequential forms of
+// the pole rows and of the horizontal bracing: eu_setup.hip, pole_rows_seq_kernel / brace_seq_kernel)
+bool full_sphere(const eu_facet *f)
+{
+  return f->projection == EU_SPHERICAL && std::fabs(f->hfov - 2.0 * M_PI) < .000001 && f->width == 2 * f->height;
+}
+
+// ---- PTO masks and lens crops on the device (eu_alpha.hip) ----------------------------------------
+
+// the refusals of eu_hip_facet_alpha, for an eu_facet_edit; *asked: the edit changes anything at all
+int check_edit(const eu_facet_edit *e, int nch, const char *who, bool *asked)
+{
+  const std::string w(who);
+  *asked = false;
+  if (!e) return EU_OK;
+  if (e->npolygons < 0 || (e->npolygons > 0 && !e->polygons) || e->crop_kind < 0 || e->crop_kind > 2)
+    return fail(EU_ERR_ARGUMENT, w + ": polygons / crop kind");
+  for (int i = 0; i < e->npolygons; i++)
+    if (e->polygons[i].n < 0 || (e->polygons[i].n > 0 && (!e->polygons[i].x || !e->polygons[i].y)))
+      return fail(EU_ERR_ARGUMENT, w + ": polygon without vertices");
+  if (e->pixel_channels < 1 || (e->pixel_channels != nch && e->pixel_channels != nch - 1))
+    return fail(EU_ERR_ARGUMENT, w + ": pixel_channels must be the facet's nchannels or one less");
+  *asked = e->npolygons > 0 || e->crop_kind != 0 || e->pixel_channels != nch;
+  if (*asked && nch != 2 && nch != 4)
+    return fail(EU_ERR_ARGUMENT, w + ": a masked or cropped facet has 2 or 4 channels (alpha last)");
+  return EU_OK;
+}
+
+// the row plan of an edit (eu::facet_alpha_rows), uploaded into the context's plan buffer; fills p's tables
+int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
+{
+  std::vector<eu::mask_polygon> ps;
+  for (int i = 0; e && i < e->npolygons; i++) ps.push_back({ e->polygons[i].n, e->polygons[i].x, e->polygons[i].y });
+  std::vector<int> plan, row_start, spans;
+  try {
+    eu::facet_alpha_rows(w, h, ps.data(), int(ps.size()), e ? e->crop_kind : 0, e ? e->crop_x0 : 0, e ? e->crop_x1 : 0,
+                         e ? e->crop_y0 : 0, e ? e->crop_y1 : 0, plan, row_start, spans);
+    plan.insert(plan.end(), row_start.begin(), row_start.end());
+    plan.insert(plan.end(), spans.begin(), spans.end());
+  } catch (...) { return fail(EU_ERR_MEMORY, "facet alpha: host memory"); }
+  // an earlier edit may still read the buffer, on a caller's stream or on the library's own
+  HIPCHK(cur().alpha.readers.host_wait());
+  HIPCHK(hipStreamSynchronize(cur().stream));
+  HIPCHK(cur().alpha.plan.reserve(plan.size() + 2));
+  HIPCHK(hipMemcpy(cur().alpha.plan.p, plan.data(), plan.size() * sizeof(int), hipMemcpyHostToDevice));
+  p->keep = cur().alpha.plan.p;
+  p->row_start = p->keep + size_t(h) * 2;
+  p->spans = p->row_start + size_t(h) + 1;
+  return EU_OK;
+}
+
+// ---- the load pipeline: pixels -> braced, prefiltered container ------------------------------------------
+
+// where a loader's pixels come from
+enum feed_kind {
+  FEED_HOST_FLOATS,      // host floats at the facet's channel count, no edit: copied straight to the destination
+  FEED_EDITED_FLOATS,    // floats on the host (staged on the device first) or on the device, through the edit
+  FEED_SAMPLES           // 8- or 16-bit samples on the host (uploaded behind their tables) or on the device, decoded there
+};
+struct load_feed {
+  feed_kind kind;
+  const char *who;             // the entry point, as messages name it
+  const void *data;            // the floats or the samples
+  bool on_device;              // data lies in device memory
+  int src_ch;                  // channels of data: the facet's, or one less
+  const eu_facet_edit *edit;   // masks and crop (FEED_HOST_FLOATS: none)
+  bool alter;                  // the edit's kernel runs: FEED_EDITED_FLOATS whenever the edit changes something (a gained
+                               // channel too), FEED_SAMPLES for masks or a crop (the decoder writes a gained channel itself)
+  const eu_samples *smp;       // FEED_SAMPLES: bits, byte order, tables
+};
+
+// One load pipeline with three feeds. Written once: the source and its container (source_bcs, new_source), the plane
+// the pixels arrive in - the facet's window as the core of the container, or the stack of a cubemap's six faces in
+// scratch -, the clearing of a flat container, the finish (cube build, or the prefilter full_sphere() picks), the one
+// synchronisation, and the error precedence: the message the plan upload or a kernel launch set, then the HIP error,
+// then "device set-up stage failed". The feed is all that differs. Host floats: one H2D copy into the plane (1-D
+// into the faces, 2-D into the core), no staging, no kernel. Floats through the edit: host pixels are staged on the
+// device at their own channel count; upload_alpha_plan + eu_launch_facet_alpha write the plane, or - an edit that
+// changes nothing, pixels on the device - a 2-D D2D copy. Integer samples: both tables and, behind them, the samples
+// of a host image go into one device block; eu_launch_decode writes the plane, or - with masks or a crop - a dense
+// buffer that eu_launch_facet_alpha then reads. Scratch is freed by scope, after the synchronisation.
+// The entry points make their own argument checks, in their own order, and find the device (ensure_init).
+int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
+                const load_feed &feed, eu_source **out)
+{
+  int rc, bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  const std::string who(feed.who);
+  const int nch = s->nch, src_ch = feed.src_ch, iir_stream = eu_read_switches().iir_stream;
+  const bool cube = eu_cube_source(fct->projection);
+  eu::metrics m {};
+  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  const eu_container &gm = s->geom;
+  const int w = cube ? int(m.face_px) : int(gm.core[0]), h = cube ? int(6 * m.face_px) : int(gm.core[1]);
+  const size_t npix = size_t(w) * size_t(h);
+  eu_dev_tmp<float> staged, faces;   // floats in front of the edit, at src_ch channels; the faces of a cubemap
+  eu_dev_tmp<char> block;            // samples: both tables and, behind them, the samples of a host image, as they are
+  std::vector<float> tabs;
+  const void *src = feed.data;
+  hipError_t e = hipSuccess;
+  int prc = 0;
+  // what the feed brings to the device first
+  if (feed.kind == FEED_SAMPLES) {
+    const size_t ntab = size_t(1) << feed.smp->bits, nbytes = npix * size_t(src_ch) * size_t(feed.smp->bits / 8);
+    try {
+      tabs.assign(feed.smp->colour_table, feed.smp->colour_table + ntab);
+      const float *at = feed.smp->alpha_table ? feed.smp->alpha_table : feed.smp->colour_table;
+      tabs.insert(tabs.end(), at, at + ntab);
+    } catch (...) { destroy_source(s); return fail(EU_ERR_MEMORY, who + ": host memory"); }
+    const size_t tab_bytes = tabs.size() * sizeof(float);
+    e = block.alloc(tab_bytes + (feed.on_device ? 0 : nbytes));
+    if (e == hipSuccess) e = hipMemcpyAsync(block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, cur().stream);
+    if (e == hipSuccess && !feed.on_device) {
+      e = hipMemcpyAsync(block.p + tab_bytes, feed.data, nbytes, hipMemcpyHostToDevice, cur().stream);
+      src = block.p + tab_bytes;
+    }
+    if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
+  } else if (feed.kind == FEED_EDITED_FLOATS && !feed.on_device) {
+    e = staged.alloc(npix * src_ch);
+    if (e == hipSuccess) e = hipMemcpyAsync(staged.p, feed.data, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, cur().stream);
+    src = staged.p;
+  }
+  // the plane: w x h pixels of nch floats at dst, rows dst_pitch pixels apart
+  if (e == hipSuccess && cube) e = faces.alloc(npix * nch);
+  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), cur().stream);
+  float *dst = cube ? faces.p : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
+  const size_t dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
+  const size_t row_bytes = size_t(w) * nch * sizeof(float), pitch_bytes = dst_pitch * nch * sizeof(float);
+  if (e == hipSuccess) {
+    eu_alpha_params p {};            // the edit, where it runs: src (src_ch channels, dense) -> the plane
+    p.src = static_cast<const float *>(src); p.dst = dst;
+    p.src_pitch = size_t(w); p.dst_pitch = dst_pitch;
+    p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
+    if (feed.kind == FEED_HOST_FLOATS) {
+      e = cube ? hipMemcpyAsync(dst, src, npix * nch * sizeof(float), hipMemcpyHostToDevice, cur().stream)
+               : hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyHostToDevice, cur().stream);
+    } else if (feed.kind == FEED_EDITED_FLOATS) {
+      if (!feed.alter)
+        e = hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyDeviceToDevice, cur().stream);
+    } else {
+      // samples -> floats: straight into the plane, or into the dense buffer the edit reads as it reads
+      // pixels_on_device input (the channel a facet gains is then the edit's work)
+      eu_decode_params d {};
+      d.src = src; d.tables = reinterpret_cast<const float *>(block.p);
+      d.dst = feed.alter ? staged.p : dst;
+      d.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
+      d.w = w; d.h = h; d.bits = feed.smp->bits; d.big_endian = feed.smp->big_endian != 0;
+      d.nch = feed.alter ? src_ch : nch; d.src_ch = src_ch;
+      if (eu_launch_decode(&d, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged.p;
+    }
+    if (feed.alter && !prc) {
+      prc = upload_alpha_plan(feed.edit, w, h, &p);
+      if (!prc && eu_launch_facet_alpha(&p, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+    }
+  }
+  // the finish: the IR image of a cubemap from its faces, or prefilter + brace of the container (a core narrower
+  // than the spline's frame on an axis is braced slice by slice in zimt's order, eu_setup.hip: brace_seq_kernel)
+  if (e == hipSuccess && !prc)
+    rc = cube ? eu_launch_cubemap_build(faces.p, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
+                                        m.refc_md, m.model_to_px, prefilter_degree, iir_stream, cur().stream)
+              : eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, full_sphere(fct), iir_stream, cur().stream);
+  const hipError_t e2 = hipStreamSynchronize(cur().stream);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess || rc || prc) {
+    destroy_source(s);
+    if (prc) return prc;           // the plan's upload or a kernel launch: the message is set
+    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
+    return fail(rc, "device set-up stage failed");
+  }
+  *out = s;
+  return EU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eu_hip_facet_alpha(float *pixels, int width, int height, int nchannels, const eu_mask_polygon *polygons,
+                       int npolygons, int crop_kind, int crop_x0, int crop_x1, int crop_y0, int crop_y1,
+                       float *alpha_out)
+{
+  if (width <= 0 || height <= 0 || (nchannels != 2 && nchannels != 4) || (!pixels && !alpha_out))
+    return fail(EU_ERR_ARGUMENT, "facet_alpha: width x height x {2, 4} channels");
+  if (npolygons < 0 || (npolygons > 0 && !polygons) || crop_kind < 0 || crop_kind > 2)
+    return fail(EU_ERR_ARGUMENT, "facet_alpha: polygons / crop kind");
+  std::vector<eu::mask_polygon> ps;
+  for (int i = 0; i < npolygons; i++) {
+    if (polygons[i].n < 0 || (polygons[i].n > 0 && (!polygons[i].x || !polygons[i].y)))
+      return fail(EU_ERR_ARGUMENT, "facet_alpha: polygon without vertices");
+    ps.push_back({ polygons[i].n, polygons[i].x, polygons[i].y });
+  }
+  std::vector<float> alpha;
+  try { alpha.resize(size_t(width) * height); } catch (...) { return fail(EU_ERR_MEMORY, "facet_alpha: host memory"); }
+  eu::facet_alpha(alpha.data(), width, height, ps.data(), int(ps.size()), crop_kind, crop_x0, crop_x1, crop_y0, crop_y1);
+  if (pixels)
+    eu::parallel_rows(height, [&](int y0, int y1) {
+      for (size_t i = size_t(y0) * width; i < size_t(y1) * width; i++)
+        for (int c = 0; c < nchannels; c++) pixels[i * nchannels + c] = pixels[i * nchannels + c] * alpha[i];
+    });
+  if (alpha_out) memcpy(alpha_out, alpha.data(), alpha.size() * sizeof(float));
+  return EU_OK;
+}
+
+int eu_hip_source_adopt(const eu_facet *fct, const float *container, int spline_degree,
+                        int bc0, int bc1, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!container || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  hipError_t e = hipMemcpy(s->dev, container, s->nfloats * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { destroy_source(s); return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }
+  *out = s;
+  return EU_OK;
+}
+
+int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degree,
+                       int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_facet_alpha_rows(int width, int height, const eu_mask_polygon *polygons, int npolygons, int crop_kind,
+                            int crop_x0, int crop_x1, int crop_y0, int crop_y1, int32_t *keep, int32_t *row_start,
+                            int32_t *spans, int max_spans)
+{
+  if (width <= 0 || height <= 0) return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: empty image");
+  if (npolygons < 0 || (npolygons > 0 && !polygons) || crop_kind < 0 || crop_kind > 2)
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: polygons / crop kind");
+  std::vector<eu::mask_polygon> ps;
+  for (int i = 0; i < npolygons; i++) {
+    if (polygons[i].n < 0 || (polygons[i].n > 0 && (!polygons[i].x || !polygons[i].y)))
+      return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: polygon without vertices");
+    ps.push_back({ polygons[i].n, polygons[i].x, polygons[i].y });
+  }
+  std::vector<int> k, r, sp;
+  try {
+    eu::facet_alpha_rows(width, height, ps.data(), int(ps.size()), crop_kind, crop_x0, crop_x1, crop_y0, crop_y1, k, r, sp);
+  } catch (...) { return fail(EU_ERR_MEMORY, "facet_alpha_rows: host memory"); }
+  const size_t n = sp.size() / 2;
+  if (n > size_t(INT32_MAX)) return fail(EU_ERR_UNSUPPORTED, "facet_alpha_rows: too many spans");
+  if (keep) memcpy(keep, k.data(), k.size() * sizeof(int32_t));
+  if (row_start) memcpy(row_start, r.data(), r.size() * sizeof(int32_t));
+  if (spans) {
+    if (max_spans < 0 || n > size_t(max_spans)) return fail(EU_ERR_ARGUMENT, "facet_alpha_rows: span buffer too small");
+    if (n) memcpy(spans, sp.data(), sp.size() * sizeof(int32_t));
+  }
+  return int(n);
+}
+
+int eu_hip_facet_alpha_dev(void *pixels_dev, int width, int height, int nchannels, const eu_facet_edit *edit,
+                           float *alpha_out_dev, void *stream)
+{
+  if (width <= 0 || height <= 0 || (nchannels != 2 && nchannels != 4) || (!pixels_dev && !alpha_out_dev))
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_dev: width x height x {2, 4} channels");
+  bool asked;
+  int rc;
+  if ((rc = check_edit(edit, nchannels, "facet_alpha_dev", &asked))) return rc;
+  if (edit && edit->pixel_channels != nchannels)
+    return fail(EU_ERR_ARGUMENT, "facet_alpha_dev: an edit in place keeps the channel count");
+  if ((rc = ensure_init())) return rc;
+  eu_alpha_params p {};
+  if ((rc = upload_alpha_plan(edit, width, height, &p))) return rc;
+  p.src = p.dst = static_cast<float *>(pixels_dev);
+  p.alpha_out = alpha_out_dev;
+  p.src_pitch = p.dst_pitch = size_t(width);
+  p.w = width; p.h = height; p.nch = p.src_ch = nchannels;
+  hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
+  if (eu_launch_facet_alpha(&p, st)) return fail(EU_ERR_NO_DEVICE, "facet_alpha_dev: kernel launch failed");
+  return note_caller(cur().alpha.readers, stream, EU_OK);
+}
+
+int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
+                              int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  bool asked;
+  if ((rc = check_edit(edit, fct->nchannels, "source_load_edited", &asked))) return rc;
+  const bool on_device = edit && edit->pixels_on_device;
+  if (!asked && !on_device)
+    return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
+                              tile_size, out);
+  if ((rc = ensure_init())) return rc;
+  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
+                               int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!smp || !smp->data || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (smp->bits != 8 && smp->bits != 16) return fail(EU_ERR_ARGUMENT, "source_load_samples: bits must be 8 or 16");
+  if (!smp->colour_table) return fail(EU_ERR_ARGUMENT, "source_load_samples: null colour table");
+  // the edit as given, with the samples' channel count in place of its own
+  eu_facet_edit ed {};
+  if (edit) ed = *edit;
+  ed.pixel_channels = smp->pixel_channels;
+  ed.pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(&ed, fct->nchannels, "source_load_samples", &asked))) return rc;
+  if (smp->on_device && smp->bits == 16 && reinterpret_cast<uintptr_t>(smp->data) % 2)
+    return fail(EU_ERR_ARGUMENT, "source_load_samples: 16-bit samples on the device lie at an even address");
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  if ((rc = ensure_init())) return rc;
+  const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
+  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_source_alloc(const eu_facet *fct, int spline_degree, int support_min, int tile_size,
+                        eu_source **out)
+{
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!out) return fail(EU_ERR_ARGUMENT, "null argument");
+  int bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  return new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, out);
+}
+
+int eu_hip_source_update_facet(eu_source *src, const eu_facet *fct)
+{
+  int rc;
+  if (!src) return fail(EU_ERR_HANDLE, "null source");
+  if ((rc = check_facet(fct))) return rc;
+  const eu_facet &o = src->fct;
+  // what the resident container was built from stays as it is
+  if (fct->projection != o.projection || fct->nchannels != o.nchannels || fct->width != o.width ||
+      fct->height != o.height || fct->window_width != o.window_width || fct->window_height != o.window_height)
+    return fail(EU_ERR_ARGUMENT, "the facet's image (projection, size, channels) differs from the resident one");
+  if (eu_cube_source(o.projection) && fct->hfov != o.hfov)
+    return fail(EU_ERR_ARGUMENT, "a cubemap's field of view is part of its resident image");
+  const eu_src_dev keep = src->sd;
+  src->fct = *fct;
+  fill_src_dev(src);
+  if (eu_cube_source(o.projection)) {
+    src->sd.refc_md = keep.refc_md; src->sd.model_to_px = keep.model_to_px; src->sd.section_px = keep.section_px;
+  }
+  return EU_OK;
+}
+
+int eu_hip_source_device_ptr(const eu_source *src, void **dev_ptr, size_t *nfloats)
+{
+  if (!src) return fail(EU_ERR_HANDLE, "null source");
+  if (dev_ptr) *dev_ptr = src->dev;
+  if (nfloats) *nfloats = src->nfloats;
+  return EU_OK;
+}
+
+int eu_hip_source_download(const eu_source *src, float *container, size_t nfloats)
+{
+  if (!src || !container) return fail(EU_ERR_HANDLE, "null argument");
+  if (nfloats != src->nfloats) return fail(EU_ERR_ARGUMENT, "container size mismatch");
+  HIPCHK(hipMemcpy(container, src->dev, nfloats * sizeof(float), hipMemcpyDeviceToHost));
+  return EU_OK;
+}
+
+int eu_hip_source_info(const eu_source *src, eu_container *geom, int *nch)
+{
+  if (!src) return fail(EU_ERR_HANDLE, "null source");
+  if (geom) *geom = src->geom;
+  if (nch) *nch = src->nch;
+  return EU_OK;
+}
+
+int eu_hip_source_release(eu_source *src)
+{
+  if (!src) return EU_OK;
+  for (int k = 0; k < EU_MAX_SLOTS; k++) destroy_source(src->replica[k]);
+  destroy_source(src);
+  return EU_OK;
+}
+
+// DIAGNOSTIC (not declared in eu_hip.h): a source handle without a container, made without a device, so that
+// the argument checks of eu_hip_render_rays can be exercised where there is none (tests/test_rays_host.py).
+// Only eu_hip_render_rays[_timed] - which refuse it once they have a device - and eu_hip_source_release take it.
+int eu_hip_diag_host_source(const eu_facet *fct, int spline_degree, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!out) return fail(EU_ERR_ARGUMENT, "null argument");
+  eu_source *s = bare_source(fct, spline_degree);
+  if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
+  *out = s;
+  return EU_OK;
+}
+
+// DIAGNOSTIC (not in eu_hip.h): the ray -> source coordinate stage of the kernels on
+// caller-supplied rays (n x 3 floats, host): variant 0 eu_source_coordinate, 1 eu_coord2,
+// 2 eu_coord2_ok (eu_diag.hip). out = n x 3 floats: x, y, cube face | 0; a miss is 0, 0, -1
+int eu_hip_diag_source_coordinates(const eu_source *src, const float *rays, long n, int variant, float *out)
+{
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  if (!src || !rays || !out || n < 0) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (n == 0) return EU_OK;
+  eu_dev_tmp<float> buf;
+  HIPCHK(buf.alloc((size_t)n * 6));
+  float *d = buf.p;
+  HIPCHK(hipMemcpy(d, rays, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  const int lrc = eu_launch_diag_coords(&src->sd, d, n, variant, d + (size_t)n * 3, cur().stream);
+  if (lrc > 0) return fail(EU_ERR_UNSUPPORTED, "the packed forms cover lat/lon, cubemap and biatan6 sources");
+  if (lrc < 0) return fail(EU_ERR_NO_DEVICE, "diag launch failed");
+  HIPCHK(hipStreamSynchronize(cur().stream));
+  HIPCHK(hipMemcpy(out, d + (size_t)n * 3, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  return EU_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// The boundary between the C ABI's host glue (eu_api.hip) and the kernel files, declared once: the
+// The boundary between the C ABI's host glue (eu_api.hip, eu_api_*.hip) and the kernel files, declared once: the
 // launchers, the argument structure of the multi-facet kernels and a typed device buffer.
 #ifndef EU_LAUNCH_H
 #define EU_LAUNCH_H

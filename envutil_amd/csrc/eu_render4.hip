@@ -571,7 +571,7 @@ struct plan_cache {
   int l1_ecols = 1;
   long long follower_tiles = 0;
 } g4s[EU_MAX_SLOTS];
-// one cache per device slot (eu_api.hip: eu_hip_init_devices)
+// one cache per device slot (eu_api_devices.hip: eu_hip_init_devices)
 #define g4 (g4s[eu_current_slot()])
 
 bool ensure_atab()

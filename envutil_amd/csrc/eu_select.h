@@ -1,5 +1,5 @@
 // How a single-facet job finds its kernel, and the EU_HIP_* switches that can change the answer.
-// Plain C++ (no HIP): eu_api.hip and the launchers include it, and so does a host test program
+// Plain C++ (no HIP): the host glue (eu_api_*.hip) and the launchers include it, and so does a host test program
 // (tests/csrc/select_demo.cc).
 //
 //   general          eu_render.hip    one pixel per lane, every job
@@ -208,7 +208,7 @@ inline int eu_views_per_chunk(int width, int height, int max_kb, int nfct = 1)
 
 // ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------
 // The frame is cut into segments of EU_SEG_ROWS rows; flags[k] != 0 where segment k renders faster with
-// 32x16 tiles than with 128x4 row strips (eu_api.hip: refresh_seg_flags).
+// 32x16 tiles than with 128x4 row strips (eu_api_render.hip: refresh_seg_flags).
 #define EU_SEG_ROWS 512
 
 struct eu_run { int row_begin, row_end, layout; };     // local rows; layout 1 row strips, 2 tiles

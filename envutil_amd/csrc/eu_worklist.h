@@ -1,5 +1,5 @@
 // The work list between the staged render kernels and the direct-gather kernel behind them
-// (eu_render4.hip, eu_render5.h; the buffer is eu_render_params::wl, allocated in eu_api.hip): its layout,
+// (eu_render4.hip, eu_render5.h; the buffer is eu_render_params::wl, allocated in eu_api_render.hip): its layout,
 // the list a tile goes to, and how many ints a launch needs - defined once, for the kernels that write
 // and read it, for the host that sizes it and for a host test program (tests/csrc/worklist_demo.cc).
 // Plain C++ with the functions the kernels call marked for both sides under hipcc.

@@ -151,7 +151,7 @@ typedef struct eu_target {
   const eu_facet *single;
 } eu_target;
 
-/* How the library would lay the job's rows out (eu_api.hip: launch-level choice between
+/* How the library would lay the job's rows out (eu_api_render.hip: launch-level choice between
  * row strips and 32x16 tiles): flags[k] = 1 for segment k of *seg_rows frame rows where
  * source rows run across target rows - those rows take about 1.55x the time of the others,
  * about 2x when they are part of a strip they break into several launches. For hosts that
