@@ -138,6 +138,7 @@ def lib():
     L.eu_hip_source_load.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_source_load_edited.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_source_load_samples.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_source_load_rgbe.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_facet_alpha_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.eu_hip_facet_alpha_rows.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32]
     L.eu_hip_source_adopt.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -150,6 +151,8 @@ def lib():
     L.eu_hip_render.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_samples.argtypes = [vp, vp, i32, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_encode_samples.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, vp, vp, C.c_size_t, i32, vp]
+    L.eu_hip_render_rgbe.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
+    L.eu_hip_encode_rgbe.argtypes = [vp, C.c_size_t, i32, i32, i32, vp, C.c_size_t, i32, vp]
     L.eu_hip_init_devices.argtypes = [vp, i32]
     L.eu_hip_render_devices.argtypes = [vp, vp, i32, vp, C.c_size_t, i32]
     L.eu_hip_device_strips.argtypes = [vp, vp, i32, vp, vp]
@@ -253,6 +256,11 @@ class Samples(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bits", C.c_int32), ("big_endian", C.c_int32),
                 ("pixel_channels", C.c_int32), ("on_device", C.c_int32),
                 ("colour_table", C.c_void_p), ("alpha_table", C.c_void_p)]
+
+
+class Rgbe(C.Structure):
+    """struct eu_rgbe"""
+    _fields_ = [("data", C.c_void_p), ("on_device", C.c_int32), ("colour_table", C.c_void_p)]
 
 
 def _is_torch(x):
@@ -460,6 +468,44 @@ class Source:
         edited = len(masks) or crop is not None
         _check(lib().eu_hip_source_load_samples(C.byref(cf), C.byref(sm), C.byref(e) if edited else None, spline_degree,
                                                 prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct)
+
+    @classmethod
+    def load_rgbe(cls, fct, quads, colour_table=None, spline_degree=1, prefilter_degree=None, support_min=8,
+                  tile_size=64, masks=(), crop=None, crop_kind=0):
+        """Radiance RGBE pixels -> the same source as load() of their decoded floats, decoded on the device
+        (eu_hip_source_load_rgbe): the quads go up as they are, no float copy is made on the host. `quads`: a uint8
+        numpy array or a contiguous torch uint8 tensor on the library's device, (h, w, 4): R, G, B, E. fct.nchannels is
+        3, or 4: the facet gains alpha = 1.0 here. colour_table: float32, 65536 entries indexed (E << 8) | mantissa -
+        the float a channel becomes; None: mantissa * 2^(E - 136), E == 0 -> 0. masks, crop, crop_kind as load()."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
+        on_device = _is_torch(quads)
+        if on_device:
+            import torch
+            if quads.dtype != torch.uint8 or not quads.is_cuda or not quads.is_contiguous():
+                raise EuError("a torch tensor handed over as quads is uint8, contiguous and on the device")
+            torch.cuda.current_stream(quads.device).synchronize()
+            data = quads.data_ptr()
+        else:
+            quads = np.asarray(quads)
+            if quads.dtype != np.uint8:
+                raise EuError("quads are uint8")
+            quads = np.ascontiguousarray(quads)
+            data = quads.ctypes.data
+        if quads.ndim < 1 or quads.shape[-1] != 4:
+            raise EuError("quads have shape (..., 4): R, G, B, E")
+        if colour_table is not None:
+            colour_table = np.ascontiguousarray(colour_table, np.float32)
+            if colour_table.shape != (65536,):
+                raise EuError("a table for RGBE pixels has 65536 entries")
+        px = Rgbe(data, int(on_device), colour_table.ctypes.data if colour_table is not None else None)
+        e, hold = _facet_edit(masks, crop, crop_kind, 3, on_device)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        edited = len(masks) or crop is not None
+        _check(lib().eu_hip_source_load_rgbe(C.byref(cf), C.byref(px), C.byref(e) if edited else None, spline_degree,
+                                             prefilter_degree, support_min, tile_size, C.byref(h)))
         return cls(h, fct)
 
     @classmethod
@@ -808,6 +854,55 @@ def render_samples(args, sources, nchannels=None, row_begin=0, row_end=None, col
     arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
     _check(lib().eu_hip_render_samples(C.byref(t), arr, len(sources), C.byref(e), C.c_void_p(optr), ostride, int(o_dev),
                                        C.c_void_p(stream) if stream else None))
+    return out
+
+
+def encode_rgbe(frame, out=None, stream=None):
+    """eu_hip_encode_rgbe: float pixels to Radiance RGBE quads on the device. `frame`: float32, shape (..., 3), a numpy
+    array or a torch tensor on the library's device (_grid's layouts) - the result of render(), render_rays() or
+    render_views(). Returns uint8 quads of shape (..., 4) - R, G, B, E -: a new numpy array for a numpy frame, a new
+    torch tensor on the device for a torch frame, or `out` (numpy or torch, rows may be padded, a 4-byte boundary).
+    With frame and out on the device the call is asynchronous on `stream` (a hipStream_t address; None: the
+    library's stream) until sync()."""
+    if not _is_torch(frame) and not (isinstance(frame, np.ndarray) and frame.dtype == np.float32):
+        frame = np.ascontiguousarray(frame, np.float32)
+    if frame.ndim < 1 or frame.shape[-1] != 3:
+        raise EuError("encode_rgbe: a frame has shape (..., 3)")
+    fptr, fstride, f_dev, lead, width, height = _grid(frame, "frame")
+    shape = tuple(frame.shape[:-1]) + (4,)
+    if out is None:
+        if f_dev:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=frame.device)
+        else:
+            out = np.zeros(shape, np.uint8)
+    if tuple(out.shape) != shape:
+        raise EuError(f"encode_rgbe: out has shape {tuple(out.shape)}, expected {shape}")
+    flat = out if out.ndim == 3 and tuple(out.shape[:2]) == (height, width) else out.reshape(height, width, 4)
+    optr, ostride, o_dev = _sample_rows("encode_rgbe", flat, (height, width, 4), 8)
+    _check(lib().eu_hip_encode_rgbe(C.c_void_p(fptr), fstride, int(f_dev), width, height, C.c_void_p(optr), ostride,
+                                    int(o_dev), C.c_void_p(stream) if stream else None))
+    return out
+
+
+def render_rgbe(args, sources, nchannels=None, row_begin=0, row_end=None, out=None, band=None, stream=None):
+    """eu_hip_render_rgbe: render() of a 3-channel target with the encode behind it on the device - (rows, width, 4)
+    uint8 quads, byte for byte encode_rgbe(render(...)), without the float frame leaving the device. Returns a new
+    numpy array, or `out` (numpy, or a torch uint8 tensor on the library's device; rows may be padded); with `out` on
+    the device the call is asynchronous on `stream` until sync(). Float frames only: no stage output, not a tethered
+    job."""
+    if not isinstance(sources, (list, tuple)):
+        sources = [sources]
+    if args.tethered:
+        raise EuError("render_rgbe: a tethered job has its own format (render)")
+    t = args.target(nchannels or sources[0].fct.nchannels, row_begin, row_end, 0, band)    # the library asks for 3
+    rows, w = t.row_end - t.row_begin, args.out_width
+    if out is None:
+        out = np.zeros((rows, w, 4), np.uint8)
+    optr, ostride, o_dev = _sample_rows("render_rgbe", out, (rows, w, 4), 8)
+    arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
+    _check(lib().eu_hip_render_rgbe(C.byref(t), arr, len(sources), C.c_void_p(optr), ostride, int(o_dev),
+                                    C.c_void_p(stream) if stream else None))
     return out
 
 

@@ -4,6 +4,7 @@
 #include "eu_context.h"
 #include "eu_setup_math.h"
 #include "eu_encode.h"
+#include "eu_rgbe_dev.h"
 
 using namespace eu_host;
 
@@ -437,9 +438,10 @@ namespace eu_host __attribute__((visibility("hidden"))) {
 
 // one job, everything on the device: float pixels straight into out_dev, or float pixels into the library's
 // frame buffer followed by a post-pass that writes out_dev - tethered, the to_screen_t pass and its packed words;
-// with `enc` (its tables are in enc.steps: upload_steps), the encode to integer samples
+// with `enc` (its tables are in enc.steps: upload_steps), the encode to integer samples; with `rgbe`, the encode to
+// Radiance quads (no tables; render_frame has ordered `st`)
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
-                     const eu_switches &sw, hipStream_t st, const eu_encode *enc)
+                     const eu_switches &sw, hipStream_t st, const eu_encode *enc, bool rgbe)
 {
   int rc;
   const bool multi = nsrc > 1;
@@ -448,9 +450,9 @@ int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, flo
   float *fout = out_dev;
   size_t fstride = stride_bytes;
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
-  if (screen || enc) {
+  if (screen || enc || rgbe) {
     if (screen && !cur().lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
-    // a post-pass queued on another stream may still read the frame buffer (upload_steps has ordered `st` where enc is set)
+    // a post-pass queued on another stream may still read the frame buffer (render_frame has ordered `st` where enc or rgbe is set)
     if (screen && (rc = order_encoders(st))) return rc;
     tf.out_format = EU_OUT_FLOAT;
     fstride = (size_t)frame_w(trg) * trg->nchannels * sizeof(float);
@@ -481,6 +483,13 @@ int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, flo
     ep.w = frame_w(trg); ep.h = (int)rows; ep.nch = trg->nchannels;
     ep.bits = enc->bits; ep.big_endian = enc->big_endian;
     if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+  }
+  if (rgbe && rows) {
+    eu_rgbe_encode_params ep {};
+    ep.src = fout; ep.src_stride_bytes = fstride;
+    ep.dst = reinterpret_cast<uint32_t *>(out_dev); ep.dst_stride_bytes = stride_bytes;
+    ep.w = frame_w(trg); ep.h = (int)rows;
+    if (eu_launch_rgbe_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
   }
   return EU_OK;
 }
@@ -560,25 +569,27 @@ static int check_render_sources(const eu_target *trg, eu_source *const *srcs, in
   return EU_OK;
 }
 
-// The job of eu_hip_render and of eu_hip_render_samples behind their argument checks: `out` receives rows of
-// row_bytes bytes - floats or packed words, or, with `enc`, integer samples.
+// The job of eu_hip_render, eu_hip_render_samples and eu_hip_render_rgbe behind their argument checks: `out` receives
+// rows of row_bytes bytes - floats or packed words, or, with `enc`, integer samples, or, with `rgbe`, Radiance quads.
 static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out, size_t row_bytes,
-                        size_t out_row_stride_bytes, int out_on_device, void *stream, const eu_encode *enc)
+                        size_t out_row_stride_bytes, int out_on_device, void *stream, const eu_encode *enc, bool rgbe = false)
 {
   int rc;
   hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
   const eu_switches sw = eu_read_switches();
   if (enc && (rc = upload_steps(enc, st))) return rc;
+  // the frame buffer is about to be rewritten on `st`: behind the calls that used it before, as upload_steps orders it
+  if (rgbe && (rc = order_encoders(st))) return rc;
   if (out_on_device)
-    return note_caller(cur().tables, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc));
+    return note_caller(cur().tables, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc, rgbe));
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (!rows) return EU_OK;
   HIPCHK(cur().out.stage.reserve((rows * row_bytes + sizeof(float) - 1) / sizeof(float)));
   // The frame goes to the host in up to four row chunks: every chunk is a launch of its own
   // on `st`, and its copy (second stream, behind the chunk's event) runs while the later
   // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
-  // whole cost, the kernels hide under the first copy. Samples: the encode runs behind each chunk's render,
-  // and the link carries a quarter or half of the bytes.
+  // whole cost, the kernels hide under the first copy. Samples and quads: the encode runs behind each chunk's render,
+  // and the link carries a quarter, half or a third of the bytes.
   const size_t nchunk = rows >= 1024 ? 4 : 1;
   if (!cur().out.copy) HIPCHK(hipStreamCreateWithFlags(&cur().out.copy, hipStreamNonBlocking));
   for (size_t c = 0; c < 4; c++)
@@ -592,7 +603,7 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
     tc.row_begin = trg->row_begin + (int)a;
     tc.row_end = trg->row_begin + (int)b;
     char *dst = (char *)cur().out.stage.p + a * row_bytes;
-    if ((rc = render_on_device(&tc, srcs, nsrc, (float *)dst, row_bytes, sw, st, enc))) return rc;
+    if ((rc = render_on_device(&tc, srcs, nsrc, (float *)dst, row_bytes, sw, st, enc, rgbe))) return rc;
     HIPCHK(hipEventRecord(cur().out.chunk_done[c], st));
     HIPCHK(hipStreamWaitEvent(cur().out.copy, cur().out.chunk_done[c], 0));
     HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, row_bytes,
@@ -683,6 +694,87 @@ int eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int
     }
     if (!out_on_device) { ep.dst = cur().enc.out.p; ep.dst_stride_bytes = out_row; }
     if (eu_launch_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    if (!out_on_device)
+      HIPCHK(hipMemcpy2DAsync(fout, out_row_stride_bytes, cur().enc.out.p, out_row, out_row, (size_t)h, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return EU_OK;
+}
+
+// ---- Radiance RGBE quads on the way out (eu_rgbe.hip) -------------------------------------------------------------
+// what both entry points ask of `out`: rows of `width` quads on 4-byte boundaries
+static int check_rgbe_out(const char *who, int width, const void *out, size_t out_row_stride_bytes)
+{
+  const std::string head = std::string(who) + ": ";
+  if (!out) return fail(EU_ERR_ARGUMENT, head + "null argument");
+  if (width < 0 || (size_t)width > (size_t(1) << 28)) return fail(EU_ERR_ARGUMENT, head + "rows of 0 .. 2^28 pixels");
+  if (out_row_stride_bytes < (size_t)width * 4) return fail(EU_ERR_ARGUMENT, head + "row stride smaller than a row");
+  if (reinterpret_cast<uintptr_t>(out) % 4 || out_row_stride_bytes % 4)
+    return fail(EU_ERR_ARGUMENT, head + "quads lie on 4-byte boundaries: out and its row stride are multiples of 4");
+  return EU_OK;
+}
+
+int eu_hip_render_rgbe(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out, size_t out_row_stride_bytes,
+                       int out_on_device, void *stream)
+{
+  int rc;
+  if (!trg) return fail(EU_ERR_ARGUMENT, "render_rgbe: null target");
+  if (!srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "render_rgbe: no source / no output");
+  if ((rc = check_target(trg))) return rc;
+  if (trg->stage) return fail(EU_ERR_ARGUMENT, "render_rgbe: stage outputs are float only");
+  if (trg->out_format != EU_OUT_FLOAT) return fail(EU_ERR_ARGUMENT, "render_rgbe: EU_OUT_SRGBA8 is a format of its own, not a frame to encode");
+  if (trg->nchannels != 3) return fail(EU_ERR_ARGUMENT, "render_rgbe: a Radiance picture holds 3 channels");
+  if ((rc = check_rgbe_out("render_rgbe", frame_w(trg), out, out_row_stride_bytes))) return rc;
+  if ((rc = check_render_sources(trg, srcs, nsrc))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (trg->row_end == trg->row_begin) return EU_OK;
+  return render_frame(trg, srcs, nsrc, out, (size_t)frame_w(trg) * 4, out_row_stride_bytes, out_on_device, stream, nullptr, true);
+}
+
+int eu_hip_encode_rgbe(const float *frame, size_t frame_row_stride_bytes, int frame_on_device, int width, int height,
+                       void *out, size_t out_row_stride_bytes, int out_on_device, void *stream)
+{
+  int rc;
+  if (!frame) return fail(EU_ERR_ARGUMENT, "encode_rgbe: null argument");
+  if (height < 0) return fail(EU_ERR_ARGUMENT, "encode_rgbe: negative height");
+  if ((rc = check_rgbe_out("encode_rgbe", width, out, out_row_stride_bytes))) return rc;
+  const size_t in_row = (size_t)width * 3 * sizeof(float), out_row = (size_t)width * 4;
+  if (frame_row_stride_bytes < in_row) return fail(EU_ERR_ARGUMENT, "encode_rgbe: frame row stride smaller than a row");
+  if (frame_row_stride_bytes % sizeof(float) || reinterpret_cast<uintptr_t>(frame) % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "encode_rgbe: the frame and its row stride are multiples of 4 bytes");
+  if (!width || !height) return EU_OK;
+  if ((rc = ensure_init())) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
+  eu_rgbe_encode_params ep {};
+  ep.w = width;
+  if (frame_on_device && out_on_device) {
+    // nothing of the library's is read: no table, no staging - so the call leaves no event behind either
+    ep.src = frame; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.dst = static_cast<uint32_t *>(out); ep.dst_stride_bytes = out_row_stride_bytes;
+    ep.h = height;
+    if (eu_launch_rgbe_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    return EU_OK;
+  }
+  // A host buffer on either side: the chunks of eu_hip_encode_samples, through its staging buffers. `st` goes behind
+  // the calls that used them before; the call returns when `out` is complete.
+  if ((rc = order_encoders(st))) return rc;
+  const int ch = (int)std::min<size_t>((size_t)height, std::max<size_t>(1, EU_ENCODE_CHUNK_BYTES / (in_row + out_row)));
+  if (!frame_on_device) HIPCHK(cur().enc.frame.reserve((size_t)ch * width * 3));
+  if (!out_on_device) HIPCHK(cur().enc.out.reserve((size_t)ch * width));
+  drain drain_on_exit{ st, st };
+  for (int y0 = 0; y0 < height; y0 += ch) {
+    const int h = std::min(ch, height - y0);
+    const char *fin = (const char *)frame + (size_t)y0 * frame_row_stride_bytes;
+    char *fout = (char *)out + (size_t)y0 * out_row_stride_bytes;
+    ep.src = (const float *)fin; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.dst = (uint32_t *)fout; ep.dst_stride_bytes = out_row_stride_bytes;
+    ep.h = h;
+    if (!frame_on_device) {
+      ep.src = cur().enc.frame.p; ep.src_stride_bytes = in_row;
+      HIPCHK(hipMemcpy2DAsync(cur().enc.frame.p, in_row, fin, frame_row_stride_bytes, in_row, (size_t)h, hipMemcpyHostToDevice, st));
+    }
+    if (!out_on_device) { ep.dst = cur().enc.out.p; ep.dst_stride_bytes = out_row; }
+    if (eu_launch_rgbe_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
     if (!out_on_device)
       HIPCHK(hipMemcpy2DAsync(fout, out_row_stride_bytes, cur().enc.out.p, out_row, out_row, (size_t)h, hipMemcpyDeviceToHost, st));
   }

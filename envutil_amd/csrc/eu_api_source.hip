@@ -5,6 +5,7 @@
 #include "eu_imageprep.h"
 #include "eu_alpha.h"
 #include "eu_decode.h"
+#include "eu_rgbe_dev.h"
 
 using namespace eu_host;
 
@@ -243,7 +244,8 @@ int upload_alpha_plan(const eu_facet_edit *e, int w, int h, eu_alpha_params *p)
 enum feed_kind {
   FEED_HOST_FLOATS,      // host floats at the facet's channel count, no edit: copied straight to the destination
   FEED_EDITED_FLOATS,    // floats on the host (staged on the device first) or on the device, through the edit
-  FEED_SAMPLES           // 8- or 16-bit samples on the host (uploaded behind their tables) or on the device, decoded there
+  FEED_SAMPLES,          // 8- or 16-bit samples on the host (uploaded behind their tables) or on the device, decoded there
+  FEED_RGBE              // Radiance RGBE quads on the host (uploaded behind their table, if any) or on the device, decoded there
 };
 struct load_feed {
   feed_kind kind;
@@ -255,9 +257,10 @@ struct load_feed {
   bool alter;                  // the edit's kernel runs: FEED_EDITED_FLOATS whenever the edit changes something (a gained
                                // channel too), FEED_SAMPLES for masks or a crop (the decoder writes a gained channel itself)
   const eu_samples *smp;       // FEED_SAMPLES: bits, byte order, tables
+  const float *rgbe_table;     // FEED_RGBE: 65536 floats, or nullptr for the format's own decode
 };
 
-// One load pipeline with three feeds. Written once: the source and its container (source_bcs, new_source), the plane
+// One load pipeline with four feeds. Written once: the source and its container (source_bcs, new_source), the plane
 // the pixels arrive in - the facet's window as the core of the container, or the stack of a cubemap's six faces in
 // scratch -, the clearing of a flat container, the finish (cube build, or the prefilter full_sphere() picks), the one
 // synchronisation, and the error precedence: the message the plan upload or a kernel launch set, then the HIP error,
@@ -266,7 +269,9 @@ struct load_feed {
 // device at their own channel count; upload_alpha_plan + eu_launch_facet_alpha write the plane, or - an edit that
 // changes nothing, pixels on the device - a 2-D D2D copy. Integer samples: both tables and, behind them, the samples
 // of a host image go into one device block; eu_launch_decode writes the plane, or - with masks or a crop - a dense
-// buffer that eu_launch_facet_alpha then reads. Scratch is freed by scope, after the synchronisation.
+// buffer that eu_launch_facet_alpha then reads. RGBE quads: the integer feed with a dword per pixel - the optional table
+// and, behind it, the quads of a host image in one block; eu_launch_rgbe_decode writes what eu_launch_decode writes
+// for three samples per pixel. Scratch is freed by scope, after the synchronisation.
 // The entry points make their own argument checks, in their own order, and find the device (ensure_init).
 int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
                 const load_feed &feed, eu_source **out)
@@ -305,6 +310,19 @@ int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, in
       src = block.p + tab_bytes;
     }
     if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
+  } else if (feed.kind == FEED_RGBE) {
+    const size_t tab_bytes = feed.rgbe_table ? 65536 * sizeof(float) : 0, nbytes = npix * 4;
+    if (feed.rgbe_table) {
+      try { tabs.assign(feed.rgbe_table, feed.rgbe_table + 65536); }
+      catch (...) { destroy_source(s); return fail(EU_ERR_MEMORY, who + ": host memory"); }
+    }
+    if (tab_bytes || !feed.on_device) e = block.alloc(tab_bytes + (feed.on_device ? 0 : nbytes));
+    if (e == hipSuccess && tab_bytes) e = hipMemcpyAsync(block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, cur().stream);
+    if (e == hipSuccess && !feed.on_device) {
+      e = hipMemcpyAsync(block.p + tab_bytes, feed.data, nbytes, hipMemcpyHostToDevice, cur().stream);
+      src = block.p + tab_bytes;
+    }
+    if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
   } else if (feed.kind == FEED_EDITED_FLOATS && !feed.on_device) {
     e = staged.alloc(npix * src_ch);
     if (e == hipSuccess) e = hipMemcpyAsync(staged.p, feed.data, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, cur().stream);
@@ -327,6 +345,16 @@ int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, in
     } else if (feed.kind == FEED_EDITED_FLOATS) {
       if (!feed.alter)
         e = hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyDeviceToDevice, cur().stream);
+    } else if (feed.kind == FEED_RGBE) {
+      // quads -> floats, as the samples below: into the plane, or into the dense buffer the edit reads
+      eu_rgbe_decode_params d {};
+      d.src = static_cast<const uint32_t *>(src);
+      d.table = feed.rgbe_table ? reinterpret_cast<const float *>(block.p) : nullptr;
+      d.dst = feed.alter ? staged.p : dst;
+      d.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
+      d.w = w; d.h = h; d.nch = feed.alter ? src_ch : nch;
+      if (eu_launch_rgbe_decode(&d, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged.p;
     } else {
       // samples -> floats: straight into the plane, or into the dense buffer the edit reads as it reads
       // pixels_on_device input (the channel a facet gains is then the edit's work)
@@ -416,7 +444,7 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
-  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr };
+  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
@@ -486,7 +514,7 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
     return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
                               tile_size, out);
   if ((rc = ensure_init())) return rc;
-  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr };
+  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
@@ -512,7 +540,33 @@ int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
   const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
-  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp };
+  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp, nullptr };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
+                            int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!px || !px->data || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  if (fct->nchannels != 3 && fct->nchannels != 4)
+    return fail(EU_ERR_ARGUMENT, "source_load_rgbe: a facet of RGBE pixels has 3 channels, or 4 where it gains alpha");
+  // the edit as given, with the three channels of a quad in place of its own
+  eu_facet_edit ed {};
+  if (edit) ed = *edit;
+  ed.pixel_channels = 3;
+  ed.pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(&ed, fct->nchannels, "source_load_rgbe", &asked))) return rc;
+  if (px->on_device && reinterpret_cast<uintptr_t>(px->data) % 4)
+    return fail(EU_ERR_ARGUMENT, "source_load_rgbe: quads on the device lie on a 4-byte boundary");
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  if ((rc = ensure_init())) return rc;
+  const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
+  const load_feed feed { FEED_RGBE, "source_load_rgbe", px->data, px->on_device != 0, 3, &ed, edited, nullptr, px->colour_table };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 

@@ -204,7 +204,7 @@ inline void destroy_source(eu_source *s)
 
 // eu_api_render.hip. One job, everything on the device: what eu_hip_render_devices takes from the render family
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
-                     const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr);
+                     const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr, bool rgbe = false);
 
 // mean GPU time of `iters` calls of once() on the library's stream between two events, after one untimed call (which
 // builds whatever the first call builds: a plan's tables, derived copies)

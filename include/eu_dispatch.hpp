@@ -102,6 +102,12 @@ struct facet_spec : public facet_base
   int sample_bits = 0;            // 8 or 16
   bool samples_big_endian = false;
   const float *colour_table = nullptr, *alpha_table = nullptr;
+  // Or as the quads of a Radiance picture (pixels == nullptr, samples == nullptr): window_width x window_height x
+  // R G B E, scanlines expanded; a facet of 4 channels gains its alpha channel. payload() sends the quads up as they
+  // are and decodes them on the device (eu_hip_source_load_rgbe), masks and crop included. rgbe_table: 65536 floats
+  // indexed (E << 8) | mantissa for a file whose colour space is not the working one, nullptr for the plain decode.
+  const void *rgbe = nullptr;
+  const float *rgbe_table = nullptr;
 };
 
 struct arguments : public facet_base
@@ -129,6 +135,9 @@ struct arguments : public facet_base
   // the float route: payload() refuses p_output_samples for them, the caller asks before it chooses.
   void *p_output_samples = nullptr;
   eu_encode output_encode {};
+  // or as Radiance RGBE quads, encoded on the device (eu_hip_render_rgbe): width x height x 4 bytes, 3-channel
+  // targets. Refused where p_output_samples is: --ray_map jobs, several GPUs.
+  void *p_output_rgbe = nullptr;
   // PTO p-line crop (envutil_basic.h:684-687; envutil_payload.cc:440-474)
   bool store_cropped = false;
   int p_crop_x0 = 0, p_crop_x1 = 0, p_crop_y0 = 0, p_crop_y1 = 0;
@@ -266,7 +275,7 @@ struct hip_dispatch : public dispatch_base
   {
     if (projection != args.projection) return EU_ERR_ARGUMENT;
     if ((ninputs == 9) != !args.twine_spread.empty()) return EU_ERR_ARGUMENT;
-    if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples) return EU_ERR_ARGUMENT;
+    if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples && !args.p_output_rgbe) return EU_ERR_ARGUMENT;
     // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
     if (args.synopsis != "panorama" && args.synopsis != "hdr_merge") return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
@@ -302,6 +311,12 @@ struct hip_dispatch : public dispatch_base
           sm.colour_table = fct.colour_table; sm.alpha_table = fct.alpha_table;
           rc = eu_hip_source_load_samples(&e, &sm, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
                                           args.support_min, args.tile_size, &s);
+        } else if (fct.rgbe && !fct.pixels) {
+          // Radiance quads: uploaded as they are, decoded on the device, through the same edit
+          eu_rgbe px {};
+          px.data = fct.rgbe; px.colour_table = fct.rgbe_table;
+          rc = eu_hip_source_load_rgbe(&e, &px, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
+                                       args.support_min, args.tile_size, &s);
         } else if (edit) {
           rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
                                          args.support_min, args.tile_size, &s);
@@ -369,6 +384,11 @@ struct hip_dispatch : public dispatch_base
       if (slots > 1) return EU_ERR_ARGUMENT;
       return eu_hip_render_samples(&t, srcs.data(), int(srcs.size()), &args.output_encode, args.p_output_samples,
                                    size_t(w) * nchannels * size_t(args.output_encode.bits / 8), 0, nullptr);
+    }
+    if (args.p_output_rgbe && !args.p_output) {
+      // Radiance quads: encoded on the device behind the render, a third of the float frame's bytes
+      if (slots > 1) return EU_ERR_ARGUMENT;
+      return eu_hip_render_rgbe(&t, srcs.data(), int(srcs.size()), args.p_output_rgbe, size_t(w) * 4, 0, nullptr);
     }
     if (slots > 1)
       return eu_hip_render_devices(&t, srcs.data(), int(srcs.size()), args.p_output,

@@ -297,6 +297,22 @@ typedef struct eu_samples {
 int  eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit,
                                 int spline_degree, int prefilter_degree, int support_min, int tile_size,
                                 eu_source **out);
+/* The same container from Radiance RGBE pixels (include/eu_rgbe.h): the payload of a .hdr / .pic file with its
+ * scanlines expanded. The quads go to the device as they are - a third of the float image's bytes - or are read
+ * where they lie there, and become floats (eu_rgbe.hip) on the way into the container: bit for bit the container
+ * eu_hip_source_load_edited builds from the decoded floats with the same edit (edit == NULL: none;
+ * edit->pixel_channels and edit->pixels_on_device are ignored in favour of px). fct->nchannels is 3, or 4: the facet
+ * gains alpha = 1.0f here. The optional table serves a facet whose colour space is not the working one: a channel's
+ * float is a function of its (E, mantissa) pair alone, so 65536 entries say it all. Argument errors
+ * (EU_ERR_ARGUMENT) are reported before a device is looked for: null pointers, nchannels other than 3 or 4, masks
+ * or a crop on a facet of 3 channels, device data off a 4-byte boundary, degrees out of range. */
+typedef struct eu_rgbe {
+  const void *data;          /* width x height quads R G B E, rows dense; cubemaps: the six faces stacked */
+  int32_t on_device;         /* `data` is memory of the library's device */
+  const float *colour_table; /* host, 65536 floats indexed (E << 8) | mantissa: the float a channel becomes; NULL: mantissa * 2^(E-136), E == 0 -> 0 */
+} eu_rgbe;
+int  eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
+                             int prefilter_degree, int support_min, int tile_size, eu_source **out);
 /* Adopt an already prefiltered and braced container (host pointer, shape as
  * eu_hip_container_geometry reports; cubemaps: the IR image section_px x
  * 6*section_px). This is what a bound reference hands over when it keeps its
@@ -474,6 +490,26 @@ int  eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, in
  * and EU_OUT_SRGBA8. */
 int  eu_hip_render_samples(const eu_target *trg, eu_source *const *srcs, int nsrc, const eu_encode *enc,
                            void *out, size_t out_row_stride_bytes, int out_on_device, void *stream);
+
+/* ---- the way out as Radiance RGBE pixels --------------------------------------- */
+/* Any float frame of width x height pixels of THREE floats to RGBE quads ON THE DEVICE (eu_rgbe.hip), the mirror of
+ * eu_hip_source_load_rgbe: a frame leaves as a third of its float bytes, and the host does no per-pixel work. The
+ * quad of a pixel is eu_rgbe_encode's (include/eu_rgbe.h), the function the file route calls on the host: defined for
+ * every float, channels above 255 * 2^119 clamped to it. Frame, strides, `out_on_device` and `stream` as
+ * eu_hip_encode_samples; `out` receives width quads per row, rows out_row_stride_bytes apart, and no byte outside the
+ * quads of a row is written. There is no table, so nothing is uploaded and no buffer of the library's is read after a
+ * call with both pointers on the device. EU_ERR_ARGUMENT, before a device is looked for: null pointers, negative sizes,
+ * a stride smaller than a row, a frame or a float stride that is no multiple of 4, `out` or its stride off a 4-byte
+ * boundary. width == 0 or height == 0 is EU_OK and writes nothing. */
+int  eu_hip_encode_rgbe(const float *frame, size_t frame_row_stride_bytes, int frame_on_device, int width, int height,
+                        void *out, size_t out_row_stride_bytes, int out_on_device, void *stream);
+/* eu_hip_render with that encode behind it, as eu_hip_render_samples is built: every job eu_hip_render runs with a
+ * 3-channel target (single- and multi-facet, crops, row_begin / row_end, bands), the float frame in the library's frame
+ * buffer, the same pipeline of up to four row chunks for a host `out`. EU_ERR_ARGUMENT, before a device is looked
+ * for: what eu_hip_render and eu_hip_encode_rgbe refuse, a target channel count other than 3, stage != 0 and
+ * EU_OUT_SRGBA8. */
+int  eu_hip_render_rgbe(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out,
+                        size_t out_row_stride_bytes, int out_on_device, void *stream);
 
 /* device memory helpers for hosts without a HIP binding of their own */
 int  eu_hip_malloc(void **p, size_t bytes);

@@ -37,6 +37,11 @@
 // convert_colour() + write_one() take it - what eu_hip_render_samples wants - and write_samples() writes samples
 // that were encoded on the device into the file write_one writes.
 //
+// Radiance pictures go the same two ways: read_rgbe() returns the file's quads with their scanlines expanded,
+// rgbe_table() the float every (exponent, mantissa) pair becomes - what eu_hip_source_load_rgbe wants - and
+// write_rgbe() writes quads that eu_hip_render_rgbe encoded. The two pixel functions are those of eu_rgbe.h, for
+// read_one and write_one and for the device alike.
+//
 // Header-only, host code, no dependency on the HIP library.
 #ifndef EU_IMAGE_IO_HPP
 #define EU_IMAGE_IO_HPP
@@ -48,6 +53,7 @@
 #include <exception>
 #include <string>
 #include <vector>
+#include "eu_rgbe.h"
 
 namespace project {
 namespace io {
@@ -225,6 +231,44 @@ inline bool probe(const std::string &name, int &width, int &height, int &nchanne
   return true;
 }
 
+// one scanline of a Radiance picture, flat or run-length encoded, as width quads R G B E
+inline bool read_rgbe_scanline(FILE *f, int width, uint8_t *sl)
+{
+  uint8_t b4[4];
+  if (std::fread(b4, 1, 4, f) != 4) return false;
+  if (b4[0] == 2 && b4[1] == 2 && !(b4[2] & 0x80) && ((int(b4[2]) << 8) | b4[3]) == width && width >= 8 && width < 32768) {
+    // new run-length encoding: the four components one after the other
+    for (int c = 0; c < 4; c++) {
+      int x = 0;
+      while (x < width) {
+        int n = std::fgetc(f);
+        if (n == EOF) return false;
+        if (n > 128) {
+          n -= 128;
+          const int v = std::fgetc(f);
+          if (v == EOF || x + n > width) return false;
+          for (int i = 0; i < n; i++) sl[size_t(x++) * 4 + c] = uint8_t(v);
+        } else {
+          if (n == 0 || x + n > width) return false;
+          for (int i = 0; i < n; i++) {
+            const int v = std::fgetc(f);
+            if (v == EOF) return false;
+            sl[size_t(x++) * 4 + c] = uint8_t(v);
+          }
+        }
+      }
+    }
+    return true;
+  }
+  // flat scanline (the first pixel is already read)
+  std::memcpy(sl, b4, 4);
+  const size_t rest = size_t(width) * 4 - 4;
+  return std::fread(sl + 4, 1, rest, f) == rest;
+}
+
+// the four bytes of a quad as eu_rgbe.h takes them, whatever the host's byte order
+inline uint32_t rgbe_quad(const uint8_t *p) { return uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24); }
+
 // rows top to bottom, interleaved, the file's own channel count
 inline bool read_one(const std::string &name, header &h, float *dst, std::string &err)
 {
@@ -243,44 +287,10 @@ inline bool read_one(const std::string &name, header &h, float *dst, std::string
   if (h.rgbe) {
     std::vector<uint8_t> sl(size_t(h.width) * 4);
     for (int y = 0; y < h.height && ok; y++) {
-      uint8_t b4[4];
-      ok = std::fread(b4, 1, 4, f) == 4;
+      ok = read_rgbe_scanline(f, h.width, sl.data());
       if (!ok) break;
-      if (b4[0] == 2 && b4[1] == 2 && !(b4[2] & 0x80) && ((int(b4[2]) << 8) | b4[3]) == h.width && h.width >= 8 && h.width < 32768) {
-        // new run-length encoding: the four components one after the other
-        for (int c = 0; c < 4 && ok; c++) {
-          int x = 0;
-          while (x < h.width && ok) {
-            int n = std::fgetc(f);
-            if (n == EOF) { ok = false; break; }
-            if (n > 128) {
-              n -= 128;
-              const int v = std::fgetc(f);
-              if (v == EOF || x + n > h.width) { ok = false; break; }
-              for (int i = 0; i < n; i++) sl[size_t(x++) * 4 + c] = uint8_t(v);
-            } else {
-              if (n == 0 || x + n > h.width) { ok = false; break; }
-              for (int i = 0; i < n; i++) {
-                const int v = std::fgetc(f);
-                if (v == EOF) { ok = false; break; }
-                sl[size_t(x++) * 4 + c] = uint8_t(v);
-              }
-            }
-          }
-        }
-      } else {
-        // flat scanline (the first pixel is already read)
-        std::memcpy(sl.data(), b4, 4);
-        ok = std::fread(sl.data() + 4, 1, sl.size() - 4, f) == sl.size() - 4;
-      }
       float *d = dst + size_t(y) * row;
-      for (int x = 0; x < h.width; x++) {
-        const uint8_t *p = sl.data() + size_t(x) * 4;
-        if (p[3]) {
-          const float fexp = std::ldexp(1.0f, int(p[3]) - (128 + 8));
-          d[3 * x] = p[0] * fexp; d[3 * x + 1] = p[1] * fexp; d[3 * x + 2] = p[2] * fexp;
-        } else d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = 0.0f;
-      }
+      for (int x = 0; x < h.width; x++) eu_rgbe_decode(rgbe_quad(sl.data() + size_t(x) * 4), d + 3 * x, d + 3 * x + 1, d + 3 * x + 2);
     }
   } else if (h.maxval == 0) {
     const uint16_t one = 1;
@@ -583,6 +593,14 @@ inline bool sample_format(const std::string &name, int &bits, int &maxval)
   return false;
 }
 
+// the header of a Radiance picture with flat scanlines, the metadata as header lines: for write_one and write_rgbe
+inline void write_rgbe_header(FILE *f, int width, int height, const metadata *meta)
+{
+  std::fprintf(f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n");
+  if (meta && !meta->projection.empty()) std::fprintf(f, "Projection=%s\nHfov=%.9g\n", meta->projection.c_str(), meta->hfov);
+  std::fprintf(f, "\n-Y %d +X %d\n", height, width);
+}
+
 inline bool write_one(const std::string &name, const float *src, int width, int height, int nch, std::string &err,
                       const metadata *meta = nullptr)
 {
@@ -599,22 +617,14 @@ inline bool write_one(const std::string &name, const float *src, int width, int 
     for (int y = height - 1; y >= 0 && ok; y--) ok = std::fwrite(src + size_t(y) * row, 4, row, f) == row;
   } else if (ext == "hdr" || ext == "pic") {
     if (nch != 3) { std::fclose(f); err = name + ": a Radiance picture holds 3 channels"; return false; }
-    std::fprintf(f, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n");
-    if (meta && !meta->projection.empty()) std::fprintf(f, "Projection=%s\nHfov=%.9g\n", meta->projection.c_str(), meta->hfov);
-    std::fprintf(f, "\n-Y %d +X %d\n", height, width);
+    write_rgbe_header(f, width, height, meta);
     std::vector<uint8_t> sl(size_t(width) * 4);
     for (int y = 0; y < height && ok; y++) {
       const float *sp = src + size_t(y) * row;
       for (int x = 0; x < width; x++) {
-        const float r = sp[3 * x], g = sp[3 * x + 1], b = sp[3 * x + 2];
-        float v = r > g ? r : g;
-        v = b > v ? b : v;
+        const uint32_t q = eu_rgbe_encode(sp[3 * x], sp[3 * x + 1], sp[3 * x + 2]);
         uint8_t *p = sl.data() + size_t(x) * 4;
-        if (!(v >= 1e-32f)) { p[0] = p[1] = p[2] = p[3] = 0; continue; }     // also NaN and negatives
-        int e;
-        const float m = std::frexp(v, &e) * 256.0f / v;
-        p[0] = uint8_t(r > 0.0f ? r * m : 0.0f); p[1] = uint8_t(g > 0.0f ? g * m : 0.0f);
-        p[2] = uint8_t(b > 0.0f ? b * m : 0.0f); p[3] = uint8_t(e + 128);
+        p[0] = uint8_t(q); p[1] = uint8_t(q >> 8); p[2] = uint8_t(q >> 16); p[3] = uint8_t(q >> 24);
       }
       ok = std::fwrite(sl.data(), 1, sl.size(), f) == sl.size();
     }
@@ -698,6 +708,92 @@ inline bool write_samples(const std::string &name, const uint8_t *src, int width
     return true;
   }
   return write_samples_one(name, src, width, height, nch, err, meta);
+}
+
+// ---- Radiance pictures handed on as they are (eu_hip_source_load_rgbe, eu_hip_render_rgbe) -----------------------
+
+// read_image for .hdr / .pic without the step to float: the file's quads R G B E, rows top to bottom, scanlines
+// expanded as read_one expands them, six cube faces stacked. Every other format: false, "not a Radiance picture".
+inline bool read_rgbe(const std::string &name, std::vector<uint8_t> &quads, int &width, int &height, std::string &err)
+{
+  std::vector<std::string> faces;
+  if (name.find('%') != std::string::npos) {
+    if (!cubeface_names(name, faces)) { err = "a format string needs exactly one %s: " + name; return false; }
+  } else faces.push_back(name);
+  header h;
+  if (!probe_one(faces[0], h, err)) return false;
+  if (!h.rgbe) { err = faces[0] + ": not a Radiance picture"; return false; }
+  const size_t per = size_t(h.width) * h.height * 4;
+  try { quads.resize(per * faces.size()); }
+  catch (const std::exception &) { err = name + ": not enough host memory for " + std::to_string(h.width) + " x " + std::to_string(h.height) + " pixels"; return false; }
+  for (size_t i = 0; i < faces.size(); i++) {
+    FILE *f = std::fopen(faces[i].c_str(), "rb");
+    if (!f) { err = "cannot open " + faces[i]; return false; }
+    header g;
+    if (!read_header(f, g, err)) { std::fclose(f); err = faces[i] + ": " + err; return false; }
+    if (!g.rgbe || g.width != h.width || g.height != h.height) {
+      std::fclose(f);
+      err = faces[i] + ": size differs from the first image of the set";
+      return false;
+    }
+    bool ok = true;
+    for (int y = 0; y < h.height && ok; y++) ok = read_rgbe_scanline(f, h.width, quads.data() + i * per + size_t(y) * h.width * 4);
+    std::fclose(f);
+    if (!ok) { err = faces[i] + ": truncated pixel data"; return false; }
+  }
+  width = h.width; height = h.height * int(faces.size());
+  return true;
+}
+
+// The float a channel of a quad becomes, as a table over EVERY (E, mantissa) pair, indexed (E << 8) | mantissa:
+// read_one's decode followed by what convert_colour makes of that float on the way from `from` to `to`. A channel's
+// float depends on its pair alone, so a look-up gives the bits of read_image + convert_colour.
+inline bool rgbe_table(const std::string &from, const std::string &to, std::vector<float> &table, std::string &err)
+{
+  colour_class a, b;
+  bool same;
+  if (!colour_pair(from, to, a, b, same, err)) return false;
+  table.resize(65536);
+  for (uint32_t e = 0; e < 256; e++)
+    for (uint32_t m = 0; m < 256; m++) {
+      float v, g, bl;
+      eu_rgbe_decode(m | (e << 24), &v, &g, &bl);
+      table[(e << 8) | m] = same ? v : convert_sample(a, b, v);
+    }
+  return true;
+}
+
+// write_one for pixels that are already encoded (eu_hip_render_rgbe): `src` holds width quads per row, and the file
+// is, header and metadata included, the one write_one writes from the floats those quads were made of.
+inline bool write_rgbe_one(const std::string &name, const uint8_t *src, int width, int height, std::string &err,
+                           const metadata *meta = nullptr)
+{
+  const std::string ext = lower_ext(name);
+  if (ext != "hdr" && ext != "pic") { err = name + ": quads go to .hdr or .pic"; return false; }
+  FILE *f = std::fopen(name.c_str(), "wb");
+  if (!f) { err = "cannot create " + name; return false; }
+  write_rgbe_header(f, width, height, meta);
+  const size_t n = size_t(width) * height * 4;
+  bool ok = std::fwrite(src, 1, n, f) == n;
+  ok = std::fclose(f) == 0 && ok;
+  if (!ok) err = name + ": write failed";
+  return ok;
+}
+
+// write_image for quads: six face files for a cubemap target and a format string, else one file
+inline bool write_rgbe(const std::string &name, const uint8_t *src, int width, int height, bool cubemap, std::string &err,
+                       const metadata *meta = nullptr)
+{
+  std::vector<std::string> faces;
+  if (cubemap && name.find('%') != std::string::npos && cubeface_names(name, faces)) {
+    if (height != 6 * width) { err = "a cubemap is 1:6"; return false; }
+    metadata face_meta;
+    if (meta) { face_meta.projection = "rectilinear"; face_meta.hfov = meta->hfov; }
+    for (int i = 0; i < 6; i++)
+      if (!write_rgbe_one(faces[size_t(i)], src + size_t(i) * width * width * 4, width, width, err, meta ? &face_meta : nullptr)) return false;
+    return true;
+  }
+  return write_rgbe_one(name, src, width, height, err, meta);
 }
 
 }  // namespace io

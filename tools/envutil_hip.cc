@@ -124,6 +124,40 @@ static int run_payload(const std::string &output)
     if (args.verbose) std::printf("%s: float pixels, encoded on the host (%s)\n", output.c_str(), why.c_str());
   }
 
+  // A Radiance output leaves the device as the file's quads (eu_hip_render_rgbe): eu_rgbe_encode is the function
+  // write_one calls below - the same bytes, without the float download and the host's pass over them. A colour
+  // conversion on the way out, a target of another channel count (write_one's error message), --ray_map and several
+  // devices keep the float route.
+  const std::string oext = io::lower_ext(output);
+  if ((oext == "hdr" || oext == "pic") && !args.tethered) {
+    io::colour_class ca, cb;
+    bool same = false;
+    std::string cerr;
+    const char *why = nullptr;
+    if (ray_map) why = "a ray map's output";
+    else if (hip_dispatch::device_slots() != 1) why = "several devices";
+    else if (args.nchannels != 3) why = "not 3 channels";
+    else if (!io::colour_pair(args.working_colour_space, args.colour_space, ca, cb, same, cerr) || !same) why = "the output's colour space is not the working one";
+    if (!why) {
+      std::vector<uint8_t> quads(size_t(ow) * oh * 4);
+      args.p_output_rgbe = quads.data();
+      const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
+      args.p_output_rgbe = nullptr;
+      if (rc != 0) {
+        std::fprintf(stderr, "envutil_hip: render failed (%d): %s\n", rc, eu_hip_last_error());
+        return 1;
+      }
+      if (!io::write_rgbe(output, quads.data(), ow, oh, cube, err, &meta)) {
+        std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+        return 1;
+      }
+      if (args.verbose)
+        std::printf("saved %s (%d x %d x %d): RGBE pixels, encoded on the device\n", output.c_str(), ow, oh, args.nchannels);
+      return 0;
+    }
+    if (args.verbose) std::printf("%s: float pixels, encoded on the host (%s)\n", output.c_str(), why);
+  }
+
   std::vector<float> out(size_t(ow) * oh * args.nchannels);
   args.p_output = out.data();
   const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
@@ -169,7 +203,8 @@ static int core(int argc, const char *const *argv)
   }
 
   // pixels of the facets that are not resident yet (asset_handler, environment.h:84-227): floats, or - PNM / PAM
-  // files - the file's integer samples with the tables that say which float each value becomes
+  // files - the file's integer samples with the tables that say which float each value becomes, or - Radiance
+  // pictures - the file's quads, with such a table where the file's colour space is not the working one
   std::vector<std::vector<float>> pixels(args.facet_spec_v.size()), colour_tab(args.facet_spec_v.size()), alpha_tab(args.facet_spec_v.size());
   std::vector<std::vector<uint8_t>> samples(args.facet_spec_v.size());
   for (size_t k = 0; k < args.facet_spec_v.size(); k++) {
@@ -179,26 +214,34 @@ static int core(int argc, const char *const *argv)
       if (args.verbose) std::printf("asset %s is already resident\n", f.asset_key.c_str());
       continue;
     }
-    f.pixels = nullptr; f.samples = nullptr;
+    f.pixels = nullptr; f.samples = nullptr; f.rgbe = nullptr; f.rgbe_table = nullptr;
     int w = 0, h = 0, nch = 0, maxval = 0, sbits = 0;
     // an integer file goes up as it is and is widened and linearised on the device; whatever read_samples refuses
     // is left to the float route and to its messages
     std::string serr;
     const bool as_samples = io::read_samples(f.filename, samples[k], w, h, nch, maxval, sbits, serr);
-    if (!as_samples && !io::read_image(f.filename, pixels[k], w, h, nch, err)) {
+    // ... and so does a Radiance picture, as its quads (they share the byte buffer: a file is one or the other)
+    const bool as_rgbe = !as_samples && io::read_rgbe(f.filename, samples[k], w, h, serr);
+    if (as_rgbe) nch = 3;
+    if (!as_samples && !as_rgbe && !io::read_image(f.filename, pixels[k], w, h, nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
       return 2;
     }
     if (args.verbose)
       std::printf("%s: %s\n", f.filename.c_str(), as_samples ? (sbits == 8 ? "8-bit samples, decoded on the device" : "16-bit samples, decoded on the device")
-                                                             : "float pixels");
+                                                 : as_rgbe ? "RGBE pixels, decoded on the device" : "float pixels");
     // read_image_data: from the facet's colour space - Csp clause / --input_colour_space, else what the file's
     // format says - to the working one (envutil_basic.h:950-977)
     {
       const std::string csp = f.colour_space.empty() ? io::file_colour_space(f.filename) : f.colour_space;
       if (args.verbose && csp != args.working_colour_space)
         std::printf("converting %s from %s to %s\n", f.filename.c_str(), csp.c_str(), args.working_colour_space.c_str());
+      io::colour_class ca, cb;
+      bool same = false;
       const bool ok = as_samples ? io::sample_tables(sbits, maxval, csp, args.working_colour_space, colour_tab[k], alpha_tab[k], err)
+                    // (no table where the colour spaces agree: the device's decode is the file route's)
+                    : as_rgbe ? io::colour_pair(csp, args.working_colour_space, ca, cb, same, err) &&
+                                (same || io::rgbe_table(csp, args.working_colour_space, colour_tab[k], err))
                                  : io::convert_colour(pixels[k].data(), size_t(w) * h, nch, csp, args.working_colour_space, err);
       if (!ok) {
         std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
@@ -213,13 +256,16 @@ static int core(int argc, const char *const *argv)
     }
     // PTO masks and lens crops edit the loaded pixels (environment.h:700-890): the dispatch does that on the
     // device when it loads the facet, from the pixels at the file's own channel count
-    if (!check_facet_pixels(f, as_samples ? samples[k].size() / size_t(sbits / 8) : pixels[k].size(), nch, err)) {
+    if (!check_facet_pixels(f, as_samples ? samples[k].size() / size_t(sbits / 8) : as_rgbe ? samples[k].size() / 4 * 3 : pixels[k].size(), nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
       return 2;
     }
     if (as_samples) {
       f.samples = samples[k].data(); f.sample_bits = sbits; f.samples_big_endian = true;
       f.colour_table = colour_tab[k].data(); f.alpha_table = alpha_tab[k].data();
+    } else if (as_rgbe) {
+      f.rgbe = samples[k].data();
+      f.rgbe_table = colour_tab[k].empty() ? nullptr : colour_tab[k].data();
     } else f.pixels = pixels[k].data();
   }
 
@@ -282,6 +328,7 @@ int main(int argc, const char **argv)
         "            --twine_sigma F  --twine_threshold F  --twine_normalize  --twine_precise  --twf_file FILE\n"
         "  images:   .pfm .hdr (float), .pgm .ppm .pnm (8 / 16 bit), .pam (8 / 16 bit, alpha); a name with one %s\n"
         "            stands for six cube faces: left right top bottom front back\n"
+        "            .hdr / .pic and the integer formats go to and from the device as the file's own pixels\n"
         "  -v verbose; a trailing '-' reads one job per line from stdin (sources stay resident in HBM)");
       return 0;
     }
