@@ -12,7 +12,7 @@ present, calls raise.
 from .api import (  # noqa: F401
     EuError, Facet, Source, Target, arguments, facet_spec, get_dispatch,
     container_geometry, cubemap_metrics, device_count, get_extent, get_step,
-    lib, lib_path, make_spread, render, render_timed, render_rays, render_rays_timed, render_views, view_tables, View, sync, listed_tiles, launch_count, Rays, build, band_rows, band_frame_rows,
+    lib, lib_path, make_spread, render, render_timed, render_rays, render_rays_timed, render_views, render_layers, view_tables, View, sync, listed_tiles, launch_count, Rays, build, band_rows, band_frame_rows,
     encode_samples, render_samples, sample_steps, Encode,
     encode_rgbe, render_rgbe, Rgbe,
     layout_segments, facet_alpha, facet_alpha_dev, facet_alpha_rows, init_devices, device_slots, device_strips, render_devices,

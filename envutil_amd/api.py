@@ -161,6 +161,7 @@ def lib():
     L.eu_hip_render_rays_timed.argtypes = [vp, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_views.argtypes = [vp, vp, i32, vp, vp, C.c_size_t, C.c_size_t, i32, vp]
     L.eu_hip_render_views_multi.argtypes = [vp, vp, i32, vp, i32, vp, C.c_size_t, C.c_size_t, i32, vp]
+    L.eu_hip_render_layers.argtypes = [vp, vp, i32, vp, C.c_size_t, C.c_size_t, i32, vp]
     L.eu_hip_view_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.eu_hip_layout_segments.argtypes = [vp, vp, i32, vp, i32, vp]
     L.eu_hip_band_rows.argtypes = [i32, i32, i32, i32]
@@ -1078,6 +1079,34 @@ def render_views(args, views, source, nchannels=None, out=None, stream=None):
         handles = (C.c_void_p * len(facets))(*[s.handle for s in facets])
         _check(lib().eu_hip_render_views_multi(C.byref(t), arr, len(views), handles, len(facets), C.c_void_p(optr),
                                                row, view, int(on_device), st))
+    return out
+
+
+def render_layers(args, sources, nchannels=None, out=None, stream=None):
+    """eu_hip_render_layers: many pictures of one geometry in one call. `sources` is a list or tuple of Source that
+    share projection, size, field of view, orientation, lens, channel count and spline degree - the eyes of a stereo
+    pair, the exposures of a bracket (brighten may differ), passes, frames - and are NOT composed: every one gives a
+    frame of its own (render(args, [sources]) is the multi-facet job). Returns (L, H, W, C) float32, layer k being
+    render(args, sources[k]) bit for bit: a new numpy array, or `out` (numpy, or a float32 torch tensor in device
+    memory; rows and layers may be padded). C defaults to the layers' channel count. With `out` on the device the
+    call is asynchronous on `stream` (a hipStream_t address; None: the library's stream) until sync()."""
+    _views_args(args, "render_layers")
+    if not isinstance(sources, (list, tuple)):
+        raise EuError("render_layers: sources is a list or tuple of Source")
+    layers = list(sources)
+    nch = nchannels or (layers[0].fct.nchannels if layers else 0)
+    if not nch:
+        raise EuError("render_layers: no layer and no nchannels to shape the result by")
+    shape = (len(layers), args.height, args.width, nch)
+    if out is None:
+        out = np.zeros(shape, np.float32)
+    if tuple(out.shape) != shape:
+        raise EuError(f"render_layers: out has shape {tuple(out.shape)}, expected {shape}")
+    optr, row, layer, on_device = _frames(out, "out")
+    t = args.target(nch)
+    handles = (C.c_void_p * max(len(layers), 1))(*[s.handle for s in layers])
+    _check(lib().eu_hip_render_layers(C.byref(t), handles, len(layers), C.c_void_p(optr), row, layer, int(on_device),
+                                      C.c_void_p(stream) if stream else None))
     return out
 
 

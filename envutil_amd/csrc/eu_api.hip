@@ -3,7 +3,8 @@
 // library: without a HIP device every render/load call fails with
 // EU_ERR_NO_DEVICE.
 // This file: the state and the helpers the call families share (eu_context.h), initialisation, the pure queries,
-// memory. The families: eu_api_source.hip, eu_api_render.hip, eu_api_devices.hip, eu_api_rays.hip, eu_api_views.hip.
+// memory. The families: eu_api_source.hip, eu_api_render.hip, eu_api_devices.hip, eu_api_rays.hip, eu_api_views.hip,
+// eu_api_layers.hip.
 
 #include "eu_context.h"
 #include "eu_setup_math.h"
@@ -196,7 +197,7 @@ int eu_hip_sync(void)
   if (cur().device < 0) return EU_OK;
   HIPCHK(hipStreamSynchronize(cur().stream));
   const context &c = cur();
-  for (const eu_readers *r : { &c.tables, &c.staged.wl_pair, &c.rays.readers, &c.views.readers, &c.enc.readers, &c.alpha.readers })
+  for (const eu_readers *r : { &c.tables, &c.staged.wl_pair, &c.rays.readers, &c.views.readers, &c.layers.readers, &c.enc.readers, &c.alpha.readers })
     HIPCHK(r->host_wait());
   return EU_OK;
 }

@@ -129,6 +129,14 @@ struct context {
     eu_dev_buf<eu_src_dev> src;
     eu_readers readers;                           // scal, col, row, taps, src
   } views;
+  // eu_hip_render_layers: the one camera's stepper tables (built on the host per call), the tap table, the layer
+  // table and the staging of a host output - all its own, like the view calls' buffers
+  struct {
+    eu_dev_buf<float> col, row, stage;
+    held_table taps;
+    eu_dev_buf<eu_layer_dev> tab;
+    eu_readers readers;                           // col, row, taps, tab
+  } layers;
   // eu_hip_encode_samples / eu_hip_render_samples: the step tables on the device (colour, then alpha) with the host
   // copy they were uploaded from - it stays, so that an upload queued on a stream never reads a caller's memory after
   // the call - and the staging of a host frame and of a host output

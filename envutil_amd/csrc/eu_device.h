@@ -152,4 +152,19 @@ struct eu_view_dev {
 // the view on blockIdx.y: floats from one view's column table, row table and frame to the next one's
 struct eu_view_strides { long long col, row, out; };
 
+// eu_hip_render_layers (eu_render_layers.hip): what one picture has of its own. Everything else of its eu_src_dev
+// is layer 0's (eu_render_params::src). 16 bytes, read wave-uniformly: scalar-cache loads
+struct eu_layer_dev {
+  const float *base;           // core origin inside the layer's braced container
+  float brighten;
+  int pad;
+};
+
+// the layers of one launch, and floats from one layer's frame to the next one's
+struct eu_layers_params {
+  const eu_layer_dev *layers;
+  int nlayers;
+  long long out_layer;
+};
+
 #endif

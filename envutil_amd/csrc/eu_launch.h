@@ -90,6 +90,10 @@ int eu_launch_view_tables(const eu_view_dev *views, int nviews, int prj, int wid
                           float *row, void *stream);
 int eu_launch_render_views(const eu_render_params *p, const eu_view_strides *vs, int nviews, int path,
                            const eu_switches *sw, void *stream);
+// eu_render_layers.hip: p describes the job with layer 0's source block, lp the layers of this launch; path is an
+// eu_layer_path
+int eu_launch_render_layers(const eu_render_params *p, const eu_layers_params *lp, int path, const eu_switches *sw,
+                            void *stream);
 int eu_launch_render_multi(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch1(const eu_multi_params *p, int degree, void *stream);
 int eu_launch_render_multi_nch2(const eu_multi_params *p, int degree, void *stream);

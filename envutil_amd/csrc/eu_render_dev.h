@@ -190,6 +190,7 @@ __device__ __forceinline__ void eu_bspline(const eu_src_dev &s, float cx, float 
 }
 
 // runtime-degree evaluator for degrees above the specialised ones
+// (eu_render_layers.hip keeps a copy that takes a layer's base, eu_layers_bspline_generic: change both)
 template <int NCH>
 __device__ void eu_bspline_generic(const eu_src_dev &s, float cx, float cy, float *out)
 {

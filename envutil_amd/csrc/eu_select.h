@@ -9,7 +9,8 @@
 //   staged           eu_render4.hip   LDS-staged tiles plus the direct-gather kernel behind them
 //                                     (eu_staged_covers), two launches
 // A call with the caller's own rays (eu_hip_render_rays) has two forms of its own: eu_select_ray_path().
-// So has a sequence of views (eu_hip_render_views): eu_select_view_path().
+// So has a sequence of views (eu_hip_render_views): eu_select_view_path(), and a set of pictures of one geometry
+// (eu_hip_render_layers): eu_select_layer_path().
 #ifndef EU_SELECT_H
 #define EU_SELECT_H
 #include <algorithm>
@@ -38,12 +39,17 @@ struct eu_switches {
   int boxtab_max_kb;   // EU_HIP_BOXTAB_MAX_KB: the largest box table built, KiB (EU_BOXTAB_MAX_KB); a job beyond it gets none
   int views_max_kb;    // EU_HIP_VIEWS_MAX_KB: the most stepper tables eu_hip_render_views keeps at a time, KiB
                        // (EU_VIEWS_MAX_KB); a longer sequence goes through in chunks of views
+  int layers_max;      // EU_HIP_LAYERS_MAX: the most layers one launch of eu_hip_render_layers walks (EU_LAYERS_MAX); 0 or
+                       // negative: 0, all of them. A longer list goes through in chunks, in stream order
 };
 
 // 64 bytes per second-loop tile: 64 MiB hold the polar faces of a 6 x 8192 cubemap, four times the headline's 16 MiB
 #define EU_BOXTAB_MAX_KB 65536
 // 120 KiB per 1024 x 1024 view: 64 MiB hold the tables of 546 of them
 #define EU_VIEWS_MAX_KB 65536
+// measured ("Many pictures of one geometry"): of 1, 2, 4 and all at eight layers, four is the fastest or
+// within 6 % of the fastest on every job timed; all of them cost the big cubemap jobs 3 to 8 %
+#define EU_LAYERS_MAX 4
 
 inline eu_switches eu_read_switches()
 {
@@ -69,6 +75,8 @@ inline eu_switches eu_read_switches()
   s.boxtab_max_kb = bm && bm[0] ? std::max(0, std::min(atoi(bm), 16 * 1024 * 1024)) : EU_BOXTAB_MAX_KB;
   const char *vm = getenv("EU_HIP_VIEWS_MAX_KB");
   s.views_max_kb = vm && vm[0] ? std::max(0, std::min(atoi(vm), 16 * 1024 * 1024)) : EU_VIEWS_MAX_KB;
+  const char *lm = getenv("EU_HIP_LAYERS_MAX");
+  s.layers_max = lm && lm[0] ? std::max(0, atoi(lm)) : EU_LAYERS_MAX;
   return s;
 }
 
@@ -204,6 +212,51 @@ inline int eu_views_per_chunk(int width, int height, int max_kb, int nfct = 1)
   const unsigned long long per = nf * ((unsigned long long)6 * width + (unsigned long long)EU_ROW_FLOATS * height) * sizeof(float);
   const unsigned long long n = per ? (unsigned long long)max_kb * 1024ull / per : EU_VIEWS_MAX_GRID_Y;
   return (int)std::max<unsigned long long>(1, std::min<unsigned long long>(n, EU_VIEWS_MAX_GRID_Y / nf));
+}
+
+// ---- many pictures of one geometry (eu_hip_render_layers, eu_render_layers.hip) --------------------
+// One camera, so the host builds the stepper tables once, as eu_hip_render does; like the view calls there is no
+// plan behind the launch: no runs, no staged kernels, row strips only.
+//   general  eu_layers_kernel   one pixel per lane: every mount and degree, channel adaption, twining
+//   packed   eu_layers2_kernel  two per lane: what eu_packed_covers() admits
+// p.src is layer 0's block; the layers agree in everything asked here. A --mask_for source is refused by the entry
+// point (the paint would replace every layer's pixels alike); should one arrive, only the general form could paint it.
+enum eu_layer_path { EU_LAYERS_GENERAL, EU_LAYERS_PACKED };
+
+inline eu_layer_path eu_select_layer_path(const eu_render_params &p, const eu_switches &sw)
+{
+  if (p.src.mask_paint || sw.force_general) return EU_LAYERS_GENERAL;
+  return eu_packed_covers(p) ? EU_LAYERS_PACKED : EU_LAYERS_GENERAL;
+}
+
+// A twined job carries one sum per layer across its tap loop: the layers of a launch are taken in groups of
+// EU_LAYERS_GROUP, each group running the tap loop once. Chosen from the compiler's figures ("Many
+// pictures of one geometry"): the largest of 1, 2, 4 at which the cubic RGB lat/lon twined kernels keep the three
+// wavefronts per SIMD of their single-picture counterparts. That is 1 - at 2 the packed form needs 188 VGPRs (two
+// wavefronts), at 4 219 - so a twined launch shares the rays and their differences between layers, not yet the
+// coordinates of a tap.
+#ifndef EU_LAYERS_GROUP
+#define EU_LAYERS_GROUP 1
+#endif
+
+// The chunking arithmetic, in one place for the host glue, the kernels and the host test (constexpr: device code
+// calls them too). Layers of one launch: layers_max of them (0: all), never more than there are
+constexpr int eu_layers_per_launch(int nlayers, int layers_max)
+{
+  return layers_max > 0 && layers_max < nlayers ? layers_max : nlayers;
+}
+// launches a list of nlayers takes (eu_hip_render_layers' loop)
+constexpr int eu_layers_launches(int nlayers, int layers_max)
+{
+  return eu_layers_per_launch(nlayers, layers_max) > 0
+             ? (nlayers + eu_layers_per_launch(nlayers, layers_max) - 1) / eu_layers_per_launch(nlayers, layers_max) : 0;
+}
+// tap loops a twined launch of n layers runs per pixel, and the layers of group g (the last one may be partial): the
+// twined kernels' group loop
+constexpr int eu_layers_groups(int n, int group = EU_LAYERS_GROUP) { return n > 0 ? (n + group - 1) / group : 0; }
+constexpr int eu_layers_in_group(int n, int g, int group = EU_LAYERS_GROUP)
+{
+  return n - g * group <= 0 ? 0 : n - g * group < group ? n - g * group : group;
 }
 
 // ---- the run splitter of the packed kernel's launch-level hybrid --------------------------------

@@ -152,6 +152,12 @@ struct arguments : public facet_base
   std::string ray_map;
   const float *p_ray_map = nullptr;
   int ray_map_width = 0, ray_map_height = 0;
+  // --layer IMAGE OUTPUT, repeatable (no counterpart in the reference): further pictures of the single facet's
+  // geometry - each a copy of that facet's spec with its own file - rendered with the facet's picture in one
+  // eu_hip_render_layers. p_output then holds 1 + layer_spec_v.size() frames behind one another: the facet's, then
+  // the layers' in their order. Float output of one device only.
+  std::vector<facet_spec> layer_spec_v;
+  std::vector<std::string> layer_output_v;
 
   // target extent and step, envutil_main.cc:1203-1232
   void target_setup()
@@ -281,10 +287,8 @@ struct hip_dispatch : public dispatch_base
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
     if (args.single >= int(args.facet_spec_v.size()) || args.solo >= int(args.facet_spec_v.size())) return EU_ERR_ARGUMENT;
     std::vector<eu_source *> srcs;
-    for (size_t fi = 0; fi < args.facet_spec_v.size(); fi++) {
-      // --solo: only that facet takes part (fuse(), envutil_payload.cc:2085-2127)
-      if (args.solo >= 0 && int(fi) != args.solo) continue;
-      const auto &fct = args.facet_spec_v[fi];
+    // the facet's source: loaded on first use, resident from then on (asset_handler)
+    auto resident_source = [&](const facet_spec &fct) -> int {
       auto it = resident.find(fct.asset_key);
       if (it == resident.end()) {
         eu_facet e = to_eu(fct);
@@ -334,6 +338,21 @@ struct hip_dispatch : public dispatch_base
         if (rc != EU_OK) return rc;
       }
       srcs.push_back(it->second);
+      return EU_OK;
+    };
+    for (size_t fi = 0; fi < args.facet_spec_v.size(); fi++) {
+      // --solo: only that facet takes part (fuse(), envutil_payload.cc:2085-2127)
+      if (args.solo >= 0 && int(fi) != args.solo) continue;
+      const int rc = resident_source(args.facet_spec_v[fi]);
+      if (rc != EU_OK) return rc;
+    }
+    if (!args.layer_spec_v.empty()) {
+      // further pictures of the one facet's geometry: every one a source of its own, none of them composed
+      if (srcs.size() != 1 || args.p_ray_map || args.single >= 0) return EU_ERR_ARGUMENT;
+      for (const auto &l : args.layer_spec_v) {
+        const int rc = resident_source(l);
+        if (rc != EU_OK) return rc;
+      }
     }
     if (args.p_ray_map) {
       // `act` alone at the caller's rays: no stepper, no target geometry, no twining; float output
@@ -371,6 +390,11 @@ struct hip_dispatch : public dispatch_base
     // per GPU, the sources replicated by peer copies on first use; eu_hip.h: eu_hip_render_devices).
     // EU_HIP_DEVICES=n limits the slots, =1 keeps the single-device path.
     const int slots = device_slots();
+    if (!args.layer_spec_v.empty()) {
+      if (args.tethered || !args.p_output || args.p_output_samples || slots > 1) return EU_ERR_ARGUMENT;
+      const size_t row_bytes = size_t(w) * nchannels * sizeof(float);
+      return eu_hip_render_layers(&t, srcs.data(), int(srcs.size()), args.p_output, row_bytes, size_t(h) * row_bytes, 0, nullptr);
+    }
     if (args.tethered) {
       t.out_format = EU_OUT_SRGBA8;
       if (slots > 1)

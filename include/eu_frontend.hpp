@@ -145,9 +145,9 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_precise", 0 }, { "--twine_width", 1 }, { "--twine_density", 1 }, { "--twine_sigma", 1 },
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
-    { "--nchannels", 1 }, { "--ray_map", 1 } };
+    { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 } };
   std::map<std::string, std::string> opt;
-  std::vector<std::vector<std::string>> facets;
+  std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
   for (int i = 1; i < argc; i++) {
     const std::string key = argv[i];
@@ -157,6 +157,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     std::vector<std::string> v(argv + i + 1, argv + i + 1 + it->second);
     i += it->second;
     if (key == "--facet") facets.push_back(v);
+    else if (key == "--layer") layers.push_back(v);
     else if (key == "--photo") photos.push_back(v[0]);
     else if (key == "--pto_line") addenda.push_back(v[0]);
     else if (key == "--oiio") continue;
@@ -429,6 +430,35 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     a.twine = 0;                   // automatic twining is not applied either
   }
 
+  // --layer IMAGE OUTPUT: further pictures of the single facet's geometry, each with an output of its own. What
+  // the one call behind them (eu_hip_render_layers) does not render is refused here, not guessed
+  std::vector<image_info> layer_info;
+  if (!layers.empty()) {
+    if (a.nfacets != 1) { err = "--layer gives further pictures of ONE facet's geometry: " + std::to_string(a.nfacets) + " facets given"; return false; }
+    if (a.single >= 0 || !a.split.empty()) { err = "--layer does not go with --single / --split"; return false; }
+    if (!a.ray_map.empty()) { err = "--layer does not go with --ray_map"; return false; }
+    if (a.output.empty()) { err = "--layer needs the facet's own --output"; return false; }
+    const facet_spec &f0 = a.facet_spec_v[0];
+    for (const auto &l : layers) {
+      image_info li;
+      if (!probe || !probe(l[0], li) || li.width <= 0 || li.height <= 0 || li.nchannels <= 0) {
+        err = "failed to open layer image '" + l[0] + "'";
+        return false;
+      }
+      if (li.width != f0.window_width || li.height != f0.window_height) {
+        err = "--layer " + l[0] + " is " + std::to_string(li.width) + " x " + std::to_string(li.height) + ", the facet " +
+              std::to_string(f0.window_width) + " x " + std::to_string(f0.window_height) + ": layers share the facet's size";
+        return false;
+      }
+      if (li.nchannels != f0.nchannels) {
+        err = "--layer " + l[0] + " has " + std::to_string(li.nchannels) + " channels, the facet " + std::to_string(f0.nchannels) +
+              ": layers share the facet's channel count";
+        return false;
+      }
+      if (l[1].empty()) { err = "--layer " + l[0] + ": empty output name"; return false; }
+    }
+  }
+
   // brightness from the Eev values (envutil_main.cc:1003-1060), channel counts (:1062-1157)
   a.nchannels = 1;
   bool alpha_seen = false;
@@ -447,6 +477,15 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   const int nch = in("--nchannels", 0);
   if (nch > 0) a.nchannels = nch;
   if (bad) return false;
+  // a layer is the facet - geometry, lens, masks, brighten - with another file
+  for (const auto &l : layers) {
+    facet_spec f = a.facet_spec_v[0];
+    f.filename = l[0];
+    f.asset_key = "layer of " + a.facet_spec_v[0].asset_key + ": " + l[0];
+    f.pixels = nullptr; f.samples = nullptr; f.rgbe = nullptr; f.rgbe_table = nullptr;
+    a.layer_spec_v.push_back(f);
+    a.layer_output_v.push_back(l[1]);
+  }
 
   if (a.single >= 0) {
     // the facet's geometry becomes the target's (envutil_main.cc:1170-1182)

@@ -450,6 +450,36 @@ int  eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int n
 int  eu_hip_view_tables(const eu_target *trg, const eu_view *view, eu_source *src, float *col_dev_built,
                         float *row_dev_built, float *col_host_built, float *row_host_built);
 
+/* ---- many pictures of one geometry -------------------------------------------- */
+/* The other axis of batching: ONE camera, many pictures that share projection, size, field of view, orientation and
+ * lens - the eyes of a stereo pair, the exposures of a bracket, the passes of a rendered panorama, frames of a
+ * video. Layer k is written at out + k * out_layer_stride_bytes, rows out_row_stride_bytes apart, and is bit for
+ * bit the frame eu_hip_render(trg, &layers[k], 1, ...) gives (NaN payloads apart, as everywhere). What does not
+ * depend on the picture - ray, source coordinate, gate, split, weights, per tap for a twined job - is computed once
+ * per pixel; per layer only the taps, the weighted sum and the store are new work (eu_render_layers.hip).
+ *
+ * `trg` is whatever a single-facet eu_hip_render job may be with float output and whole frames: its own orientation
+ * and extent, a tap table, nchannels different from the layers'. The layers must agree in everything the kernels
+ * compute coordinates, gates and weights from: the device parameter block of layer k equals layer 0's byte for
+ * byte apart from the container's address and `brighten` (which may differ per layer: a bracket).
+ *
+ * EU_ERR_ARGUMENT, before a device is looked for: null pointers, nlayers < 0, stage != 0, a crop window, row bands,
+ * row_begin / row_end other than the whole frame, single != NULL, EU_OUT_SRGBA8, a --mask_for source, strides that
+ * are no multiples of 4, a row stride smaller than a row, a layer stride smaller than `height` rows, layers that
+ * do not agree (the message names the first differing layer). A null entry of `layers` is EU_ERR_HANDLE.
+ * EU_ERR_UNSUPPORTED: a facet with PTO translation or a target that needs the generic stepper, a target projection
+ * without a stepper. nlayers == 0 is EU_OK and writes nothing.
+ *
+ * With `out` on the device the call is asynchronous on `stream` (NULL: the library's) until eu_hip_sync();
+ * otherwise the layers are staged through at most 64 MiB of device memory and the call returns when `out` is
+ * complete. At most EU_HIP_LAYERS_MAX layers are walked by one launch (default 4; 0: all); a longer list goes through
+ * in chunks in stream order. The call uses buffers of its own: eu_hip_render, its plan caches,
+ * eu_hip_launch_count() and the staged kernels' work list are not touched. */
+int  eu_hip_render_layers(const eu_target *trg, eu_source *const *layers, int nlayers, float *out,
+                          size_t out_row_stride_bytes, size_t out_layer_stride_bytes, int out_on_device, void *stream);
+/* For tests and tools: how many layers the twined kernels of this build take through one tap loop (EU_LAYERS_GROUP). */
+int  eu_hip_layers_group(void);
+
 /* ---- the way out as integer samples ------------------------------------------ */
 /* Float pixels to 8- or 16-bit samples ON THE DEVICE (eu_encode.hip), the mirror of eu_hip_source_load_samples: a
  * frame leaves as a quarter or half of its float bytes, and the host does no per-sample work. The library knows

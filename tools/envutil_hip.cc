@@ -4,6 +4,8 @@
 //               --width 1024 --degree 3 --output cube.pfm
 //   envutil_hip --pto project.pto --output pano.pfm
 //   envutil_hip --facet pano.pfm spherical 360 0 0 0 --degree 3 --ray_map rays.pfm --output looked_up.pfm
+//   envutil_hip --facet left.pfm spherical 360 0 0 0 --projection cubemap --width 1024 --degree 3
+//               --output left_cube.pfm --layer right.pfm right_cube.pfm        (two pictures, one geometry, one call)
 //   envutil_hip <fixed options> -          (pipe mode: one job per line of stdin)
 //
 // The same options, defaults and PTO handling as the reference's main() / core()
@@ -85,8 +87,9 @@ static int run_payload(const std::string &output)
   // the way from the working colour space to the output's and the file's maxval, which sample a float becomes by
   // convert_colour + write_one below - the same bytes, without the float download and the host's pass over them.
   // A table the builder refuses (a curve whose code drops at a joint), --ray_map and several devices keep that route.
+  const size_t nlayers = args.layer_spec_v.size();          // --layer: every picture leaves by the float route
   int bits = 0, maxval = 0;
-  if (io::sample_format(output, bits, maxval) && !ray_map && !args.tethered && hip_dispatch::device_slots() == 1) {
+  if (!nlayers && io::sample_format(output, bits, maxval) && !ray_map && !args.tethered && hip_dispatch::device_slots() == 1) {
     // (the tables of a pair of colour spaces are kept: the jobs of a pipe-mode session share them)
     struct step_tables { bool ok; std::string why; std::vector<float> colour, alpha; };
     static std::map<std::string, step_tables> kept;
@@ -129,7 +132,7 @@ static int run_payload(const std::string &output)
   // conversion on the way out, a target of another channel count (write_one's error message), --ray_map and several
   // devices keep the float route.
   const std::string oext = io::lower_ext(output);
-  if ((oext == "hdr" || oext == "pic") && !args.tethered) {
+  if ((oext == "hdr" || oext == "pic") && !args.tethered && !nlayers) {
     io::colour_class ca, cb;
     bool same = false;
     std::string cerr;
@@ -158,7 +161,9 @@ static int run_payload(const std::string &output)
     if (args.verbose) std::printf("%s: float pixels, encoded on the host (%s)\n", output.c_str(), why);
   }
 
-  std::vector<float> out(size_t(ow) * oh * args.nchannels);
+  // the facet's frame, and behind it one frame per --layer: one eu_hip_render_layers call renders them all
+  const size_t frame = size_t(ow) * oh * args.nchannels;
+  std::vector<float> out(frame * (1 + nlayers));
   args.p_output = out.data();
   const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
   args.p_output = nullptr;
@@ -166,22 +171,28 @@ static int run_payload(const std::string &output)
     std::fprintf(stderr, "envutil_hip: render failed (%d): %s\n", rc, eu_hip_last_error());
     return 1;
   }
-  // save_array: from the working colour space to the output's where they differ (envutil_basic.h:786-812)
-  if (!io::convert_colour(out.data(), size_t(ow) * oh, args.nchannels, args.working_colour_space, args.colour_space, err)) {
-    std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
-    return 1;
+  if (nlayers && args.verbose)
+    std::printf("rendered %zu pictures of one geometry in one eu_hip_render_layers call\n", 1 + nlayers);
+  for (size_t k = 0; k <= nlayers; k++) {
+    const std::string &name = k ? args.layer_output_v[k - 1] : output;
+    float *px = out.data() + k * frame;
+    // save_array: from the working colour space to the output's where they differ (envutil_basic.h:786-812)
+    if (!io::convert_colour(px, size_t(ow) * oh, args.nchannels, args.working_colour_space, args.colour_space, err)) {
+      std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+      return 1;
+    }
+    // (a ray map's output has no projection of its own to record)
+    if (!io::write_image(name, px, ow, oh, args.nchannels, cube, err, ray_map ? nullptr : &meta)) {
+      std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+      return 1;
+    }
+    if (args.verbose) std::printf("saved %s (%d x %d x %d)\n", name.c_str(), ow, oh, args.nchannels);
   }
-  // (a ray map's output has no projection of its own to record)
-  if (!io::write_image(output, out.data(), ow, oh, args.nchannels, cube, err, ray_map ? nullptr : &meta)) {
-    std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
-    return 1;
-  }
-  if (args.verbose) std::printf("saved %s (%d x %d x %d)\n", output.c_str(), ow, oh, args.nchannels);
   return 0;
 }
 
 // core(), envutil_main.cc:1634-1727
-static int core(int argc, const char *const *argv)
+static int core(int argc, const char *const *argv, bool pipe_mode = false)
 {
   std::string err;
   image_probe probe = [&](const std::string &name, image_info &info) {
@@ -195,6 +206,20 @@ static int core(int argc, const char *const *argv)
     std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
     return 2;
   }
+  if (!args.layer_spec_v.empty()) {
+    if (pipe_mode) {
+      std::fprintf(stderr, "envutil_hip: --layer does not go with pipe mode: one call renders the layers, then the program ends\n");
+      return 2;
+    }
+    if (args.store_cropped) {
+      std::fprintf(stderr, "envutil_hip: --layer renders whole frames: the p-line's crop (S clause) does not go with it\n");
+      return 2;
+    }
+    if (hip_dispatch::device_slots() > 1) {
+      std::fprintf(stderr, "envutil_hip: --layer renders on one device: set EU_HIP_DEVICES=1 on a host with several\n");
+      return 2;
+    }
+  }
   const auto *dp = static_cast<const hip_dispatch *>(get_dispatch());
   if (args.verbose) std::printf("using %s (%s)\n", dp->hwy_target_name.c_str(), dp->hwy_target_str.c_str());
   if (!args.twine_setup()) {
@@ -205,11 +230,13 @@ static int core(int argc, const char *const *argv)
   // pixels of the facets that are not resident yet (asset_handler, environment.h:84-227): floats, or - PNM / PAM
   // files - the file's integer samples with the tables that say which float each value becomes, or - Radiance
   // pictures - the file's quads, with such a table where the file's colour space is not the working one
-  std::vector<std::vector<float>> pixels(args.facet_spec_v.size()), colour_tab(args.facet_spec_v.size()), alpha_tab(args.facet_spec_v.size());
-  std::vector<std::vector<uint8_t>> samples(args.facet_spec_v.size());
-  for (size_t k = 0; k < args.facet_spec_v.size(); k++) {
-    facet_spec &f = args.facet_spec_v[k];
-    if (args.solo >= 0 && int(k) != args.solo) continue;
+  // (the pictures of --layer come behind the facets: each by the route its own file type takes)
+  const size_t nfct = args.facet_spec_v.size(), nimg = nfct + args.layer_spec_v.size();
+  std::vector<std::vector<float>> pixels(nimg), colour_tab(nimg), alpha_tab(nimg);
+  std::vector<std::vector<uint8_t>> samples(nimg);
+  for (size_t k = 0; k < nimg; k++) {
+    facet_spec &f = k < nfct ? args.facet_spec_v[k] : args.layer_spec_v[k - nfct];
+    if (k < nfct && args.solo >= 0 && int(k) != args.solo) continue;
     if (dp->resident.count(f.asset_key)) {
       if (args.verbose) std::printf("asset %s is already resident\n", f.asset_key.c_str());
       continue;
@@ -321,6 +348,8 @@ int main(int argc, const char **argv)
         "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge\n"
         "  rays:     --ray_map FILE.pfm  the single facet's image at the rays x y z of a 3-channel PFM, in the facet's\n"
         "            frame (no yaw / pitch / roll, no twining); the output has the map's size\n"
+        "  layers:   --layer IMAGE OUTPUT (repeatable)  a further picture of the single facet's geometry - same size and\n"
+        "            channels - with an output of its own; all of them are rendered in one call, float route\n"
         "  target:   --output FILE  --projection P  --hfov DEG  --width W  --height H  --yaw --pitch --roll DEG\n"
         "            --x0 --x1 --y0 --y1 (extent instead of hfov)  --nchannels N  --brighten F\n"
         "  spline:   --degree D  --prefilter D  --support_min PX  --tile_size PX (cubemap sources)\n"
@@ -341,7 +370,7 @@ int main(int argc, const char **argv)
     if (sv.empty()) continue;
     std::vector<const char *> av(argv, argv + argc);
     for (const auto &t : sv) av.push_back(t.c_str());
-    const int r = core(int(av.size()), av.data());
+    const int r = core(int(av.size()), av.data(), true);
     if (r) rc = r;
   }
   return rc;
