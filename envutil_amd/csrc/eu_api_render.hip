@@ -372,7 +372,8 @@ int launch_staged(const eu_render_params *p, const eu_switches &sw, hipStream_t 
   // the work list, the persistent kernel's queues and the cached plans belong to ONE launch pair at a time: `st` waits
   // for the pair before, the event moves behind this one - on any stream, for eu_hip_listed_tiles() the library's own too
   if (cur().staged.wl_pair.order_after(st) != hipSuccess) return -1;
-  const int rc = eu_launch_render4(&q, &sw, cur().plan.h_row.data(), cur().plan.h_row.size(), cur().plan.plan_gen, st, launches);
+  const int rc = eu_launch_render4(&q, &sw, cur().plan.h_row.data(), cur().plan.h_row.size(), cur().plan.h_col.data(),
+                                   cur().plan.h_col.size(), cur().plan.plan_gen, st, launches);
   if (rc || !*launches) return rc;
   return cur().staged.wl_pair.note(st) != hipSuccess ? -1 : 0;
 }

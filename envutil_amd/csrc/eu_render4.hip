@@ -38,6 +38,7 @@
 #include <algorithm>
 #include "eu_packed_dev.h"
 #include "eu_launch.h"
+#include "eu_polar_groups.h"
 
 #define EU4_TW 16          // wave tile, pixels
 #define EU4_TH 8
@@ -121,6 +122,13 @@ struct eu4_plan {
   unsigned long long l1_magic;
   const int *xtab;        // [plan][tiles16] { min, max } of the column entries' base position ix; min = INT_MAX: not fast
   const int *boxtab;      // the second loop's tile boxes (eu_render5.h: EU5_BT_RECS records per tile of the rows in l2_rows); null: none
+  // the second loop's list where it reads the box table: entries of EU_POLAR_ENTRY_INTS ints (eu_polar_groups.h: a leader
+  // tile row and the rows rendered from its angles), those of XCD x at l2p_ent[EU_POLAR_ENTRY_INTS * l2p_off[x] ...]; an
+  // entry covers l2p_ecols tile columns in l2p_bpe batches of l2p_bcols; l2p_magic = floor(2^40 / l2p_bpe) + 1
+  const int *l2p_ent;
+  int l2p_off[9];
+  int l2p_ecols, l2p_bcols, l2p_bpe;
+  unsigned long long l2p_magic;
 #ifdef EU5_STAMPS
   unsigned long long *stamps;   // diagnostic build: 8 s_memtime stamps per tile of eu_render5_kernel
 #endif
@@ -467,6 +475,9 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
 // follower tiles (eu_share_groups.h) of the plan about to be launched / of the last launch of eu_render5_kernel's FAST form
 static long long eu4_followers_plan = 0, eu4_followers_last = 0;
 extern "C" unsigned long long eu_hip_share_follower_tiles(void) { return (unsigned long long)eu4_followers_last; }
+// ... and the same for the second loop's groups (eu_polar_groups.h): counted where the launch read the box table
+static long long eu4_polar_plan = 0, eu4_polar_last = 0;
+extern "C" unsigned long long eu_hip_polar_follower_tiles(void) { return (unsigned long long)eu4_polar_last; }
 // whether the last launch of eu_render5_kernel's FAST form read a box table (1, also for one of zero tiles) or not (0),
 // and the tiles that table holds
 static int eu4_boxtab_last = 0;
@@ -509,6 +520,7 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
     if (wgs <= 0) return -1;
     if (fast) eu4_followers_last = eu4_followers_plan;
     eu4_boxtab_last = bt;
+    if (bt) eu4_polar_last = eu4_polar_plan;
     if (bt) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
     else if (fast) hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, true>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
     else hipLaunchKernelGGL((eu_render5_kernel<NCH, DEG, PRJ, false>), dim3((unsigned)wgs), dim3(64 * EU5_WAVES), 0, st, p, w);
@@ -560,7 +572,7 @@ static_assert(EU_STAGED_TILE_ROWS == EU4_TH && EU_STAGED_MAX_TILES_Y == 65535 * 
 namespace {
 struct plan_cache {
   std::vector<unsigned char> key;
-  eu_dev_buf<int> tileplan, l2_rows, l1_ent, xtab, boxtab;
+  eu_dev_buf<int> tileplan, l2_rows, l1_ent, xtab, boxtab, l2p_ent;
   bool has_boxtab = false;   // the second loop's box table exists (it may hold no tile)
   long long boxtab_tiles = 0;
   eu_dev_buf<float> coltab;
@@ -570,6 +582,9 @@ struct plan_cache {
   int l1_off[9] = {};
   int l1_ecols = 1;
   long long follower_tiles = 0;
+  int l2p_off[9] = {};
+  int l2p_ecols = 1, l2p_bcols = 2;
+  long long polar_follower_tiles = 0;
 } g4s[EU_MAX_SLOTS];
 // one cache per device slot (eu_api_devices.hip: eu_hip_init_devices)
 #define g4 (g4s[eu_current_slot()])
@@ -593,13 +608,13 @@ void launch_colplan(const eu_render_params &p, float *ct, const float *k, hipStr
 // everything the cached plans depend on
 std::vector<unsigned char> eu4_plan_key(const eu_render_params &p, unsigned long long plan_gen, const eu_switches &sw)
 {
-  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 11 * sizeof(int));
+  std::vector<unsigned char> key(sizeof(unsigned long long) + sizeof(eu_src_dev) + 12 * sizeof(int));
   unsigned char *q = key.data();
   memcpy(q, &plan_gen, sizeof plan_gen); q += sizeof plan_gen;
   eu_src_dev sd = p.src; sd.base = nullptr;
   memcpy(q, &sd, sizeof sd); q += sizeof sd;
-  const int v[11] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, sw.share,
-                      sw.boxtab, sw.boxtab_max_kb };
+  const int v[12] = { p.width, p.row_begin, p.row_end, p.band_shift, p.band_count, p.band_index, p.form, p.norm_mode, sw.share,
+                      sw.boxtab, sw.boxtab_max_kb, sw.polar_share };
   memcpy(q, v, sizeof v);
   return key;
 }
@@ -620,34 +635,16 @@ void launch_boxplan(const eu_render_params &p, const float *atab_g, const int *l
 // the plans of a lat/lon job into the slot's cache: the tile rows' plan ids, the second loop's rows, the column
 // tables (one kernel launch per plan) and, from their bits, the first loop's entries (eu_share_groups.h)
 int eu4_build_plans(const eu_render_params &p, int tiles16, const eu_switches &sw, const float *h_row,
-                    size_t h_row_floats, hipStream_t st)
+                    size_t h_row_floats, const float *h_col, size_t h_col_floats, hipStream_t st)
 {
+  static_assert(EU_TILE_ROWS == EU4_TH && EU_PLAN_MAX == EU4_MAX_PLANS && EU_SECOND_LOOP_UNIT_ROWS == EU5_UNIT_ROWS,
+                "eu_polar_groups.h: what a host program takes for the launcher's constants");
   std::vector<int> tp((size_t)p.tiles_y, -1);
   std::vector<float> plans;          // 4 floats per plan: A0, A2, B0, B2
   const bool can = p.form == EU_FORM_BA && p.norm_mode == EU_NORM_NONE && h_row;
-  if (can && sw.colplan) {
-    for (int ty = 0; ty < p.tiles_y; ty++) {
-      float k[4] = { 0, 0, 0, 0 };
-      bool same = true;
-      for (int ly = 0; ly < EU4_TH && same; ly++) {
-        const int y = std::min(p.row_begin + ty * EU4_TH + ly, p.row_end - 1);
-        const size_t fr = (size_t)eu_frame_row(y, p.band_shift, p.band_count, p.band_index) * EU_ROW_FLOATS;
-        if (fr + 6 > h_row_floats) { same = false; break; }
-        const float c[4] = { h_row[fr + 0], h_row[fr + 2], h_row[fr + 3], h_row[fr + 5] };
-        if (ly == 0) memcpy(k, c, sizeof k);
-        else same = memcmp(k, c, sizeof k) == 0;
-      }
-      if (!same) continue;
-      int id = -1;
-      for (size_t j = 0; j < plans.size() / 4 && id < 0; j++)
-        if (memcmp(&plans[4 * j], k, sizeof k) == 0) id = (int)j;
-      if (id < 0 && plans.size() / 4 < EU4_MAX_PLANS) {
-        id = (int)(plans.size() / 4);
-        plans.insert(plans.end(), k, k + 4);
-      }
-      tp[(size_t)ty] = id;
-    }
-  }
+  if (can && sw.colplan)
+    eu_tile_row_plans(h_row, h_row_floats, EU_ROW_FLOATS, p.row_begin, p.row_end,
+                      [&](int y) { return eu_frame_row(y, p.band_shift, p.band_count, p.band_index); }, tp, plans);
   const int nplans = (int)(plans.size() / 4);
   // the previous launch pair may still read the old plans, on this stream or on another: `st` is ordered behind it
   // (eu_launch.h), so when `st` is through, that pair is
@@ -660,12 +657,24 @@ int eu4_build_plans(const eu_render_params &p, int tiles16, const eu_switches &s
   auto paired = [&](int m) { return 2 * m + 1 < p.tiles_y && tp[(size_t)2 * m] >= 0 && tp[(size_t)2 * m] == tp[(size_t)2 * m + 1]; };
   {
     // the second loop's rows per XCD: units of EU5_UNIT_ROWS tile rows dealt round-robin, as in the first loop
-    std::vector<int> rows[8], all;
-    for (int r = 0; r < p.tiles_y; r++)
-      if (!paired(r >> 1)) rows[(r / EU5_UNIT_ROWS) & 7].push_back(r);
-    for (int x = 0; x < 8; x++) { g4.l2_off[x] = (int)all.size(); all.insert(all.end(), rows[x].begin(), rows[x].end()); }
-    g4.l2_off[8] = (int)all.size();
+    std::vector<int> all;
+    eu_second_loop_rows(tp, EU5_UNIT_ROWS, all, g4.l2_off);
     if (!upload(g4.l2_rows, all, 1)) return -1;
+    // ... and who may follow whom there, from the bits of the tables the kernel reads (eu_polar_groups.h): the list
+    // of the loop's form that reads the box table
+    eu_polar_input pin;
+    pin.width = p.width; pin.tiles16 = tiles16; pin.row_begin = p.row_begin; pin.row_end = p.row_end;
+    pin.band_mode = p.band_count > 1;
+    pin.nrows = (int)all.size(); pin.rows = all.data();
+    pin.h_row = h_row; pin.h_row_floats = h_row_floats; pin.row_floats = EU_ROW_FLOATS;
+    pin.h_col = h_col; pin.h_col_floats = h_col_floats;
+    pin.mode = can ? sw.polar_share : 0; pin.unit_rows = EU5_UNIT_ROWS;
+    eu_polar_result pr;
+    eu_polar_build(pin, pr);
+    if (!upload(g4.l2p_ent, pr.entries, EU_POLAR_ENTRY_INTS)) return -1;
+    for (int x = 0; x < 9; x++) g4.l2p_off[x] = pr.off[x];
+    g4.l2p_ecols = pr.ecols; g4.l2p_bcols = pr.bcols;
+    g4.polar_follower_tiles = pr.follower_tiles;
   }
   // the second loop's box table (eu_render5.h), for the FAST form - the only reader: one wave per tile of those rows,
   // on the stream the plans are built on. A table beyond sw.boxtab_max_kb is not built: the job takes the loop that
@@ -739,6 +748,11 @@ void eu4_fill_plan(eu4_plan &w)
   w.l1_magic = (1ull << 40) / (unsigned long long)w.l1_ecols + 1;
   w.xtab = g4.xtab.p;
   w.boxtab = g4.has_boxtab ? g4.boxtab.p : nullptr;
+  w.l2p_ent = g4.l2p_ent.p;
+  for (int x = 0; x < 9; x++) w.l2p_off[x] = g4.l2p_off[x];
+  w.l2p_ecols = g4.l2p_ecols; w.l2p_bcols = g4.l2p_bcols;
+  w.l2p_bpe = std::max(1, (w.l2p_ecols + w.l2p_bcols - 1) / w.l2p_bcols);
+  w.l2p_magic = (1ull << 40) / (unsigned long long)w.l2p_bpe + 1;
 }
 
 int launch4(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
@@ -798,10 +812,10 @@ int launch4_stamped(const eu_render_params &p, eu4_plan &w, hipStream_t st)
 }  // namespace
 
 extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *sw, const float *h_row, size_t h_row_floats,
-                                 unsigned long long plan_gen, void *stream, int *launches)
+                                 const float *h_col, size_t h_col_floats, unsigned long long plan_gen, void *stream, int *launches)
 {
   eu_render_params p = *pp;
-  eu4_followers_last = 0;
+  eu4_followers_last = 0; eu4_polar_last = 0;
   eu4_boxtab_last = 0; eu4_boxtab_tiles_last = 0;
   *launches = 2;
   if (!eu_staged_covers(p) || !p.wl) return -2;
@@ -817,13 +831,14 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
   if (p.src.prj == EU_SPHERICAL) {
     std::vector<unsigned char> key = eu4_plan_key(p, plan_gen, *sw);
     if (key != g4.key) {
-      if (eu4_build_plans(p, w.tiles16, *sw, h_row, h_row_floats, st)) return -1;
+      if (eu4_build_plans(p, w.tiles16, *sw, h_row, h_row_floats, h_col, h_col_floats, st)) return -1;
       g4.key.swap(key);
     }
     if (sw->r4 != 1 && !eu_staged_worth(p.src.degree, g4.planned_rows, p.tiles_y)) { *launches = 0; return 0; }
   }
   eu4_fill_plan(w);
   eu4_followers_plan = g4.follower_tiles;
+  eu4_polar_plan = g4.polar_follower_tiles;
   eu4_boxtab_tiles_last = w.boxtab ? g4.boxtab_tiles : 0;
 #ifdef EU5_STAMPS
   return launch4_stamped(p, w, st);

@@ -213,8 +213,13 @@ struct eu5_co8 {
 
 // the reference's operations in the reference's order (stepper.h ray, geometry.h:278-301,
 // environment.h:988-1006, map.h gates) in their leanest instruction forms (eu_math2.h, round 3)
-template <int DEG>
-__device__ __forceinline__ void eu5_coords8(const eu_src_dev &s, const float *atab, const eu5_tab8 &T, eu5_co8 &c)
+// in two halves. The angles: ray, range test, root, both atan2 chains, the flags ...
+struct eu5_ang8 {
+  eu_f2 lon, lat;
+  eu_i2 ok;                   // 0 for a pixel that left the fast path of the coordinate arithmetic
+};
+
+__device__ __forceinline__ void eu5_angles8(const float *atab, const eu5_tab8 &T, eu5_ang8 &a)
 {
   eu_i2 big0 = { 0, 0 }, big1 = { 0, 0 };
   const eu_f2 c0 = T.c0;
@@ -222,9 +227,16 @@ __device__ __forceinline__ void eu5_coords8(const eu_src_dev &s, const float *at
   const eu_i2 ok = { ~eu5_out_of_range3(rx.x, ry.x, rz.x), ~eu5_out_of_range3(rx.y, ry.y, rz.y) };
   const eu_f2 q2 = rx * rx + rz * rz;
   const eu_f2 qs = eu_sqrt2_safe(q2);
-  const eu_f2 lat = eu_atan2f_2_lean(ry, qs, atab, 1, big0);
-  const eu_f2 lon = eu_atan2f_2_lean(rx, rz, atab, 0, big1);
-  c.ok = ok & ~(big0 | big1);
+  a.lat = eu_atan2f_2_lean(ry, qs, atab, 1, big0);
+  a.lon = eu_atan2f_2_lean(rx, rz, atab, 0, big1);
+  a.ok = ok & ~(big0 | big1);
+}
+
+// ... and both halves of md_to_spline, the gates and the x split: all of a tile's coordinate stage that is not
+// the same bits in its twin and its mirror (eu_polar_groups.h), which take lon / lat with a sign bit flipped
+template <int DEG>
+__device__ __forceinline__ void eu5_spline_xy(const eu_src_dev &s, eu_f2 lon, eu_f2 lat, eu5_co8 &c)
+{
   eu_f2 i0 = { (float)((double)lon.x - s.tex_x0), (float)((double)lon.y - s.tex_x0) };
   if (s.cdiv_ok) i0 = eu_div2_const(i0, s.ext_w, s.rcp_ext_w);
   else i0 = eu_div2_rr(i0, s.ext_w, eu_rcp_refined(s.ext_w));
@@ -242,6 +254,15 @@ __device__ __forceinline__ void eu5_coords8(const eu_src_dev &s, const float *at
   i1 = i1 * s.total_h; i1 = i1 - .5f;
   const eu_f2 sy = i1 - s.win_y_off;
   c.ty = eu5_gate2(sy, s.gate1, s.lower1, s.upper1);
+}
+
+template <int DEG>
+__device__ __forceinline__ void eu5_coords8(const eu_src_dev &s, const float *atab, const eu5_tab8 &T, eu5_co8 &c)
+{
+  eu5_ang8 a;
+  eu5_angles8(atab, T, a);
+  c.ok = a.ok;
+  eu5_spline_xy<DEG>(s, a.lon, a.lat, c);
 }
 
 // the y half of the split: c.ty holds the gated coordinate and becomes its fraction
@@ -653,6 +674,7 @@ typedef unsigned eu5_u3 __attribute__((ext_vector_type(3)));
 typedef unsigned eu5_u4 __attribute__((ext_vector_type(4)));
 typedef int eu5_i4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) eu5_i4 *eu5_crec;   // read through the scalar cache
+typedef const __attribute__((address_space(4))) int *eu5_cint;
 
 __device__ __forceinline__ int eu5_bt_pack(const eu5_box &b, int w3, int c)
 {
@@ -714,126 +736,193 @@ __global__ __launch_bounds__(256) void eu5_boxplan_kernel(const eu_render_params
   if (lane < 4 * EU5_BT_RECS) tab[(size_t)g * (4 * EU5_BT_RECS) + lane] = v;
 }
 
-// One 16x8 tile of the second loop WITH the box table. R: the tile's record 0, requested through the scalar
-// cache a tile ahead; rec: where the tile's records lie. The box is known before the coordinates are, so the
-// order of a tile is: table values (requested by the previous tile ahead of its stores) -> staging of the first
-// pass -> coordinate stage and weights, under the staging's round trip -> ONE wait -> taps -> the next tile's
-// table values -> two stores, always. No reduction, no lane reads, no fit cascade, no gate tests, no fast-path
-// flags; a tile of the work list is appended without its coordinate stage. Later passes stay serial in the one
-// slice.
+// One POSITION of the second loop WITH the box table: a 16x8 tile - the leader: tile row m0 (slot slot0 of
+// w.l2_rows), tile column tcol - and the members the host found to have the leader's angles with a sign bit flipped
+// (eu_polar_groups.h: ent, n): its twin (lane rows the other way, the latitude's sign), its column mirror (tile column
+// tiles16 - 1 - tcol, the lane's columns W-1-xa and W-2-xa, the longitude's sign) and the twin's mirror.
+//   angles, once: ray, range test, root, both atan2 chains (eu5_angles8), under the staging of the leader's first pass;
+//   member stage, per member: its record 0 (requested a member ahead through the scalar cache; R: the leader's,
+//     requested a position ahead) -> staging of its first pass -> eu5_spline_xy on the angles with the member's sign
+//     bits, the y split and the weights, under the staging's round trip -> ONE wait -> taps -> two stores, always.
+// The box is known before the coordinates are: no reduction, no lane reads, no fit cascade, no gate tests, no
+// fast-path flags; a member of the work list is appended on its own, without its coordinate stage; later passes
+// stay serial in the one slice. A lane keeps its (rw, pr, hf) in every member: a half or a quarter of a member's
+// records is the one the lane's pixels lie in there.
+// T: the leader's table values, requested by the PREVIOUS position ahead of its last stores, dead behind the angles;
+// the next leader's (have_n, ty_n, x0_n) are requested into T itself ahead of the last member's stores, which
+// therefore stand behind the member loop.
 template <int NCH, int DEG>
 __device__ __forceinline__ void eu5_tile_bt(const eu_render_params &p, const eu4_plan &w, const float *atab, float *wtile,
-                                            int tile_y, int x0, int lane, const eu5_tab8 &T, eu5_i4 R, eu5_crec rec,
-                                            bool have_n, int ty_n, int x0_n, eu5_tab8 &Tn)
+                                            int lane0, eu5_tab8 &T, eu5_i4 R, eu5_cint ent, int n, int m0, int slot0,
+                                            int tcol, bool have_n, int ty_n, int x0_n)
 {
   constexpr int order = DEG + 1;
   const eu_src_dev &s = p.src;
+  const eu5_crec bt = (eu5_crec)w.boxtab;
+  const unsigned lds_tile = (unsigned)(unsigned long long)(eu4_lds_void)wtile;
 #ifdef EU5_STAMPS
   unsigned long long st_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
 #endif
   EU5_STAMP(0);
-  const int cls = R.w;
-  if (cls & EU5_BT_WORK) {
-    if (lane == 0) {
-      const int id = tile_y * w.tiles16 + x0 / EU4_TW;
-      const int sh = eu4_shard_of(id);
-      const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
-      p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
+  eu5_ang8 A;
+  A.lon = (eu_f2){ 0.0f, 0.0f }; A.lat = (eu_f2){ 0.0f, 0.0f };
+  if (n > 1 || !(R.w & EU5_BT_WORK)) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    // the table values first: their wait is the one for the loads requested ahead of the previous position's stores;
+    // behind the staging it would be a wait for the staging and those stores (vmcnt counts in issue order)
+    eu5_tab8 Tl = T;
+    asm volatile("" : "+v"(Tl.c0), "+v"(Tl.A0), "+v"(Tl.A1), "+v"(Tl.A2), "+v"(Tl.B0), "+v"(Tl.B1), "+v"(Tl.B2));
+    if (!(R.w & EU5_BT_WORK) && (R.w & 7) > 0 && R.z >= 0) {
+      const eu5_box bx = { R.x, R.y, R.x + (R.z & 0xffff), R.y + (R.z >> 16) };
+      eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
     }
-    if (have_n) eu5_load8<true>(p, ty_n, x0_n, lane, Tn);
-    __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);         // (no stores behind these loads: see the stores below)
-    return;
+    eu5_angles8(atab, Tl, A);
   }
-  const int npass = cls & 7;
-  const unsigned lds_tile = (unsigned)(unsigned long long)(eu4_lds_void)wtile;
-  // the table values first: their wait is the one for the loads requested ahead of the previous tile's stores;
-  // behind the staging it would be a wait for the staging and those stores (vmcnt counts in issue order)
-  eu5_tab8 Tl = T;
-  asm volatile("" : "+v"(Tl.c0), "+v"(Tl.A0), "+v"(Tl.A1), "+v"(Tl.A2), "+v"(Tl.B0), "+v"(Tl.B1), "+v"(Tl.B2));
-  eu5_box bx = { R.x, R.y, R.x + (R.z & 0xffff), R.y + (R.z >> 16) };
-  bool some = npass > 0 && R.z >= 0;
-  if (some) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
-  const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
-  const int y = p.row_begin + tile_y * EU4_TH + rw;
-  const bool yin = y < p.row_end;
-  const int xa = x0 + 8 * hf + 2 * pr, xb = xa + 1;
-  const bool va = yin && xa < p.width, vb = yin && xb < p.width;
-  eu_f2 rga = { 0.0f, 0.0f }, bxa = { 0.0f, 0.0f }, rgb = { 0.0f, 0.0f }, bxb = { 0.0f, 0.0f };
-  if (npass > 0) {
-    eu5_co8 c;
-    eu5_coords8<DEG>(s, atab, Tl, c);
-    eu5_split_y<DEG>(c);
-#ifdef EU5_STAMPS
-    asm volatile("" : : "v"(c.iya), "v"(c.iyb), "v"(c.ixa), "v"(c.ixb));
-#endif
-    EU5_STAMP(2);
-#ifdef EU5_STAMPS
-    st_[3] = st_[2];
-#endif
-    eu_f2 wx[order], wy[order];
-    if constexpr (DEG >= 2) {
-      eu_weights2<DEG>(s.wm, c.ty, wy);
-      eu_weights2<DEG>(s.wm, c.tx, wx);
-    }
-    const int grp = npass == 1 ? 0 : npass == 2 ? hf : (lane >> 4);
-#pragma unroll 1
-    for (int pi = 0; pi < npass; pi++) {
-      // the next pass's record, requested under this pass
-      eu5_i4 Rn = { 0, 0, -1, 0 };
-      if (pi + 1 < npass) Rn = rec[pi + 1];
-      if (some) {
-        if (pi > 0) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
-        const int ibw = bx.mxx - bx.mnx + order;
-        // lanes of other groups and lanes without a hit read the box origin
-        const bool mine = grp == pi;
-        const int oa = (mine && va) ? ((c.iya - bx.mny) * ibw + (c.ixa - bx.mnx)) * 4 : 0;
-        const int ob = (mine && vb) ? ((c.iyb - bx.mny) * ibw + (c.ixb - bx.mnx)) * 4 : 0;
-        if (pi == 0) EU5_STAMP(4);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (pi == 0) EU5_STAMP(5);
-        if (mine) eu5_taps<NCH, DEG>((eu_lptr)wtile, oa, ob, ibw * 4, wx, wy, c.tx, c.ty, rga, bxa, rgb, bxb);
-      }
-      bx = (eu5_box){ Rn.x, Rn.y, Rn.x + (Rn.z & 0xffff), Rn.y + (Rn.z >> 16) };
-      some = Rn.z >= 0;
-    }
-  }
-#ifdef EU5_STAMPS
-  asm volatile("" : : "v"(rga), "v"(bxa), "v"(rgb), "v"(bxb));
-#endif
-  EU5_STAMP(6);
-  // zero on a miss (FAST: every ray hits, a miss is a pixel outside the frame, which is not stored); storer
-  float qa[4] = { rga.x, rga.y, bxa.x, bxa.y }, qb[4] = { rgb.x, rgb.y, bxb.x, bxb.y };
-  if (have_n) eu5_load8<true>(p, ty_n, x0_n, lane, Tn);
-  __builtin_amdgcn_sched_barrier(0);
-  {
-    // Stores WITHOUT a branch around them: the tile's rows as a buffer, a pixel outside the frame gets an offset
-    // beyond the buffer's end, which the hardware drops (launch4_ndp: eight rows of the output are below 2^31
-    // bytes). Behind 'if (va)' a store sits behind a branch that skips it when no lane stores, the compiler cannot
-    // count the stores behind the table-value loads above, and the next tile's wait for those loads becomes
-    // vmcnt(0): a wait for this tile's stores to be acknowledged, 1-2k cycles at the head of every tile. With two
-    // stores on every path it is vmcnt(2). Every other path to a tile's head ends in an explicit vmcnt(0).
-    float *const base = p.out + (long long)(tile_y * EU4_TH) * p.out_stride + (long long)x0 * NCH;
+  int mk = m0, sk = slot0;
+  eu5_i4 Rk = R;
+  eu_f2 rga, bxa, rgb, bxb;
+  unsigned oa, ob;
+  int srow;
+  // Stores WITHOUT a branch around them: the tile's rows as a buffer, a pixel outside the frame - and every pixel of
+  // a member of the work list - gets an offset beyond the buffer's end, which the hardware drops (launch4_ndp: eight
+  // rows of the output are below 2^31 bytes). Behind 'if (va)' a store sits behind a branch that skips it when no
+  // lane stores, the compiler cannot count the stores behind the table-value loads, and the next position's wait for
+  // those loads becomes vmcnt(0): a wait for the stores to be acknowledged, 1-2k cycles. With two stores on every
+  // path it is vmcnt(2).
+  auto put = [&]() {
+    float *const base = p.out + (long long)(srow * EU4_TH) * p.out_stride;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x80000000u, 0x00027000);
-    const unsigned off = ((unsigned)rw * (unsigned)p.out_stride + (unsigned)((8 * hf + 2 * pr) * NCH)) * 4u;
-    const unsigned oa = va ? off : 0xfffff000u, ob = vb ? oa + NCH * 4u : 0xfffff000u;     // (vb implies va)
     if constexpr (NCH == 3) {
-      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(qa[0]), __float_as_uint(qa[1]), __float_as_uint(qa[2]) }, rs, (int)oa, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(qb[0]), __float_as_uint(qb[1]), __float_as_uint(qb[2]) }, rs, (int)ob, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(rga.x), __float_as_uint(rga.y), __float_as_uint(bxa.x) }, rs, (int)oa, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b96((eu5_u3){ __float_as_uint(rgb.x), __float_as_uint(rgb.y), __float_as_uint(bxb.x) }, rs, (int)ob, 0, 0);
     } else {
-      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(qa[0]), __float_as_uint(qa[1]), __float_as_uint(qa[2]), __float_as_uint(qa[3]) }, rs, (int)oa, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(qb[0]), __float_as_uint(qb[1]), __float_as_uint(qb[2]), __float_as_uint(qb[3]) }, rs, (int)ob, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(rga.x), __float_as_uint(rga.y), __float_as_uint(bxa.x), __float_as_uint(bxa.y) }, rs, (int)oa, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128((eu5_u4){ __float_as_uint(rgb.x), __float_as_uint(rgb.y), __float_as_uint(bxb.x), __float_as_uint(bxb.y) }, rs, (int)ob, 0, 0);
     }
-  }
-  EU5_STAMP(7);
+  };
+#pragma unroll 1
+  for (int k = 0;; k++) {
+    // everything a member derives from the lane index is recomputed per member
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
 #ifdef EU5_STAMPS
-  if (lane == 0 && w.stamps) {
-    unsigned long long *o = w.stamps + ((size_t)tile_y * w.tiles16 + x0 / EU4_TW) * 8;
-    st_[1] = (unsigned long long)(npass + 1);
-#pragma unroll
-    for (int k = 0; k < 8; k++) o[k] = st_[k];
-  }
+    if (k > 0) { EU5_STAMP(0); st_[4] = 0; st_[5] = 0; }
 #endif
+    const bool last = k + 1 >= n;
+    // the next member's entry (scalar cache), requested a member ahead
+    int mk_n = 0, sk_n = 0;
+    if (!last) { mk_n = ent[2 * k + 4]; sk_n = ent[2 * k + 5]; }
+    eu5_i4 Rk_n = { 0, 0, -1, 0 };
+    const bool flip = (mk & EU_POLAR_FLIP) != 0, mir = (mk & EU_POLAR_MIRROR) != 0;
+    srow = mk & (EU_POLAR_FLIP - 1);
+    const int tc = mir ? w.tiles16 - 1 - tcol : tcol;
+    const eu5_crec rec = bt + (sk * w.tiles16 + tc) * EU5_BT_RECS;
+    // ... and its record 0, once its entry has arrived: under this member's staging
+    auto next_record = [&]() {
+      if (!last) {
+        const int tc_n = (mk_n & EU_POLAR_MIRROR) ? w.tiles16 - 1 - tcol : tcol;
+        Rk_n = bt[(sk_n * w.tiles16 + tc_n) * EU5_BT_RECS];
+      }
+    };
+    const int pr = lane & 3, rw = (lane >> 2) & 7, hf = lane >> 5;
+    // the lane's pixels in this member: frame row rwm of the tile row, columns xa and xb
+    const int rwm = flip ? 7 - rw : rw;
+    const int xl = tcol * EU4_TW + 8 * hf + 2 * pr;
+    const int xa = mir ? p.width - 1 - xl : xl, xb = mir ? xa - 1 : xa + 1;
+    const bool yin = p.row_begin + srow * EU4_TH + rwm < p.row_end;
+    const bool va = yin && xa < p.width, vb = yin && xb < p.width;
+    rga = (eu_f2){ 0.0f, 0.0f }; bxa = (eu_f2){ 0.0f, 0.0f }; rgb = (eu_f2){ 0.0f, 0.0f }; bxb = (eu_f2){ 0.0f, 0.0f };
+    oa = 0xfffff000u; ob = 0xfffff000u;
+    const int cls = Rk.w;
+    if (cls & EU5_BT_WORK) {
+      if (lane == 0) {
+        const int id = srow * w.tiles16 + tc;
+        const int sh = eu4_shard_of(id);
+        const int slot = atomicAdd(p.wl + EU4_WL_SHARD(sh), 1);
+        p.wl[EU4_WL_ENTRIES + (size_t)slot * EU4_SHARDS + sh] = id;
+      }
+      next_record();
+    } else {
+      const int npass = cls & 7;
+      eu5_box bx = { Rk.x, Rk.y, Rk.x + (Rk.z & 0xffff), Rk.y + (Rk.z >> 16) };
+      bool some = npass > 0 && Rk.z >= 0;
+      if (some && k > 0) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);     // (the leader's: ahead of the angles)
+      next_record();
+      if (npass > 0) {
+        // the member's angles: the leader's with the member's sign bits (an odd function's sign, not a product)
+        const unsigned sgx = mir ? 0x80000000u : 0u, sgy = flip ? 0x80000000u : 0u;
+        const eu_f2 lon = { __uint_as_float(__float_as_uint(A.lon.x) ^ sgx), __uint_as_float(__float_as_uint(A.lon.y) ^ sgx) };
+        const eu_f2 lat = { __uint_as_float(__float_as_uint(A.lat.x) ^ sgy), __uint_as_float(__float_as_uint(A.lat.y) ^ sgy) };
+        eu5_co8 c;
+        eu5_spline_xy<DEG>(s, lon, lat, c);
+        eu5_split_y<DEG>(c);
+#ifdef EU5_STAMPS
+        asm volatile("" : : "v"(c.iya), "v"(c.iyb), "v"(c.ixa), "v"(c.ixb));
+#endif
+        EU5_STAMP(2);
+#ifdef EU5_STAMPS
+        st_[3] = st_[2];
+#endif
+        eu_f2 wx[order], wy[order];
+        if constexpr (DEG >= 2) {
+          eu_weights2<DEG>(s.wm, c.ty, wy);
+          eu_weights2<DEG>(s.wm, c.tx, wx);
+        }
+        // the half / quarter of the MEMBER's tile the lane's pixels lie in (its records are in its own lane order)
+        const int hfm = mir ? 1 - hf : hf;
+        const int grp = npass == 1 ? 0 : npass == 2 ? hfm : 2 * hfm + (rwm >> 2);
+#pragma unroll 1
+        for (int pi = 0; pi < npass; pi++) {
+          // the next pass's record, requested under this pass
+          eu5_i4 Rn = { 0, 0, -1, 0 };
+          if (pi + 1 < npass) Rn = rec[pi + 1];
+          if (some) {
+            if (pi > 0) eu5_stage<NCH, DEG>(s, bx, lds_tile, lane);
+            const int ibw = bx.mxx - bx.mnx + order;
+            // lanes of other groups and lanes without a hit read the box origin
+            const bool mine = grp == pi;
+            const int fa = (mine && va) ? ((c.iya - bx.mny) * ibw + (c.ixa - bx.mnx)) * 4 : 0;
+            const int fb = (mine && vb) ? ((c.iyb - bx.mny) * ibw + (c.ixb - bx.mnx)) * 4 : 0;
+            if (pi == 0) EU5_STAMP(4);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (pi == 0) EU5_STAMP(5);
+            if (mine) eu5_taps<NCH, DEG>((eu_lptr)wtile, fa, fb, ibw * 4, wx, wy, c.tx, c.ty, rga, bxa, rgb, bxb);
+          }
+          bx = (eu5_box){ Rn.x, Rn.y, Rn.x + (Rn.z & 0xffff), Rn.y + (Rn.z >> 16) };
+          some = Rn.z >= 0;
+        }
+      }
+      // zero on a miss (FAST: every ray hits, a miss is a pixel outside the frame, which is not stored)
+      const unsigned orow = (unsigned)rwm * (unsigned)p.out_stride;
+      if (va) oa = (orow + (unsigned)(xa * NCH)) * 4u;
+      if (vb) ob = (orow + (unsigned)(xb * NCH)) * 4u;
+    }
+#ifdef EU5_STAMPS
+    asm volatile("" : : "v"(rga), "v"(bxa), "v"(rgb), "v"(bxb));
+    EU5_STAMP(6);
+    if (lane == 0 && w.stamps && !(cls & EU5_BT_WORK)) {
+      // class: the pass count + 1, a follower's (no angles of its own) with bit 4 - 'hoist 1' in the report
+      unsigned long long *o = w.stamps + ((size_t)srow * w.tiles16 + tc) * 8;
+      st_[1] = (unsigned long long)((cls & 7) + 1) | (k > 0 ? 16ull : 0ull);
+      st_[7] = __builtin_amdgcn_s_memtime();
+#pragma unroll
+      for (int q = 0; q < 8; q++) o[q] = st_[q];
+    }
+#endif
+    if (last) break;
+    put();
+    mk = mk_n; sk = sk_n; Rk = Rk_n;
+  }
+  {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    if (have_n) eu5_load8<true>(p, ty_n, x0_n, lane, T);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  put();
 }
+
 
 // A 16x16 tile on tile rows with a column plan (FAST profile, lat/lon source): FOUR pixels per lane - the
 // pairs (xa, xb) of rows y and y + 8. The two pairs share everything that depends on the column (the table
@@ -864,8 +953,6 @@ __device__ __forceinline__ void eu5_load16(const eu_render_params &p, const floa
   T.A1A = rtA[1]; T.B1A = rtA[4]; T.A1B = rtB[1]; T.B1B = rtB[4];
   T.c0 = (eu_f2){ p.col[xac], p.col[xbc] };
 }
-
-typedef const __attribute__((address_space(4))) int *eu5_cint;   // read through the scalar cache
 
 // the column entries of the lane's two columns only: all a follower of a group reads from the tables
 __device__ __forceinline__ void eu5_load_cols(const float *ct, int xa, int xb, eu5_tab16 &T)
@@ -1219,8 +1306,6 @@ __global__ __launch_bounds__(64 * EU5_WAVES, EU5_OCC) void eu_render5_kernel(con
     // waiting for the waves that had drawn the poles. Each tile requests the next one's table values ahead of its
     // stores, as in the first loop.
     int *const queue = p.wl + EU4_WL_DYN(xcd);
-    const int nbatch = (w.l2_off[xcd + 1] - w.l2_off[xcd]) * w.l2_half;
-    const eu5_cint rows2 = (eu5_cint)w.l2_rows + w.l2_off[xcd];
     auto take = [&]() -> int {                      // the queue's next batch (lane 0's value counts)
       int v = 0;
       if (lane0 == 0) v = atomicAdd(queue, 1);
@@ -1228,46 +1313,55 @@ __global__ __launch_bounds__(64 * EU5_WAVES, EU5_OCC) void eu_render5_kernel(con
     };
     if constexpr (BOXTAB) {
       static_assert(FAST && PRJ == EU_SPHERICAL, "the box table is that of the FAST lat/lon second loop");
-      // as below, with every tile's record 0 requested through the scalar cache as soon as its id is known: a tile ahead
+      // With the table the loop walks POSITIONS: batch j of the XCD's queue is l2p_bcols neighbouring tile columns of
+      // entry j / l2p_bpe of the XCD's list (w.l2p_ent: eu_polar_groups.h), and a position renders every member of its
+      // entry (eu5_tile_bt). Where every entry has a follower a batch is one column - two tiles or more - else two,
+      // as below. The leader's record 0 is requested through the scalar cache as soon as its position is known: a
+      // position ahead, and the dequeue is taken a position ahead of its use. (NOT in flight across the position, though
+      // the source reads so: the compiler's atomic optimiser expands take() into mbcnt / bcnt / global_atomic_add and
+      // reads the result back at once, behind an s_waitcnt vmcnt(0) - at the head of every position that dequeues, a
+      // wait for the previous position's two stores and table-value loads as well. The parent's take() compiles to the
+      // same shape; taking the result without that epilogue is the next thing to try here.)
       const eu5_crec bt = (eu5_crec)w.boxtab;
-      auto decode = [&](int j, int &ty, int &tcol, int &ti) -> bool {
-        if (j >= nbatch) return false;
-        const int r = (int)(((unsigned long long)(unsigned)j * w.l2_magic) >> 40);      // j / l2_half
-        ty = rows2[r]; tcol = 2 * (j - r * w.l2_half);
-        ti = ((w.l2_off[xcd] + r) * w.tiles16 + tcol) * EU5_BT_RECS;
+      const eu5_cint ents = (eu5_cint)w.l2p_ent + EU_POLAR_ENTRY_INTS * w.l2p_off[xcd];
+      const int npos = (w.l2p_off[xcd + 1] - w.l2p_off[xcd]) * w.l2p_bpe;
+      auto decode = [&](int j, eu5_cint &e, int &n, int &m, int &sl, int &tcol, int &lim) -> bool {
+        if (j >= npos) return false;
+        const int r = (int)(((unsigned long long)(unsigned)j * w.l2p_magic) >> 40);     // j / l2p_bpe
+        e = ents + EU_POLAR_ENTRY_INTS * r;
+        n = e[0]; m = e[2] & (EU_POLAR_FLIP - 1); sl = e[3];
+        tcol = e[1] + (j - r * w.l2p_bpe) * w.l2p_bcols;
+        lim = e[1] + w.l2p_ecols;
         return true;
       };
-      int ty_a = 0, col_a = 0, ti_a = 0, ty_n = 0, col_n = 0, ti_n = 0;
-      bool have = decode(__builtin_amdgcn_readfirstlane(take()), ty_a, col_a, ti_a);
-      eu5_tab8 Ta, Tb;
-      eu5_i4 Ra = { 0, 0, -1, 0 }, Rb = { 0, 0, -1, 0 };
-      if (have) { Ra = bt[ti_a]; eu5_load8<FAST>(p, ty_a, col_a * EU4_TW, lane0, Ta); }
+      eu5_cint e_a = ents, e_n = ents;
+      int n_a = 0, m_a = 0, sl_a = 0, col_a = 0, lim_a = 0, n_n = 0, m_n = 0, sl_n = 0, col_n = 0, lim_n = 0;
+      bool have = decode(__builtin_amdgcn_readfirstlane(take()), e_a, n_a, m_a, sl_a, col_a, lim_a);
+      int jn_lane = take();
+      bool second = have && w.l2p_bcols == 2 && col_a + 1 < lim_a;     // the batch's other column comes next
+      eu5_tab8 Ta;
+      eu5_i4 Ra = { 0, 0, -1, 0 };
+      if (have) { Ra = bt[(sl_a * w.tiles16 + col_a) * EU5_BT_RECS]; eu5_load8<FAST>(p, m_a, col_a * EU4_TW, lane0, Ta); }
       __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);       // (see eu5_tile_bt's stores)
 #pragma unroll 1
       while (have) {
-        const int jn_lane = take();                   // in flight across the first tile of this batch
-        const bool second = col_a + 1 < w.tiles16;    // (an odd number of tiles per row: the last batch is one tile)
-        if (second) Rb = bt[ti_a + EU5_BT_RECS];
-        {
-          int lane = lane0;
-          asm volatile("" : "+v"(lane));
-          eu5_tile_bt<NCH, DEG>(p, w, atab, tile, ty_a, col_a * EU4_TW, lane, Ta, Ra, bt + ti_a, second, ty_a,
-                                (col_a + 1) * EU4_TW, Tb);
-        }
-        const bool have_n = decode(__builtin_amdgcn_readfirstlane(jn_lane), ty_n, col_n, ti_n);
-        if (have_n) Ra = bt[ti_n];
+        bool have_n = true;
         if (second) {
-          int lane = lane0;
-          asm volatile("" : "+v"(lane));
-          eu5_tile_bt<NCH, DEG>(p, w, atab, tile, ty_a, (col_a + 1) * EU4_TW, lane, Tb, Rb, bt + ti_a + EU5_BT_RECS, have_n,
-                                ty_n, col_n * EU4_TW, Ta);
-        } else if (have_n) {
-          eu5_load8<FAST>(p, ty_n, col_n * EU4_TW, lane0, Ta);
-          __builtin_amdgcn_s_waitcnt(EU5_WAIT_VM0);
+          e_n = e_a; n_n = n_a; m_n = m_a; sl_n = sl_a; col_n = col_a + 1; lim_n = lim_a;
+          second = false;
+        } else {
+          have_n = decode(__builtin_amdgcn_readfirstlane(jn_lane), e_n, n_n, m_n, sl_n, col_n, lim_n);
+          jn_lane = take();
+          second = have_n && w.l2p_bcols == 2 && col_n + 1 < lim_n;
         }
-        ty_a = ty_n; col_a = col_n; ti_a = ti_n; have = have_n;
+        eu5_i4 Rn = { 0, 0, -1, 0 };
+        if (have_n) Rn = bt[(sl_n * w.tiles16 + col_n) * EU5_BT_RECS];
+        eu5_tile_bt<NCH, DEG>(p, w, atab, tile, lane0, Ta, Ra, e_a, n_a, m_a, sl_a, col_a, have_n, m_n, col_n * EU4_TW);
+        e_a = e_n; n_a = n_n; m_a = m_n; sl_a = sl_n; col_a = col_n; lim_a = lim_n; Ra = Rn; have = have_n;
       }
     } else {
+      const int nbatch = (w.l2_off[xcd + 1] - w.l2_off[xcd]) * w.l2_half;
+      const eu5_cint rows2 = (eu5_cint)w.l2_rows + w.l2_off[xcd];
       auto decode = [&](int j, int &ty, int &tcol) -> bool {
         if (j >= nbatch) return false;
         const int r = (int)(((unsigned long long)(unsigned)j * w.l2_magic) >> 40);      // j / l2_half

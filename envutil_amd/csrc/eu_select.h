@@ -32,6 +32,8 @@ struct eu_switches {
   int rej;             // EU_HIP_REJ: 1 the early-miss tables of a multi-facet job, 2 their table-free form; else 0
   int colplan;         // EU_HIP_COLPLAN=0: no column plans (0); else 1
   int share;           // EU_HIP_SHARE: EU_SHARE_* bits - 0: none, m: mirrors, f: faces; else both
+  int polar_share;     // EU_HIP_POLAR_SHARE: EU_POLAR_* bits, the second loop's groups (with the box table) - 0: none, t: twins,
+                       // m: mirrors; else both
   int direct;          // EU_HIP_DIRECT=1: the general kernel never stages through LDS
   int iir_stream;      // EU_HIP_IIR_STREAM: bit 0 rows, bit 1 columns, bit 2 checkpoints; unset: 7
   int boxtab;          // EU_HIP_BOXTAB=0: the persistent staged kernel's second loop reduces its tile boxes per frame (0); else 1:
@@ -67,6 +69,8 @@ inline eu_switches eu_read_switches()
   s.colplan = first("EU_HIP_COLPLAN") != '0';
   const char sh = first("EU_HIP_SHARE");
   s.share = sh == '0' ? 0 : sh == 'm' ? EU_SHARE_MIRRORS : sh == 'f' ? EU_SHARE_FACES : EU_SHARE_FACES | EU_SHARE_MIRRORS;
+  const char ps = first("EU_HIP_POLAR_SHARE");
+  s.polar_share = ps == '0' ? 0 : ps == 't' ? EU_POLAR_TWINS : ps == 'm' ? EU_POLAR_MIRRORS : EU_POLAR_TWINS | EU_POLAR_MIRRORS;
   s.direct = first("EU_HIP_DIRECT") == '1';
   const char *iir = getenv("EU_HIP_IIR_STREAM");
   s.iir_stream = iir ? atoi(iir) : 7;

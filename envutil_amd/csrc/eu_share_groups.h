@@ -21,6 +21,9 @@
 #define EU_SHARE_MIRROR (1 << 30)
 #define EU_SHARE_FACES 1        // mode bits: double rows of other faces may follow a leader
 #define EU_SHARE_MIRRORS 2      //            a double row mirrored column for column may
+// ... and those of the second loop's groups (eu_polar_groups.h), here for eu_select.h's sake
+#define EU_POLAR_TWINS 1        //            a tile row of the opposite polar face may follow a leader
+#define EU_POLAR_MIRRORS 2      //            a tile row mirrored column for column may
 
 struct eu_share_input {
   int width, tiles16;           // frame width, 16-pixel tile columns

@@ -168,6 +168,11 @@ unsigned long long eu_hip_launch_count(void);
  * the tables the kernel reads do not agree bit for bit, and under EU_HIP_SHARE=0 */
 unsigned long long eu_hip_share_follower_tiles(void);
 
+/* 16x8 tiles that the last staged launch (eu_render5_kernel's second loop, where it reads the box table)
+ * rendered from the angles of another tile - the twin on the opposite polar face, the column mirror; 0
+ * where the tables the kernel reads do not agree bit for bit, and under EU_HIP_POLAR_SHARE=0 */
+unsigned long long eu_hip_polar_follower_tiles(void);
+
 /* 16x8 wave tiles that the last staged launch pair of this process handed to its second kernel, the
  * direct-gather kernel, through the work list (tiles whose texel box does not fit a wave's LDS slice, tiles
  * with a lane on a scalar fallback of the coordinate arithmetic); waits for that pair. 0 before the first
