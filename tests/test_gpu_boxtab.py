@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import devout
 import envutil_amd as ea
 import euo
 import jobs
@@ -59,15 +60,21 @@ def table():
     return int(used()), int(tiles())
 
 
-def three_ways(a, o, g, nch=None, r0=0, r1=None, ref=None, what=""):
-    """the frame with the table, the frame without, the oracle's: one frame. Returns the table's tiles."""
+def three_ways(a, o, g, nch=None, r0=0, r1=None, ref=None, what="", host=False):
+    """the frame with the table, the frame without, the oracle's: one frame. Returns the table's tiles. Either variant
+    is rendered into a guarded device buffer that is all fill word before the call (tests/devout.py): a tile a variant
+    skips is not found rendered by the variant before it. host=True: through envutil_amd.render() into host memory"""
+    def render(which):
+        if host:
+            return ea.render(a, g, nch, r0, r1)
+        return devout.rendered(f"{what}: {which}", a, g, nch, r0, r1)
     if ref is None:
         ref = jobs.oracle_render(a, o, row_begin=r0, row_end=r1)
     os.environ.pop("EU_HIP_BOXTAB", None)
-    on = ea.render(a, g, nch, r0, r1)
+    on = render("table")
     used, tiles = table()
     os.environ["EU_HIP_BOXTAB"] = "0"
-    off = ea.render(a, g, nch, r0, r1)
+    off = render("EU_HIP_BOXTAB=0")
     used_off, _ = table()
     os.environ.pop("EU_HIP_BOXTAB", None)
     print(f"{what}: table used {used}, {tiles} tiles; EU_HIP_BOXTAB=0: used {used_off}")
@@ -103,7 +110,8 @@ def test_cube_face_512(pairs):
     o, g = pairs(3, 3)
     a = ea.arguments(ea.CUBEMAP, 512, 3072, 90.0, spline_degree=3)
     ref = jobs.oracle_render(a, o)
-    three_ways(a, o, g, 3, ref=ref, what="face 512, the frame")
+    three_ways(a, o, g, 3, ref=ref, what="face 512, the frame", host=True)
+    three_ways(a, o, g, 3, ref=ref, what="face 512, the frame as one launch into device memory")
     tiles = three_ways(a, o, g, 3, 1024, 2040, ref=ref[1024:2040], what="face 512, rows 1024-2040")
     assert tiles == 127 * 32
 

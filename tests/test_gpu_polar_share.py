@@ -11,6 +11,7 @@ import subprocess
 
 import pytest
 
+import devout
 import envutil_amd as ea
 import euo
 import jobs
@@ -69,19 +70,25 @@ def host_says(demo, face, yaw, r0, r1, mode):
     return int(out.split()[1])
 
 
-def three_ways(demo, a, o, g, nch, face, yaw=0, r0=0, r1=None, ref=None, mode=None, what="", count=True):
-    """the frame with the groups, the frame without, the oracle's: one frame. Returns the follower tiles.
+def three_ways(demo, a, o, g, nch, face, yaw=0, r0=0, r1=None, ref=None, mode=None, what="", count=True, host=False):
+    """the frame with the groups, the frame without, the oracle's: one frame. Returns the follower tiles. Either variant
+    is rendered into a guarded device buffer that is all fill word before the call (tests/devout.py): a tile a variant
+    skips is not found rendered by the variant before it. host=True: through envutil_amd.render() into host memory;
     count=False: the frame takes several launches, and the query names the last one's list"""
+    def render(which):
+        if host:
+            return ea.render(a, g, nch, r0, r1)
+        return devout.rendered(f"{what}: {which}", a, g, nch, r0, r1)
     if ref is None:
         ref = jobs.oracle_render(a, o, row_begin=r0, row_end=r1)
     if mode is None:
         os.environ.pop("EU_HIP_POLAR_SHARE", None)
     else:
         os.environ["EU_HIP_POLAR_SHARE"] = mode
-    on = ea.render(a, g, nch, r0, r1)
+    on = render("groups")
     n_on = followers()
     os.environ["EU_HIP_POLAR_SHARE"] = "0"
-    off = ea.render(a, g, nch, r0, r1)
+    off = render("EU_HIP_POLAR_SHARE=0")
     n_off = followers()
     os.environ.pop("EU_HIP_POLAR_SHARE", None)
     want = host_says(demo, face, yaw, r0, 6 * face if r1 is None else r1, mode or "b")
@@ -114,7 +121,8 @@ def test_cube_face_512(demo, pairs):
     o, g = pairs(3, 3)
     a = ea.arguments(ea.CUBEMAP, 512, 3072, 90.0, spline_degree=3)
     ref = jobs.oracle_render(a, o)
-    three_ways(demo, a, o, g, 3, 512, ref=ref, r1=3072, what="face 512, the frame", count=False)
+    three_ways(demo, a, o, g, 3, 512, ref=ref, r1=3072, what="face 512, the frame", count=False, host=True)
+    three_ways(demo, a, o, g, 3, 512, ref=ref, r1=3072, what="face 512, the frame as one launch into device memory")
     n = three_ways(demo, a, o, g, 3, 512, r0=1032, r1=2040, ref=ref[1032:2040], what="face 512, rows 1032-2040")
     assert n == 3 * 63 * 16
 
