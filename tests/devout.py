@@ -11,6 +11,16 @@ signalling NaN no arithmetic yields and no finite image holds (bytes of 0xA5 for
     render_dev  one job into a fresh Guarded: (frame, outside_ok, n_touched)
     held        a case's three assertions: (a) the frame is the oracle's bit for bit, (b) no word of it is still
                 the fill word, (c) nothing outside the rows was touched
+
+The entries that write several frames in one call (eu_hip_render_views, eu_hip_render_views_multi,
+eu_hip_render_layers) and eu_hip_render_rays have an outer stride of their own:
+
+    GuardedFrames   GUARD + lead words | n frames, each rows of (row words + pad) and then gap words | GUARD words
+    views_into, layers_into, rays_into   one call through the C ABI, out_on_device = 1, into a GuardedFrames
+    held_frames     (a), (b), (c) for every frame of the buffer; untouched: the whole buffer is still fill
+
+Both buffers take device="cpu": the index arithmetic of outside() and frames() is then tested without a GPU
+(tests/test_devout_host.py).
 """
 import ctypes as C
 
@@ -40,6 +50,9 @@ class Outside:
     def __str__(self):
         if not self.count:
             return "nothing outside the rows was touched"
+        if len(self.first) == 3:
+            return f"{self.count} words outside the frames' rows were written, the first at (frame {self.first[0]}, " \
+                   f"row {self.first[1]}, column {self.first[2]})"
         return f"{self.count} words (bytes of a byte buffer) outside the rows were written, the first at (row {self.first[0]}, column {self.first[1]}) of the frame"
 
 
@@ -48,7 +61,7 @@ class Guarded:
     32-bit words (an int32 tensor: the fill word is positive there, and torch compares int32 on every build);
     words=False: bytes, `unit` of them per unit"""
 
-    def __init__(self, rows, row_units, pad=0, lead=0, words=True, unit=None, guard=GUARD):
+    def __init__(self, rows, row_units, pad=0, lead=0, words=True, unit=None, guard=GUARD, device="cuda"):
         import torch
         self.words = words
         self.unit = 4 if words else (unit or 1)          # bytes per unit
@@ -57,8 +70,9 @@ class Guarded:
         self.rows, self.row_len, self.stride = rows, row_units * per, (row_units + pad) * per
         self.start = (guard * (1 if words else 4)) + lead * per
         self.total = self.start + rows * self.stride + guard * (1 if words else 4)
-        self.buf = torch.full((self.total,), self.fill, dtype=torch.int32 if words else torch.uint8, device="cuda")
-        torch.cuda.synchronize()                         # the fill ran on torch's stream, the job runs on another
+        self.buf = torch.full((self.total,), self.fill, dtype=torch.int32 if words else torch.uint8, device=device)
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize()                     # the fill ran on torch's stream, the job runs on another
 
     @property
     def stride_bytes(self):
@@ -98,6 +112,76 @@ class Guarded:
             if first is not None:
                 break
         return Outside(n, first)
+
+
+class GuardedFrames:
+    """`n` frames between two guards, all fill, 32-bit words (an int32 tensor, as Guarded's): a frame is `rows` rows of
+    `row_units` words (+ `pad`) followed by `gap` words, so the frame stride is rows * (row_units + pad) + gap - with
+    a gap that is no multiple of the row stride the frames' rows do not lie on one grid. The first frame starts `lead`
+    words behind the front guard.
+
+    A word outside the rows is named (frame, row, column) by the frame whose first word precedes it - frame 0 for
+    the front guard and the lead, which get negative rows: row and column count in row strides from that frame's first
+    word, so a padding word has a column >= row_units and a gap or back-guard word a row >= rows."""
+
+    def __init__(self, n, rows, row_units, pad=0, lead=0, gap=0, guard=GUARD, device="cuda"):
+        import torch
+        assert n >= 1 and rows >= 1 and row_units >= 1 and min(pad, lead, gap, guard) >= 0
+        self.n, self.rows, self.row_len, self.stride, self.gap = n, rows, row_units, row_units + pad, gap
+        self.fill = FILL
+        self.frame_stride = rows * self.stride + gap
+        self.start = guard + lead
+        self.end = self.start + n * self.frame_stride
+        self.total = self.end + guard
+        self.buf = torch.full((self.total,), FILL, dtype=torch.int32, device=device)
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize()                     # the fill ran on torch's stream, the call runs on another
+
+    @property
+    def stride_bytes(self):
+        return self.stride * 4
+
+    @property
+    def frame_stride_bytes(self):
+        return self.frame_stride * 4
+
+    def ptr(self, frame=0, row=0):
+        return self.buf.data_ptr() + (self.start + frame * self.frame_stride + row * self.stride) * 4
+
+    def _parts(self):
+        """views of the buffer: front guard + lead, back guard, the rows (n, rows, stride), the gaps (n, gap)"""
+        body = self.buf[self.start:self.end].view(self.n, self.frame_stride)
+        rows = body[:, :self.rows * self.stride].unflatten(1, (self.rows, self.stride))
+        return self.buf[:self.start], self.buf[self.end:], rows, body[:, self.rows * self.stride:]
+
+    def frames(self):
+        """the rows without their padding, on the host: uint32 words, (n, rows, row_units)"""
+        return self._parts()[2][:, :, :self.row_len].contiguous().cpu().numpy().view(np.uint32)
+
+    def where(self, index):
+        """(frame, row, column) of the buffer's word `index`, as the class comment names them"""
+        j = index - self.start
+        f = min(max(j // self.frame_stride, 0), self.n - 1)
+        return (f,) + divmod(j - f * self.frame_stride, self.stride)
+
+    def outside(self):
+        """counted on the device; the position of the first touched word is looked up only when there is one"""
+        head, tail, rows, gaps = self._parts()
+        padding = rows[:, :, self.row_len:]
+        parts = [p for p in (head, tail, padding, gaps) if p.numel()]
+        n = int(sum((p != self.fill).sum() for p in parts))
+        if not n:
+            return Outside(0)
+        found = []
+        for p, index in ((head, lambda h: int(h[0])),
+                         (tail, lambda h: self.end + int(h[0])),
+                         (padding, lambda h: self.start + int(h[0]) * self.frame_stride + int(h[1]) * self.stride + self.row_len + int(h[2])),
+                         (gaps, lambda h: self.start + int(h[0]) * self.frame_stride + self.rows * self.stride + int(h[1]))):
+            if p.numel():
+                hit = (p != self.fill).nonzero()            # in the order of the addresses
+                if hit.numel():
+                    found.append(index(hit[0]))
+        return Outside(n, self.where(min(found)))
 
 
 def out_channels(args, nch, stage=0):
@@ -214,3 +298,83 @@ def rendered(what, args, sources, nch=None, row_begin=0, row_end=None, **kw):
                            f"{_at(np.argwhere(got == FILL)[0])}"
     assert outside, f"{what}: {outside}"
     return frame
+
+
+# ---- several frames in one call: eu_hip_render_views(_multi), eu_hip_render_layers, and eu_hip_render_rays --------
+def _stream(stream):
+    return C.c_void_p(stream) if stream else None
+
+
+def views_into(buf, args, views, sources, nch, stream=None, first=0):
+    """eu_hip_render_views (a Source) or eu_hip_render_views_multi (a list of them), out_on_device = 1, into `buf` from
+    its frame `first` on, with buf's row and frame strides; asynchronous"""
+    t = args.target(nch)
+    arr = api._views_struct(args, views)
+    where = (C.c_void_p(buf.ptr(first)), buf.stride_bytes, buf.frame_stride_bytes, 1, _stream(stream))
+    L = ea.lib()
+    if isinstance(sources, (list, tuple)):
+        handles = (C.c_void_p * len(sources))(*[s.handle for s in sources])
+        rc = L.eu_hip_render_views_multi(C.byref(t), arr, len(views), handles, len(sources), *where)
+    else:
+        rc = L.eu_hip_render_views(C.byref(t), arr, len(views), sources.handle, *where)
+    assert rc == 0, L.eu_hip_last_error().decode()
+
+
+def layers_into(buf, args, layers, nch, stream=None, first=0):
+    """eu_hip_render_layers, out_on_device = 1, into `buf` from its frame `first` on; asynchronous"""
+    t = args.target(nch)
+    handles = (C.c_void_p * max(len(layers), 1))(*[s.handle for s in layers])
+    L = ea.lib()
+    rc = L.eu_hip_render_layers(C.byref(t), handles, len(layers), C.c_void_p(buf.ptr(first)), buf.stride_bytes,
+                                buf.frame_stride_bytes, 1, _stream(stream))
+    assert rc == 0, L.eu_hip_last_error().decode()
+
+
+def rays_into(buf, source, rays, nch=None, taps=None, stream=None):
+    """eu_hip_render_rays, out_on_device = 1, into frame 0 of `buf`: `rays` as envutil_amd.render_rays takes them
+    (numpy: the staged route; a torch tensor on the device, its rows padded or not: asynchronous). Returns what the
+    call points into, for the caller to keep until sync()"""
+    r, _, keep = api._rays_struct(source, rays, nch, taps)
+    assert (r.height, r.width * r.nchannels) == (buf.rows, buf.row_len), (r.height, r.width, r.nchannels)
+    L = ea.lib()
+    rc = L.eu_hip_render_rays(C.byref(r), source.handle, C.c_void_p(buf.ptr()), buf.stride_bytes, 1, _stream(stream))
+    assert rc == 0, L.eu_hip_last_error().decode()
+    return keep
+
+
+def check_frames(what, got, outside, refs):
+    """(a), (b), (c) on frames already rendered: `got` is GuardedFrames.frames(), `refs` the oracle's frame of every
+    one of them (float32; its shape may split the row's words into pixels and channels). Prints the case's line"""
+    n, rows, row_len = got.shape
+    want = [words_of(np.asarray(r)).reshape(-1, row_len) for r in refs]
+    unwritten = int((got == FILL).sum())
+    print(f"{what}: touched outside {outside.count}, frame words still fill {unwritten}")
+    assert len(want) == n and all(w.shape == (rows, row_len) for w in want), (what, got.shape, [w.shape for w in want])
+    for k in range(n):
+        miss = np.argwhere(got[k] == FILL)
+        assert not miss.size, f"{what}: {len(miss)} of {got[k].size} words of frame {k} were never written, the first at " \
+                              f"(frame {k}, row {int(miss[0][0])}, word {int(miss[0][1])})"
+    for k in range(n):
+        bad = np.argwhere(got[k] != want[k])
+        if bad.size:
+            y, x = (int(v) for v in bad[0])
+            raise AssertionError(f"{what}: {len(bad)} of {got[k].size} words of frame {k} differ from the oracle, the first "
+                                 f"at (frame {k}, row {y}, word {x}): {got[k].view(np.float32)[y, x]!r} oracle "
+                                 f"{want[k].view(np.float32)[y, x]!r}")
+    assert outside, f"{what}: {outside}"
+
+
+def held_frames(what, buf, refs):
+    """a case's three assertions on a GuardedFrames a call has written (the caller has synchronised): (a) every frame
+    is the oracle's bit for bit, (b) no word of a frame is still the fill word, (c) no word of the guards, the lead,
+    the rows' padding or the gaps was touched"""
+    check_frames(what, buf.frames(), buf.outside(), refs)
+
+
+def untouched(what, buf):
+    """a call that has nothing to write: frames and everything around them still hold the fill"""
+    outside = buf.outside()
+    written = int((buf.frames() != FILL).sum())
+    print(f"{what}: touched outside {outside.count}, frame words written {written}")
+    assert outside, f"{what}: {outside}"
+    assert written == 0, f"{what}: {written} words of the frames were written"
