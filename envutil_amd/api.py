@@ -139,6 +139,9 @@ def lib():
     L.eu_hip_source_load_edited.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_source_load_samples.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_source_load_rgbe.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_source_load_ycbcr.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.eu_hip_ycbcr_floats.argtypes = [vp, i32, i32, i32, vp]
+    L.eu_hip_source_reload.argtypes = [vp, vp, i32, vp]
     L.eu_hip_facet_alpha_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.eu_hip_facet_alpha_rows.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32]
     L.eu_hip_source_adopt.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -264,17 +267,188 @@ class Rgbe(C.Structure):
     _fields_ = [("data", C.c_void_p), ("on_device", C.c_int32), ("colour_table", C.c_void_p)]
 
 
+class Ycbcr(C.Structure):
+    """struct eu_ycbcr"""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p),
+                ("y_pitch", C.c_size_t), ("c_pitch", C.c_size_t),
+                ("c_step", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32),
+                ("bits", C.c_int32), ("on_device", C.c_int32),
+                ("y_table", C.c_void_p), ("c_table", C.c_void_p),
+                ("m_rv", C.c_float), ("m_gu", C.c_float), ("m_gv", C.c_float), ("m_bu", C.c_float)]
+
+
+PX_FLOATS, PX_SAMPLES, PX_RGBE, PX_YCBCR = 0, 1, 2, 3
+
+
+class Pixels(C.Structure):
+    """struct eu_pixels"""
+    _fields_ = [("kind", C.c_int32), ("floats", C.c_void_p), ("pixel_channels", C.c_int32),
+                ("on_device", C.c_int32), ("samples", C.c_void_p), ("rgbe", C.c_void_p),
+                ("ycbcr", C.c_void_p), ("edit", C.c_void_p)]
+
+
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
 
 
-def _torch_ptr(t):
+def _settle(t, wait=True):
+    """the work queued on a device tensor's current stream is done (wait=False: the caller orders it)"""
+    if wait:
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()
+
+
+def _torch_ptr(t, wait=True):
     """address of a float32 tensor on the library's device, once the work queued on it is done"""
     import torch
     if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
         raise EuError("a torch tensor handed over as pixels is float32, contiguous and on the device")
-    torch.cuda.current_stream(t.device).synchronize()
+    _settle(t, wait)
     return t.data_ptr()
+
+
+def _stream_handle(stream):
+    """a hipStream_t for the C ABI: None (the library's stream), a torch stream or a raw handle"""
+    if stream is None:
+        return None
+    h = getattr(stream, "cuda_stream", stream)
+    return C.c_void_p(int(h)) if h else None
+
+
+_YCBCR_K = {"601": (0.299, 0.114), "709": (0.2126, 0.0722), "2020": (0.2627, 0.0593)}
+
+
+def ycbcr_matrix(name):
+    """(m_rv, m_gu, m_gv, m_bu) of BT.601, BT.709 or BT.2020 as float32 of the float64 values 2(1 - Kr),
+    -2 Kb (1 - Kb) / Kg, -2 Kr (1 - Kr) / Kg, 2(1 - Kb) with Kg = 1 - Kr - Kb"""
+    if str(name) not in _YCBCR_K:
+        raise EuError(f"ycbcr_matrix: {name!r} is none of '601', '709', '2020'")
+    kr, kb = _YCBCR_K[str(name)]
+    kg = 1.0 - kr - kb
+    return tuple(np.float32(v) for v in (2.0 * (1.0 - kr), -2.0 * kb * (1.0 - kb) / kg, -2.0 * kr * (1.0 - kr) / kg,
+                                         2.0 * (1.0 - kb)))
+
+
+def ycbcr_tables(bits, depth=None, full_range=False, msb_aligned=False):
+    """(y_table, c_table), 1 << bits float32 each: what a luma / a chroma sample of `depth` significant bits
+    (default: bits) becomes. The code c of a stored value v is v, or v >> (bits - depth) when the code sits in the
+    high bits (P010). With s = 2**(depth - 8), in float64 and then rounded: limited range (c - 16 s) / (219 s) and
+    (c - 128 s) / (224 s); full range c / (2**depth - 1) and (c - 128 s) / (2**depth - 1)."""
+    if bits not in (8, 16):
+        raise EuError("ycbcr_tables: bits is 8 or 16")
+    depth = bits if depth is None else int(depth)
+    if depth < 8 or depth > bits:
+        raise EuError("ycbcr_tables: depth is 8 .. bits")
+    v = np.arange(1 << bits, dtype=np.int64)
+    c = (v >> (bits - depth) if msb_aligned else v).astype(np.float64)
+    s = 2.0 ** (depth - 8)
+    if full_range:
+        top = 2.0 ** depth - 1.0
+        y, ch = c / top, (c - 128.0 * s) / top
+    else:
+        y, ch = (c - 16.0 * s) / (219.0 * s), (c - 128.0 * s) / (224.0 * s)
+    return y.astype(np.float32), ch.astype(np.float32)
+
+
+def _plane(a, what, on_device):
+    """(address, row pitch in bytes, element stride of a row in samples, bits) of a 2-D plane of samples"""
+    if _is_torch(a) != on_device:
+        raise EuError("ycbcr: the planes are all numpy arrays or all torch tensors on the device")
+    if a.ndim != 2:
+        raise EuError(f"ycbcr: {what} is a 2-D plane")
+    if on_device:
+        import torch
+        bits = {torch.uint8: 8, torch.uint16: 16}.get(a.dtype)
+        if bits is None or not a.is_cuda:
+            raise EuError(f"ycbcr: {what} is uint8 or uint16 and on the device")
+        size = bits // 8
+        strides = tuple(v * size for v in a.stride())
+        addr = a.data_ptr()
+    else:
+        bits = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16}.get(a.dtype)
+        if bits is None or not a.dtype.isnative:
+            raise EuError(f"ycbcr: {what} is uint8 or uint16 in host order")
+        size = bits // 8
+        strides = tuple(a.strides)
+        addr = a.ctypes.data
+    h, w = a.shape
+    step = strides[1] // size if w > 1 else 1
+    if w > 1 and (strides[1] <= 0 or strides[1] % size or step not in (1, 2)):
+        raise EuError(f"ycbcr: the samples of a row of {what} are contiguous, or interleaved with one other plane")
+    row = ((w - 1) * step + 1) * size
+    pitch = strides[0] if h > 1 else row
+    if pitch < row:
+        raise EuError(f"ycbcr: the rows of {what} overlap or run backwards")
+    return addr, pitch, step, bits
+
+
+def _ycbcr_struct(y, chroma, matrix, y_table, c_table, wait=True):
+    """(eu_ycbcr, (h, w), what it points into) for a luma plane, chroma as (cb, cr) or one (ch, cw, 2) array"""
+    on_device = _is_torch(y)
+    if not on_device:
+        y = np.asarray(y)
+    if isinstance(chroma, (tuple, list)):
+        if len(chroma) != 2:
+            raise EuError("ycbcr: chroma is a pair (cb, cr) or one (ch, cw, 2) array")
+        cb, cr = chroma if on_device else (np.asarray(chroma[0]), np.asarray(chroma[1]))
+    else:
+        if not on_device:
+            chroma = np.asarray(chroma)
+        if chroma.ndim != 3 or chroma.shape[2] != 2:
+            raise EuError("ycbcr: chroma is a pair (cb, cr) or one (ch, cw, 2) array")
+        cb, cr = chroma[:, :, 0], chroma[:, :, 1]
+    ya, yp, ystep, bits = _plane(y, "y", on_device)
+    ba, bp, bstep, bbits = _plane(cb, "cb", on_device)
+    ra, rp, rstep, rbits = _plane(cr, "cr", on_device)
+    if ystep != 1:
+        raise EuError("ycbcr: the luma samples of a row are contiguous")
+    if bbits != bits or rbits != bits or tuple(cb.shape) != tuple(cr.shape):
+        raise EuError("ycbcr: the three planes have one sample type, both chroma planes one shape")
+    h, w = y.shape
+    ch, cw = cb.shape
+    if h > 1 and ch > 1 and bp != rp:
+        raise EuError("ycbcr: both chroma planes have one row pitch")
+    if cw > 1 and bstep != rstep:
+        raise EuError("ycbcr: both chroma planes have one sample step")
+    subs = []
+    for n, cn, axis in ((w, cw, "width"), (h, ch, "height")):
+        if n < 1:
+            raise EuError("ycbcr: empty frame")
+        if cn == n:
+            subs.append(1)
+        elif cn == (n + 1) // 2:
+            subs.append(2)
+        else:
+            raise EuError(f"ycbcr: chroma {axis} {cn} fits neither {n} (no subsampling) nor {(n + 1) // 2} (by 2)")
+    if y_table is None or c_table is None:
+        dy, dc = ycbcr_tables(bits)
+        y_table = dy if y_table is None else y_table
+        c_table = dc if c_table is None else c_table
+    y_table = np.ascontiguousarray(y_table, np.float32)
+    c_table = np.ascontiguousarray(c_table, np.float32)
+    if y_table.shape != (1 << bits,) or c_table.shape != (1 << bits,):
+        raise EuError(f"a table for {bits}-bit samples has {1 << bits} entries")
+    if len(matrix) != 4:
+        raise EuError("ycbcr: matrix is (m_rv, m_gu, m_gv, m_bu)")
+    if on_device:
+        _settle(y, wait)
+    px = Ycbcr(ya, ba, ra, yp, bp if ch > 1 else max(bp, rp), bstep if cw > 1 else 1, subs[0], subs[1], bits,
+               int(on_device), y_table.ctypes.data, c_table.ctypes.data, *[float(np.float32(m)) for m in matrix])
+    return px, (h, w), (y, cb, cr, y_table, c_table)
+
+
+def ycbcr_floats(y, chroma, matrix, y_table, c_table, nchannels=3):
+    """eu_hip_ycbcr_floats: the (h, w, nchannels) float32 pixels of a Y'CbCr frame of host planes - what load_ycbcr
+    loads, by definition. Host function, no device needed. Arguments as Source.load_ycbcr."""
+    px, (h, w), hold = _ycbcr_struct(y, chroma, matrix, y_table, c_table)
+    out = np.zeros((h, w, nchannels), np.float32)
+    _check(lib().eu_hip_ycbcr_floats(C.byref(px), w, h, nchannels, _ptr(out)))
+    return out
+
+
+def reload_scratch_release():
+    """eu_hip_reload_scratch_release: waits for every reload so far and frees the scratch they share"""
+    _check(lib().eu_hip_reload_scratch_release())
 
 
 def facet_alpha_rows(width, height, polygons=(), crop=None, crop_kind=0):
@@ -391,57 +565,35 @@ class Source:
     """A source image resident in HBM (the asset_handler entry,
     environment.h:84-227)."""
 
-    def __init__(self, handle, fct):
+    def __init__(self, handle, fct, spline_degree=None):
         self.handle = handle
         self.fct = fct
+        self.spline_degree = spline_degree
 
-    @classmethod
-    def load(cls, fct, pixels, spline_degree, prefilter_degree=None, support_min=8,
-             tile_size=64, masks=(), crop=None, crop_kind=0):
-        """pixels -> braced + prefiltered coefficients, on the device. `pixels`: a numpy array or a
-        float32 torch tensor on the library's device. masks (PTO exclude polygons, a list of (xs, ys)),
-        crop (x0, x1, y0, y1) with crop_kind 1 rectangular / 2 elliptic: source_t's alpha edit, made on
-        the device on the way into the container (eu_hip_source_load_edited); the pixels may then have
-        one channel fewer than the facet, which gains its alpha channel here."""
-        if prefilter_degree is None:
-            prefilter_degree = spline_degree
-        cf = fct.c_struct()
-        h = C.c_void_p()
+    @staticmethod
+    def _float_feed(fct, pixels, masks, crop, crop_kind, wait=True):
+        """(address, channels, on_device, eu_facet_edit or None, what they point into) of float pixels"""
         on_device = _is_torch(pixels)
         if not on_device:
             pixels = np.ascontiguousarray(pixels, np.float32)
         # (h, w, channels); (h, w) for the one channel of a facet that gains alpha; else as the facet says
         pch = pixels.shape[2] if pixels.ndim == 3 else 1 if pixels.ndim == 2 and fct.nchannels == 2 else fct.nchannels
+        ptr = C.c_void_p(_torch_ptr(pixels, wait)) if on_device else _ptr(pixels)
         if on_device or len(masks) or crop is not None or pch != fct.nchannels:
             e, hold = _facet_edit(masks, crop, crop_kind, pch, on_device)
-            ptr = C.c_void_p(_torch_ptr(pixels)) if on_device else _ptr(pixels)
-            _check(lib().eu_hip_source_load_edited(C.byref(cf), ptr, C.byref(e), spline_degree, prefilter_degree,
-                                                   support_min, tile_size, C.byref(h)))
-            return cls(h, fct)
-        _check(lib().eu_hip_source_load(C.byref(cf), _ptr(pixels), spline_degree,
-                                        prefilter_degree, support_min, tile_size, C.byref(h)))
-        return cls(h, fct)
+            return ptr, pch, on_device, e, (pixels, hold)
+        return ptr, pch, on_device, None, (pixels,)
 
-    @classmethod
-    def load_samples(cls, fct, samples, colour_table=None, alpha_table=None, maxval=None, big_endian=False,
-                     spline_degree=1, prefilter_degree=None, support_min=8, tile_size=64, masks=(), crop=None,
-                     crop_kind=0):
-        """8- or 16-bit integer samples -> the same source as load() of table[samples], decoded on the device
-        (eu_hip_source_load_samples): the samples go up as they are, no float copy is made on the host.
-        `samples`: a uint8 / uint16 numpy array or a contiguous torch tensor of those dtypes on the library's
-        device, (h, w, channels) or (h, w); big_endian: 16-bit samples are stored high byte first, as in PNM /
-        PAM files. colour_table / alpha_table: float32, 256 or 65536 entries - the float each value becomes in
-        a colour channel / in the last of 2 or 4 channels (alpha_table None: the colour table). Without tables
-        both are v / maxval in float32, maxval defaulting to 255 / 65535. masks, crop, crop_kind as load()."""
-        if prefilter_degree is None:
-            prefilter_degree = spline_degree
+    @staticmethod
+    def _samples_feed(fct, samples, colour_table, alpha_table, maxval, big_endian, masks, crop, crop_kind, wait=True):
+        """(eu_samples, eu_facet_edit or None, what they point into)"""
         on_device = _is_torch(samples)
         if on_device:
             import torch
             bits = {torch.uint8: 8, torch.uint16: 16}.get(samples.dtype)
             if bits is None or not samples.is_cuda or not samples.is_contiguous():
                 raise EuError("a torch tensor handed over as samples is uint8 or uint16, contiguous and on the device")
-            torch.cuda.current_stream(samples.device).synchronize()
+            _settle(samples, wait)
             data = samples.data_ptr()
         else:
             samples = np.asarray(samples)
@@ -464,29 +616,18 @@ class Source:
         sm = Samples(data, bits, int(bool(big_endian)), pch, int(on_device), tabs[0].ctypes.data,
                      tabs[1].ctypes.data if len(tabs) > 1 else None)
         e, hold = _facet_edit(masks, crop, crop_kind, pch, on_device)
-        cf = fct.c_struct()
-        h = C.c_void_p()
         edited = len(masks) or crop is not None
-        _check(lib().eu_hip_source_load_samples(C.byref(cf), C.byref(sm), C.byref(e) if edited else None, spline_degree,
-                                                prefilter_degree, support_min, tile_size, C.byref(h)))
-        return cls(h, fct)
+        return sm, e if edited else None, (samples, tabs, hold)
 
-    @classmethod
-    def load_rgbe(cls, fct, quads, colour_table=None, spline_degree=1, prefilter_degree=None, support_min=8,
-                  tile_size=64, masks=(), crop=None, crop_kind=0):
-        """Radiance RGBE pixels -> the same source as load() of their decoded floats, decoded on the device
-        (eu_hip_source_load_rgbe): the quads go up as they are, no float copy is made on the host. `quads`: a uint8
-        numpy array or a contiguous torch uint8 tensor on the library's device, (h, w, 4): R, G, B, E. fct.nchannels is
-        3, or 4: the facet gains alpha = 1.0 here. colour_table: float32, 65536 entries indexed (E << 8) | mantissa -
-        the float a channel becomes; None: mantissa * 2^(E - 136), E == 0 -> 0. masks, crop, crop_kind as load()."""
-        if prefilter_degree is None:
-            prefilter_degree = spline_degree
+    @staticmethod
+    def _rgbe_feed(quads, colour_table, masks, crop, crop_kind, wait=True):
+        """(eu_rgbe, eu_facet_edit or None, what they point into)"""
         on_device = _is_torch(quads)
         if on_device:
             import torch
             if quads.dtype != torch.uint8 or not quads.is_cuda or not quads.is_contiguous():
                 raise EuError("a torch tensor handed over as quads is uint8, contiguous and on the device")
-            torch.cuda.current_stream(quads.device).synchronize()
+            _settle(quads, wait)
             data = quads.data_ptr()
         else:
             quads = np.asarray(quads)
@@ -502,12 +643,143 @@ class Source:
                 raise EuError("a table for RGBE pixels has 65536 entries")
         px = Rgbe(data, int(on_device), colour_table.ctypes.data if colour_table is not None else None)
         e, hold = _facet_edit(masks, crop, crop_kind, 3, on_device)
+        edited = len(masks) or crop is not None
+        return px, e if edited else None, (quads, colour_table, hold)
+
+    @staticmethod
+    def _ycbcr_feed(y, chroma, matrix, y_table, c_table, masks, crop, crop_kind, wait=True):
+        """(eu_ycbcr, eu_facet_edit or None, what they point into)"""
+        px, shape, hold = _ycbcr_struct(y, chroma, matrix, y_table, c_table, wait)
+        e, hold2 = _facet_edit(masks, crop, crop_kind, 3, bool(px.on_device))
+        edited = len(masks) or crop is not None
+        return px, e if edited else None, (hold, hold2)
+
+    @classmethod
+    def load(cls, fct, pixels, spline_degree, prefilter_degree=None, support_min=8,
+             tile_size=64, masks=(), crop=None, crop_kind=0):
+        """pixels -> braced + prefiltered coefficients, on the device. `pixels`: a numpy array or a
+        float32 torch tensor on the library's device. masks (PTO exclude polygons, a list of (xs, ys)),
+        crop (x0, x1, y0, y1) with crop_kind 1 rectangular / 2 elliptic: source_t's alpha edit, made on
+        the device on the way into the container (eu_hip_source_load_edited); the pixels may then have
+        one channel fewer than the facet, which gains its alpha channel here."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
         cf = fct.c_struct()
         h = C.c_void_p()
-        edited = len(masks) or crop is not None
-        _check(lib().eu_hip_source_load_rgbe(C.byref(cf), C.byref(px), C.byref(e) if edited else None, spline_degree,
-                                             prefilter_degree, support_min, tile_size, C.byref(h)))
-        return cls(h, fct)
+        ptr, pch, on_device, e, hold = cls._float_feed(fct, pixels, masks, crop, crop_kind)
+        if e is not None:
+            _check(lib().eu_hip_source_load_edited(C.byref(cf), ptr, C.byref(e), spline_degree, prefilter_degree,
+                                                   support_min, tile_size, C.byref(h)))
+            return cls(h, fct, spline_degree)
+        _check(lib().eu_hip_source_load(C.byref(cf), ptr, spline_degree,
+                                        prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct, spline_degree)
+
+    @classmethod
+    def load_samples(cls, fct, samples, colour_table=None, alpha_table=None, maxval=None, big_endian=False,
+                     spline_degree=1, prefilter_degree=None, support_min=8, tile_size=64, masks=(), crop=None,
+                     crop_kind=0):
+        """8- or 16-bit integer samples -> the same source as load() of table[samples], decoded on the device
+        (eu_hip_source_load_samples): the samples go up as they are, no float copy is made on the host.
+        `samples`: a uint8 / uint16 numpy array or a contiguous torch tensor of those dtypes on the library's
+        device, (h, w, channels) or (h, w); big_endian: 16-bit samples are stored high byte first, as in PNM /
+        PAM files. colour_table / alpha_table: float32, 256 or 65536 entries - the float each value becomes in
+        a colour channel / in the last of 2 or 4 channels (alpha_table None: the colour table). Without tables
+        both are v / maxval in float32, maxval defaulting to 255 / 65535. masks, crop, crop_kind as load()."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
+        sm, e, hold = cls._samples_feed(fct, samples, colour_table, alpha_table, maxval, big_endian, masks, crop, crop_kind)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        _check(lib().eu_hip_source_load_samples(C.byref(cf), C.byref(sm), C.byref(e) if e is not None else None,
+                                                spline_degree, prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct, spline_degree)
+
+    @classmethod
+    def load_rgbe(cls, fct, quads, colour_table=None, spline_degree=1, prefilter_degree=None, support_min=8,
+                  tile_size=64, masks=(), crop=None, crop_kind=0):
+        """Radiance RGBE pixels -> the same source as load() of their decoded floats, decoded on the device
+        (eu_hip_source_load_rgbe): the quads go up as they are, no float copy is made on the host. `quads`: a uint8
+        numpy array or a contiguous torch uint8 tensor on the library's device, (h, w, 4): R, G, B, E. fct.nchannels is
+        3, or 4: the facet gains alpha = 1.0 here. colour_table: float32, 65536 entries indexed (E << 8) | mantissa -
+        the float a channel becomes; None: mantissa * 2^(E - 136), E == 0 -> 0. masks, crop, crop_kind as load()."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
+        px, e, hold = cls._rgbe_feed(quads, colour_table, masks, crop, crop_kind)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        _check(lib().eu_hip_source_load_rgbe(C.byref(cf), C.byref(px), C.byref(e) if e is not None else None,
+                                             spline_degree, prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct, spline_degree)
+
+    @classmethod
+    def load_ycbcr(cls, fct, y, chroma, matrix, y_table=None, c_table=None, spline_degree=1, prefilter_degree=None,
+                   support_min=8, tile_size=64, masks=(), crop=None, crop_kind=0):
+        """The planes of a Y'CbCr frame -> the same source as load() of ycbcr_floats() of them, decoded on the device
+        (eu_hip_source_load_ycbcr): the planes go up as their rows lie, no float copy is made on the host. `y`: (h, w)
+        uint8 or uint16, a numpy array or a torch tensor on the library's device. `chroma`: a pair (cb, cr) of (ch, cw)
+        arrays, or one (ch, cw, 2) array of interleaved Cb, Cr (NV12 / P010; NV21: the pair (a[..., 1], a[..., 0])).
+        sub_x and sub_y follow from the shapes: ch, cw equal h, w or their halves rounded up. Row strides are honoured as
+        pitches; the samples of a row are contiguous (interleaved chroma: two apart). `matrix`: (m_rv, m_gu, m_gv, m_bu),
+        see ycbcr_matrix(). y_table / c_table: float32, 256 or 65536 entries - the float a luma / chroma sample becomes;
+        without them ycbcr_tables(bits). Chroma is replicated. fct.nchannels is 3, or 4: the facet gains alpha = 1.0
+        here. masks, crop, crop_kind as load()."""
+        if prefilter_degree is None:
+            prefilter_degree = spline_degree
+        px, e, hold = cls._ycbcr_feed(y, chroma, matrix, y_table, c_table, masks, crop, crop_kind)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        _check(lib().eu_hip_source_load_ycbcr(C.byref(cf), C.byref(px), C.byref(e) if e is not None else None,
+                                              spline_degree, prefilter_degree, support_min, tile_size, C.byref(h)))
+        return cls(h, fct, spline_degree)
+
+    # ---- new pixels into the resident container (eu_hip_source_reload) -----------------------------------------
+    def _reload(self, px, e, prefilter_degree, stream):
+        if prefilter_degree is None:
+            prefilter_degree = self.spline_degree
+        if prefilter_degree is None:
+            raise EuError("reload: this source does not know its spline degree: give prefilter_degree")
+        if e is not None:
+            px.edit = C.cast(C.pointer(e), C.c_void_p)
+        _check(lib().eu_hip_source_reload(self.handle, C.byref(px), prefilter_degree, _stream_handle(stream)))
+
+    def reload(self, pixels, prefilter_degree=None, masks=(), crop=None, crop_kind=0, stream=None):
+        """New float pixels into the resident container, in place (eu_hip_source_reload): afterwards the source is
+        what load() makes of `pixels` for this facet - geometry, degree and device address stay. Arguments as load().
+        stream: None (the library's stream), a torch stream or a raw hipStream_t; the device work is queued on it, behind
+        every render that still reads the container, and later renders go behind it. With a stream a torch tensor's own
+        stream is NOT synchronised: the caller orders `stream` behind whatever writes the tensor. Without one the call
+        behaves as load(): the tensor's stream is synchronised, the library's used. With device pixels and no masks or
+        crop the call does not wait for the device: sync(), or synchronising the stream, says the container is ready."""
+        ptr, pch, on_device, e, hold = self._float_feed(self.fct, pixels, masks, crop, crop_kind, wait=stream is None)
+        px = Pixels(PX_FLOATS, ptr, pch, int(on_device), None, None, None, None)
+        if e is not None and not (len(masks) or crop is not None):
+            e = None                      # nothing but the channel count and the side, which px says itself
+        self._reload(px, e, prefilter_degree, stream)
+
+    def reload_samples(self, samples, colour_table=None, alpha_table=None, maxval=None, big_endian=False,
+                       prefilter_degree=None, masks=(), crop=None, crop_kind=0, stream=None):
+        """reload() from 8- or 16-bit integer samples: arguments as load_samples(), stream as reload()."""
+        sm, e, hold = self._samples_feed(self.fct, samples, colour_table, alpha_table, maxval, big_endian, masks, crop,
+                                         crop_kind, wait=stream is None)
+        px = Pixels(PX_SAMPLES, None, 0, 0, C.cast(C.pointer(sm), C.c_void_p), None, None, None)
+        self._reload(px, e, prefilter_degree, stream)
+
+    def reload_rgbe(self, quads, colour_table=None, prefilter_degree=None, masks=(), crop=None, crop_kind=0,
+                    stream=None):
+        """reload() from Radiance RGBE pixels: arguments as load_rgbe(), stream as reload()."""
+        rg, e, hold = self._rgbe_feed(quads, colour_table, masks, crop, crop_kind, wait=stream is None)
+        px = Pixels(PX_RGBE, None, 0, 0, None, C.cast(C.pointer(rg), C.c_void_p), None, None)
+        self._reload(px, e, prefilter_degree, stream)
+
+    def reload_ycbcr(self, y, chroma, matrix, y_table=None, c_table=None, prefilter_degree=None, masks=(), crop=None,
+                     crop_kind=0, stream=None):
+        """reload() from the planes of a Y'CbCr frame: arguments as load_ycbcr(), stream as reload(). A decoder's
+        surface on the device, no masks: nothing waits - the decode, the prefilter and the renders that follow are
+        stream-ordered."""
+        yc, e, hold = self._ycbcr_feed(y, chroma, matrix, y_table, c_table, masks, crop, crop_kind, wait=stream is None)
+        px = Pixels(PX_YCBCR, None, 0, 0, None, None, C.cast(C.pointer(yc), C.c_void_p), None)
+        self._reload(px, e, prefilter_degree, stream)
 
     @classmethod
     def adopt(cls, fct, container, spline_degree, bc0=BC_REFLECT, bc1=BC_REFLECT,
@@ -518,7 +790,7 @@ class Source:
         h = C.c_void_p()
         _check(lib().eu_hip_source_adopt(C.byref(cf), _ptr(container), spline_degree, bc0,
                                          bc1, support_min, tile_size, C.byref(h)))
-        return cls(h, fct)
+        return cls(h, fct, spline_degree)
 
     @classmethod
     def alloc(cls, fct, spline_degree, support_min=8, tile_size=64):
@@ -527,7 +799,7 @@ class Source:
         h = C.c_void_p()
         _check(lib().eu_hip_source_alloc(C.byref(cf), spline_degree, support_min, tile_size,
                                          C.byref(h)))
-        return cls(h, fct)
+        return cls(h, fct, spline_degree)
 
     def update_facet(self, fct):
         """the facet's geometry changed (orientation, hfov, lens, brighten): rebuild the

@@ -197,7 +197,7 @@ int eu_hip_sync(void)
   if (cur().device < 0) return EU_OK;
   HIPCHK(hipStreamSynchronize(cur().stream));
   const context &c = cur();
-  for (const eu_readers *r : { &c.tables, &c.staged.wl_pair, &c.rays.readers, &c.views.readers, &c.layers.readers, &c.enc.readers, &c.alpha.readers })
+  for (const eu_readers *r : { &c.tables, &c.staged.wl_pair, &c.rays.readers, &c.views.readers, &c.layers.readers, &c.enc.readers, &c.alpha.readers, &c.reload.readers })
     HIPCHK(r->host_wait());
   return EU_OK;
 }

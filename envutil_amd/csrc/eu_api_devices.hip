@@ -20,6 +20,7 @@ int replica_of(eu_source *src, int k, eu_source **out)
     if (!r) return fail(EU_ERR_NO_DEVICE, "out of host memory");
     for (int j = 0; j < EU_MAX_SLOTS; j++) r->replica[j] = nullptr;
     r->is_replica = true; r->slot = k; r->dev = nullptr;
+    r->readers = eu_readers(); r->written = eu_readers(); r->own_written = false;      // the original's events stay its own
     int rc = set_slot(k);
     if (rc) { delete r; return rc; }
     hipError_t e = hipMalloc((void **)&r->dev, src->nfloats * sizeof(float));
@@ -140,6 +141,13 @@ int eu_hip_render_devices(const eu_target *trg, eu_source *const *srcs, int nsrc
   int begin[EU_MAX_SLOTS], end[EU_MAX_SLOTS];
   cost_strips(trg, srcs, nsrc, nslots_, begin, end);
   const eu_switches sw = eu_read_switches();
+  // the slots read the originals (slot 0 renders them, the others copy them on first use): a reload of one of them,
+  // on a caller's stream or on the library's own, has to be through. The call leaves no reader behind: the guard waits
+  for (int f = 0; f < nsrc; f++) {
+    if (!srcs[f]) return fail(EU_ERR_HANDLE, "null source");
+    HIPCHK(srcs[f]->written.host_wait());
+    if (srcs[f]->own_written) { HIPCHK(hipStreamSynchronize(ctx_[srcs[f]->slot].stream)); srcs[f]->own_written = false; }
+  }
   // every slot: its replicas, its strip into its own buffer, the strip's way to `out` behind it on the
   // slot's stream; the slots run concurrently, one host thread feeds them
   struct guard { ~guard() { for (int k = 0; k < nslots_; k++) { cur_slot_ = k; if (ctx_[k].device >= 0 && hipSetDevice(ctx_[k].device) == hipSuccess && ctx_[k].stream) (void)hipStreamSynchronize(ctx_[k].stream); } cur_slot_ = 0; if (ctx_[0].device >= 0) (void)hipSetDevice(ctx_[0].device); } } sync_all_on_exit;

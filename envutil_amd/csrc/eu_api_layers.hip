@@ -133,6 +133,7 @@ int eu_hip_render_layers(const eu_target *trg, eu_source *const *layers, int nla
   HIPCHK(lb.row.reserve(tb.row.size()));
   HIPCHK(lb.tab.reserve(tab.size()));
   if (!out_on_device) HIPCHK(lb.stage.reserve((size_t)per_launch * frame_bytes / sizeof(float)));
+  if ((rc = order_sources(layers, nlayers, st))) return rc;      // behind a reload of a layer
   // the one host synchronisation of the call: tables, layer table and a new tap table, in flight from host vectors
   HIPCHK(hipMemcpyAsync(lb.col.p, tb.col.data(), tb.col.size() * sizeof(float), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(lb.row.p, tb.row.data(), tb.row.size() * sizeof(float), hipMemcpyHostToDevice, st));
@@ -168,7 +169,7 @@ int eu_hip_render_layers(const eu_target *trg, eu_source *const *layers, int nla
   }
   if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
   drain_on_exit.on = false;          // a device output stays queued: `st` goes on reading the call's buffers
-  return note_caller(lb.readers, out_on_device ? stream : nullptr, EU_OK);
+  return note_readers(lb.readers, layers, nlayers, out_on_device ? stream : nullptr, EU_OK);
 }
 
 }  // extern "C"

@@ -77,8 +77,9 @@ int eu_hip_render_rays(const eu_rays *r, eu_source *src, float *out, size_t out_
   const eu_switches sw = eu_read_switches();
   if ((rc = upload_ray_taps(r))) return rc;
   hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
+  if ((rc = order_sources(&src, 1, st))) return rc;      // behind a reload of the source
   if (r->rays_on_device && out_on_device)
-    return note_caller(cur().rays.readers, stream, launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out, out_row_stride_bytes,
+    return note_readers(cur().rays.readers, &src, 1, stream, launch_rays(r, src, sw, r->rays, r->ray_row_stride_bytes, out, out_row_stride_bytes,
                                                    r->width, r->height, st));
   // A host buffer on either side: the grid goes through in chunks of rows - a flat list in chunks of its one
   // row - of bounded size, copy in, launch, copy out, all in order on `st`; the call returns when `out` is complete

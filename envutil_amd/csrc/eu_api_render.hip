@@ -581,8 +581,10 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   if (enc && (rc = upload_steps(enc, st))) return rc;
   // the frame buffer is about to be rewritten on `st`: behind the calls that used it before, as upload_steps orders it
   if (rgbe && (rc = order_encoders(st))) return rc;
+  // the sources may have been refilled in place (eu_hip_source_reload): `st` reads them behind that
+  if ((rc = order_sources(srcs, nsrc, st))) return rc;
   if (out_on_device)
-    return note_caller(cur().tables, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc, rgbe));
+    return note_readers(cur().tables, srcs, nsrc, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc, rgbe));
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (!rows) return EU_OK;
   HIPCHK(cur().out.stage.reserve((rows * row_bytes + sizeof(float) - 1) / sizeof(float)));

@@ -6,6 +6,8 @@
 #include "eu_alpha.h"
 #include "eu_decode.h"
 #include "eu_rgbe_dev.h"
+#include "eu_ycbcr_dev.h"
+#include "../../include/eu_ycbcr.h"
 
 using namespace eu_host;
 
@@ -158,6 +160,7 @@ int new_source(const eu_facet *fct, int spline_degree, int bc0, int bc1, int sup
     eu::container_geometry(spline_degree, bc0, bc1, fct->window_width, fct->window_height, &s->geom);
     s->bc[0] = bc0; s->bc[1] = bc1;
   }
+  s->support_min = support_min; s->tile_size = tile_size;
   s->nfloats = (size_t)s->geom.shape[0] * s->geom.shape[1] * s->nch;
   // slack behind the container: the LDS-staging kernel (eu_render4.hip) fetches whole
   // 64-texel instructions, up to 3 rows and 63 texels past a tile's box (never evaluated)
@@ -245,93 +248,198 @@ enum feed_kind {
   FEED_HOST_FLOATS,      // host floats at the facet's channel count, no edit: copied straight to the destination
   FEED_EDITED_FLOATS,    // floats on the host (staged on the device first) or on the device, through the edit
   FEED_SAMPLES,          // 8- or 16-bit samples on the host (uploaded behind their tables) or on the device, decoded there
-  FEED_RGBE              // Radiance RGBE quads on the host (uploaded behind their table, if any) or on the device, decoded there
+  FEED_RGBE,             // Radiance RGBE quads on the host (uploaded behind their table, if any) or on the device, decoded there
+  FEED_YCBCR             // the planes of a Y'CbCr frame on the host (uploaded behind their tables, row by row) or on the device, decoded there
 };
 struct load_feed {
   feed_kind kind;
   const char *who;             // the entry point, as messages name it
-  const void *data;            // the floats or the samples
+  const void *data;            // the floats or the samples (FEED_YCBCR: the luma plane)
   bool on_device;              // data lies in device memory
   int src_ch;                  // channels of data: the facet's, or one less
   const eu_facet_edit *edit;   // masks and crop (FEED_HOST_FLOATS: none)
   bool alter;                  // the edit's kernel runs: FEED_EDITED_FLOATS whenever the edit changes something (a gained
-                               // channel too), FEED_SAMPLES for masks or a crop (the decoder writes a gained channel itself)
+                               // channel too), the integer feeds for masks or a crop (the decoder writes a gained channel itself)
   const eu_samples *smp;       // FEED_SAMPLES: bits, byte order, tables
   const float *rgbe_table;     // FEED_RGBE: 65536 floats, or nullptr for the format's own decode
+  const eu_ycbcr *ycc;         // FEED_YCBCR: planes, layout, tables, matrix
 };
 
-// One load pipeline with four feeds. Written once: the source and its container (source_bcs, new_source), the plane
-// the pixels arrive in - the facet's window as the core of the container, or the stack of a cubemap's six faces in
-// scratch -, the clearing of a flat container, the finish (cube build, or the prefilter full_sphere() picks), the one
-// synchronisation, and the error precedence: the message the plan upload or a kernel launch set, then the HIP error,
-// then "device set-up stage failed". The feed is all that differs. Host floats: one H2D copy into the plane (1-D
-// into the faces, 2-D into the core), no staging, no kernel. Floats through the edit: host pixels are staged on the
-// device at their own channel count; upload_alpha_plan + eu_launch_facet_alpha write the plane, or - an edit that
-// changes nothing, pixels on the device - a 2-D D2D copy. Integer samples: both tables and, behind them, the samples
-// of a host image go into one device block; eu_launch_decode writes the plane, or - with masks or a crop - a dense
-// buffer that eu_launch_facet_alpha then reads. RGBE quads: the integer feed with a dword per pixel - the optional table
-// and, behind it, the quads of a host image in one block; eu_launch_rgbe_decode writes what eu_launch_decode writes
-// for three samples per pixel. Scratch is freed by scope, after the synchronisation.
-// The entry points make their own argument checks, in their own order, and find the device (ensure_init).
-int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
-                const load_feed &feed, eu_source **out)
+// Where a fill keeps what it needs beside the container. A load's is its own and freed by scope, after the load's one
+// synchronisation. A reload's cannot be - its work may still be queued when it returns - so it lies in the context
+// (context::reload), grows on demand and serves the next reload: that one's stream goes behind reload.readers, and a
+// buffer that has to grow (reserve() frees) or a table that changes is waited for by the host first.
+struct fill_scratch {
+  const bool resident;
+  eu_dev_tmp<char> t_block;
+  eu_dev_tmp<float> t_staged, t_faces;
+  std::vector<float> tabs;           // a load's tables on their way up: alive until the load has synchronised
+  explicit fill_scratch(bool res) : resident(res) {}
+
+  template <class T> static hipError_t grow(eu_dev_buf<T> &b, size_t n)
+  {
+    if (b.cap >= n) return hipSuccess;
+    hipError_t e = cur().reload.readers.host_wait();
+    if (e == hipSuccess) e = hipStreamSynchronize(cur().stream);
+    return e == hipSuccess ? b.reserve(n) : e;
+  }
+  // the feed's tables (`tabs`, possibly none) on the device and room for nbytes bytes of a host image: a load's in
+  // ONE block, tables first; a reload's tables are held (equal ones are not sent again), its bytes a buffer of their own
+  hipError_t tables_and_bytes(size_t nbytes, hipStream_t st, const float **tab, char **bytes)
+  {
+    const size_t tab_bytes = tabs.size() * sizeof(float);
+    *tab = nullptr; *bytes = nullptr;
+    hipError_t e = hipSuccess;
+    if (!resident) {
+      if (!tab_bytes && !nbytes) return e;
+      e = t_block.alloc(tab_bytes + nbytes);
+      if (e == hipSuccess && tab_bytes) e = hipMemcpyAsync(t_block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, st);
+      if (tab_bytes) *tab = reinterpret_cast<const float *>(t_block.p);
+      *bytes = t_block.p + tab_bytes;
+      return e;
+    }
+    held_table &h = cur().reload.tables;
+    if (tab_bytes && !h.holds(tabs.data(), tabs.size())) {
+      // an earlier reload may still read the device table, and its upload the host copy
+      e = cur().reload.readers.host_wait();
+      if (e == hipSuccess) e = hipStreamSynchronize(cur().stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      h.host.clear();
+      if (e == hipSuccess) e = h.dev.reserve(tabs.size());
+      if (e == hipSuccess) {
+        h.host.swap(tabs);
+        e = hipMemcpyAsync(h.dev.p, h.host.data(), tab_bytes, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) h.host.clear();
+      }
+    }
+    if (tab_bytes) *tab = h.dev.p;
+    if (e == hipSuccess && nbytes) { e = grow(cur().reload.block, nbytes); *bytes = cur().reload.block.p; }
+    return e;
+  }
+  hipError_t staged(size_t n, float **p)
+  {
+    const hipError_t e = resident ? grow(cur().reload.staged, n) : t_staged.alloc(n);
+    *p = resident ? cur().reload.staged.p : t_staged.p;
+    return e;
+  }
+  hipError_t faces(size_t n, float **p)
+  {
+    const hipError_t e = resident ? grow(cur().reload.faces, n) : t_faces.alloc(n);
+    *p = resident ? cur().reload.faces.p : t_faces.p;
+    return e;
+  }
+};
+
+// what a fill leaves: the HIP error of an allocation or a copy, the result of the finish, and the status of a plan
+// upload or a kernel launch (its message is set)
+struct fill_result { hipError_t e; int rc, prc; };
+
+// One load pipeline with five feeds, in two halves. load_source MAKES the source and its container (source_bcs,
+// new_source), has it filled, synchronises once and settles the error precedence: the message the plan upload or a
+// kernel launch set, then the HIP error, then "device set-up stage failed". fill_source FILLS a source that exists,
+// for a load and for eu_hip_source_reload alike, all of it queued on `st`: the plane the pixels arrive in - the
+// facet's window as the core of the container, or the stack of a cubemap's six faces in scratch -, the clearing of a
+// flat container, the finish (cube build, or the prefilter full_sphere() picks). The feed is all that differs. Host
+// floats: one H2D copy into the plane (1-D into the faces, 2-D into the core), no staging, no kernel. Floats through the
+// edit: host pixels are staged on the device at their own channel count; upload_alpha_plan + eu_launch_facet_alpha
+// write the plane, or - an edit that changes nothing, pixels on the device - a 2-D D2D copy. Integer samples: both
+// tables and, behind them, the samples of a host image go to the device; eu_launch_decode writes the plane, or - with
+// masks or a crop - a dense buffer that eu_launch_facet_alpha then reads. RGBE quads: the integer feed with a dword
+// per pixel - the optional table and, behind it, the quads of a host image; eu_launch_rgbe_decode writes what
+// eu_launch_decode writes for three samples per pixel. Y'CbCr planes: both tables and, behind them, the planes of a host
+// frame as their rows lie (a 2-D copy each; interleaved chroma once); eu_launch_ycbcr_decode writes what the RGBE
+// decode writes. The geometry is the source's own: its container, the boundary conditions it holds, what it was built
+// with (support_min, tile_size). The entry points make their own argument checks, in their own order, and find the device.
+fill_result fill_source(eu_source *s, int prefilter_degree, const load_feed &feed, hipStream_t st, fill_scratch &sc)
 {
-  int rc, bc0, bc1;
-  source_bcs(fct, &bc0, &bc1);
-  eu_source *s = nullptr;
-  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  const eu_facet *fct = &s->fct;
   const std::string who(feed.who);
   const int nch = s->nch, src_ch = feed.src_ch, iir_stream = eu_read_switches().iir_stream;
   const bool cube = eu_cube_source(fct->projection);
   eu::metrics m {};
-  if (cube) m = eu::make_metrics(fct->width, fct->hfov, support_min, tile_size);
+  if (cube) m = eu::make_metrics(fct->width, fct->hfov, s->support_min, s->tile_size);
   const eu_container &gm = s->geom;
   const int w = cube ? int(m.face_px) : int(gm.core[0]), h = cube ? int(6 * m.face_px) : int(gm.core[1]);
   const size_t npix = size_t(w) * size_t(h);
-  eu_dev_tmp<float> staged, faces;   // floats in front of the edit, at src_ch channels; the faces of a cubemap
-  eu_dev_tmp<char> block;            // samples: both tables and, behind them, the samples of a host image, as they are
-  std::vector<float> tabs;
+  float *staged = nullptr, *faces = nullptr;   // floats in front of the edit, at src_ch channels; the faces of a cubemap
+  const float *tab = nullptr;                  // the feed's tables on the device
+  char *bytes = nullptr;                       // the samples, quads or planes of a host image, as they are
   const void *src = feed.data;
+  eu_ycbcr_decode_params yd {};
   hipError_t e = hipSuccess;
-  int prc = 0;
+  int rc = 0, prc = 0;
   // what the feed brings to the device first
   if (feed.kind == FEED_SAMPLES) {
     const size_t ntab = size_t(1) << feed.smp->bits, nbytes = npix * size_t(src_ch) * size_t(feed.smp->bits / 8);
     try {
-      tabs.assign(feed.smp->colour_table, feed.smp->colour_table + ntab);
+      sc.tabs.assign(feed.smp->colour_table, feed.smp->colour_table + ntab);
       const float *at = feed.smp->alpha_table ? feed.smp->alpha_table : feed.smp->colour_table;
-      tabs.insert(tabs.end(), at, at + ntab);
-    } catch (...) { destroy_source(s); return fail(EU_ERR_MEMORY, who + ": host memory"); }
-    const size_t tab_bytes = tabs.size() * sizeof(float);
-    e = block.alloc(tab_bytes + (feed.on_device ? 0 : nbytes));
-    if (e == hipSuccess) e = hipMemcpyAsync(block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, cur().stream);
+      sc.tabs.insert(sc.tabs.end(), at, at + ntab);
+    } catch (...) { return { e, rc, fail(EU_ERR_MEMORY, who + ": host memory") }; }
+    e = sc.tables_and_bytes(feed.on_device ? 0 : nbytes, st, &tab, &bytes);
     if (e == hipSuccess && !feed.on_device) {
-      e = hipMemcpyAsync(block.p + tab_bytes, feed.data, nbytes, hipMemcpyHostToDevice, cur().stream);
-      src = block.p + tab_bytes;
+      e = hipMemcpyAsync(bytes, feed.data, nbytes, hipMemcpyHostToDevice, st);
+      src = bytes;
     }
-    if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
+    if (e == hipSuccess && feed.alter) e = sc.staged(npix * src_ch, &staged);
   } else if (feed.kind == FEED_RGBE) {
-    const size_t tab_bytes = feed.rgbe_table ? 65536 * sizeof(float) : 0, nbytes = npix * 4;
+    const size_t nbytes = npix * 4;
     if (feed.rgbe_table) {
-      try { tabs.assign(feed.rgbe_table, feed.rgbe_table + 65536); }
-      catch (...) { destroy_source(s); return fail(EU_ERR_MEMORY, who + ": host memory"); }
+      try { sc.tabs.assign(feed.rgbe_table, feed.rgbe_table + 65536); }
+      catch (...) { return { e, rc, fail(EU_ERR_MEMORY, who + ": host memory") }; }
     }
-    if (tab_bytes || !feed.on_device) e = block.alloc(tab_bytes + (feed.on_device ? 0 : nbytes));
-    if (e == hipSuccess && tab_bytes) e = hipMemcpyAsync(block.p, tabs.data(), tab_bytes, hipMemcpyHostToDevice, cur().stream);
+    e = sc.tables_and_bytes(feed.on_device ? 0 : nbytes, st, &tab, &bytes);
     if (e == hipSuccess && !feed.on_device) {
-      e = hipMemcpyAsync(block.p + tab_bytes, feed.data, nbytes, hipMemcpyHostToDevice, cur().stream);
-      src = block.p + tab_bytes;
+      e = hipMemcpyAsync(bytes, feed.data, nbytes, hipMemcpyHostToDevice, st);
+      src = bytes;
     }
-    if (e == hipSuccess && feed.alter) e = staged.alloc(npix * src_ch);
+    if (e == hipSuccess && feed.alter) e = sc.staged(npix * src_ch, &staged);
+  } else if (feed.kind == FEED_YCBCR) {
+    const eu_ycbcr &y = *feed.ycc;
+    const size_t ntab = size_t(1) << y.bits, sb = size_t(y.bits / 8);
+    const size_t cw = (size_t(w) + y.sub_x - 1) / y.sub_x, chh = (size_t(h) + y.sub_y - 1) / y.sub_y;
+    try {
+      sc.tabs.assign(y.y_table, y.y_table + ntab);
+      sc.tabs.insert(sc.tabs.end(), y.c_table, y.c_table + ntab);
+    } catch (...) { return { e, rc, fail(EU_ERR_MEMORY, who + ": host memory") }; }
+    yd.y = y.y; yd.cb = y.cb; yd.cr = y.cr; yd.y_pitch = y.y_pitch; yd.c_pitch = y.c_pitch;
+    // a host frame: the rows of each plane, as they lie, at a pitch of whole dwords; chroma samples that interleave in
+    // ONE plane (NV12, NV21: the two pointers one sample apart) go up once
+    const char *pb = static_cast<const char *>(y.cb), *pr = static_cast<const char *>(y.cr);
+    // (the last row of a plane may end with its last sample, so a single row is one 1-D copy whatever its pitch)
+    const bool one = y.c_step == 2 && (pr == pb + sb || pb == pr + sb) && (chh == 1 || y.c_pitch >= 2 * cw * sb);
+    auto rows_up = [&](char *d, size_t dp, const void *s, size_t sp, size_t width, size_t rows) {
+      return rows == 1 ? hipMemcpyAsync(d, s, width, hipMemcpyHostToDevice, st)
+                       : hipMemcpy2DAsync(d, dp, s, sp, width, rows, hipMemcpyHostToDevice, st);
+    };
+    const size_t y_row = size_t(w) * sb, c_row = one ? 2 * cw * sb : ((cw - 1) * y.c_step + 1) * sb;
+    const size_t y_dp = (y_row + 3) & ~size_t(3), c_dp = (c_row + 3) & ~size_t(3);
+    const size_t nbytes = y_dp * h + (one ? 1 : 2) * c_dp * chh;
+    e = sc.tables_and_bytes(feed.on_device ? 0 : nbytes, st, &tab, &bytes);
+    if (e == hipSuccess && !feed.on_device) {
+      char *dy = bytes, *dc0 = dy + y_dp * h, *dc1 = dc0 + c_dp * chh;
+      e = rows_up(dy, y_dp, y.y, y.y_pitch, y_row, size_t(h));
+      if (one) {
+        const char *first = pb < pr ? pb : pr;
+        if (e == hipSuccess) e = rows_up(dc0, c_dp, first, y.c_pitch, c_row, chh);
+        yd.cb = dc0 + (pb - first); yd.cr = dc0 + (pr - first);
+      } else {
+        if (e == hipSuccess) e = rows_up(dc0, c_dp, pb, y.c_pitch, c_row, chh);
+        if (e == hipSuccess) e = rows_up(dc1, c_dp, pr, y.c_pitch, c_row, chh);
+        yd.cb = dc0; yd.cr = dc1;
+      }
+      yd.y = dy; yd.y_pitch = y_dp; yd.c_pitch = c_dp;
+    }
+    if (e == hipSuccess && feed.alter) e = sc.staged(npix * src_ch, &staged);
   } else if (feed.kind == FEED_EDITED_FLOATS && !feed.on_device) {
-    e = staged.alloc(npix * src_ch);
-    if (e == hipSuccess) e = hipMemcpyAsync(staged.p, feed.data, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, cur().stream);
-    src = staged.p;
+    e = sc.staged(npix * src_ch, &staged);
+    if (e == hipSuccess) e = hipMemcpyAsync(staged, feed.data, npix * src_ch * sizeof(float), hipMemcpyHostToDevice, st);
+    src = staged;
   }
   // the plane: w x h pixels of nch floats at dst, rows dst_pitch pixels apart
-  if (e == hipSuccess && cube) e = faces.alloc(npix * nch);
-  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), cur().stream);
-  float *dst = cube ? faces.p : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
+  if (e == hipSuccess && cube) e = sc.faces(npix * nch, &faces);
+  if (e == hipSuccess && !cube) e = hipMemsetAsync(s->dev, 0, s->nfloats * sizeof(float), st);
+  float *dst = cube ? faces : s->dev + ((size_t)gm.left[1] * gm.shape[0] + gm.left[0]) * nch;
   const size_t dst_pitch = cube ? size_t(w) : size_t(gm.shape[0]);
   const size_t row_bytes = size_t(w) * nch * sizeof(float), pitch_bytes = dst_pitch * nch * sizeof(float);
   if (e == hipSuccess) {
@@ -340,53 +448,172 @@ int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, in
     p.src_pitch = size_t(w); p.dst_pitch = dst_pitch;
     p.w = w; p.h = h; p.nch = nch; p.src_ch = src_ch;
     if (feed.kind == FEED_HOST_FLOATS) {
-      e = cube ? hipMemcpyAsync(dst, src, npix * nch * sizeof(float), hipMemcpyHostToDevice, cur().stream)
-               : hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyHostToDevice, cur().stream);
+      e = cube ? hipMemcpyAsync(dst, src, npix * nch * sizeof(float), hipMemcpyHostToDevice, st)
+               : hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyHostToDevice, st);
     } else if (feed.kind == FEED_EDITED_FLOATS) {
       if (!feed.alter)
-        e = hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyDeviceToDevice, cur().stream);
+        e = hipMemcpy2DAsync(dst, pitch_bytes, src, row_bytes, row_bytes, size_t(h), hipMemcpyDeviceToDevice, st);
     } else if (feed.kind == FEED_RGBE) {
       // quads -> floats, as the samples below: into the plane, or into the dense buffer the edit reads
       eu_rgbe_decode_params d {};
       d.src = static_cast<const uint32_t *>(src);
-      d.table = feed.rgbe_table ? reinterpret_cast<const float *>(block.p) : nullptr;
-      d.dst = feed.alter ? staged.p : dst;
+      d.table = feed.rgbe_table ? tab : nullptr;
+      d.dst = feed.alter ? staged : dst;
       d.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
       d.w = w; d.h = h; d.nch = feed.alter ? src_ch : nch;
-      if (eu_launch_rgbe_decode(&d, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
-      if (feed.alter) p.src = staged.p;
+      if (eu_launch_rgbe_decode(&d, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged;
+    } else if (feed.kind == FEED_YCBCR) {
+      // planes -> floats, as the quads above
+      const eu_ycbcr &y = *feed.ycc;
+      yd.tables = tab;
+      yd.dst = feed.alter ? staged : dst;
+      yd.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
+      yd.w = w; yd.h = h; yd.nch = feed.alter ? src_ch : nch;
+      yd.bits = y.bits; yd.c_step = y.c_step; yd.sub_x = y.sub_x; yd.sub_y = y.sub_y;
+      yd.m_rv = y.m_rv; yd.m_gu = y.m_gu; yd.m_gv = y.m_gv; yd.m_bu = y.m_bu;
+      if (eu_launch_ycbcr_decode(&yd, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged;
     } else {
       // samples -> floats: straight into the plane, or into the dense buffer the edit reads as it reads
       // pixels_on_device input (the channel a facet gains is then the edit's work)
       eu_decode_params d {};
-      d.src = src; d.tables = reinterpret_cast<const float *>(block.p);
-      d.dst = feed.alter ? staged.p : dst;
+      d.src = src; d.tables = tab;
+      d.dst = feed.alter ? staged : dst;
       d.dst_pitch = feed.alter ? size_t(w) : dst_pitch;
       d.w = w; d.h = h; d.bits = feed.smp->bits; d.big_endian = feed.smp->big_endian != 0;
       d.nch = feed.alter ? src_ch : nch; d.src_ch = src_ch;
-      if (eu_launch_decode(&d, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
-      if (feed.alter) p.src = staged.p;
+      if (eu_launch_decode(&d, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (feed.alter) p.src = staged;
     }
     if (feed.alter && !prc) {
       prc = upload_alpha_plan(feed.edit, w, h, &p);
-      if (!prc && eu_launch_facet_alpha(&p, cur().stream)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+      if (!prc && eu_launch_facet_alpha(&p, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
     }
   }
   // the finish: the IR image of a cubemap from its faces, or prefilter + brace of the container (a core narrower
   // than the spline's frame on an axis is braced slice by slice in zimt's order, eu_setup.hip: brace_seq_kernel)
   if (e == hipSuccess && !prc)
-    rc = cube ? eu_launch_cubemap_build(faces.p, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
-                                        m.refc_md, m.model_to_px, prefilter_degree, iir_stream, cur().stream)
-              : eu_launch_prefilter(s->dev, &s->geom, nch, bc0, bc1, prefilter_degree, full_sphere(fct), iir_stream, cur().stream);
-  const hipError_t e2 = hipStreamSynchronize(cur().stream);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess || rc || prc) {
-    destroy_source(s);
-    if (prc) return prc;           // the plan's upload or a kernel launch: the message is set
-    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
-    return fail(rc, "device set-up stage failed");
-  }
+    rc = cube ? eu_launch_cubemap_build(faces, s->dev, nch, m.face_px, m.section_px, m.left_frame_px, m.right_frame_px,
+                                        m.refc_md, m.model_to_px, prefilter_degree, iir_stream, st)
+              // (a load's full sphere is always PERIODIC - source_bcs; the second condition is there for a source that
+              // eu_hip_source_adopt made with other boundary conditions, which a refill keeps)
+              : eu_launch_prefilter(s->dev, &s->geom, nch, s->bc[0], s->bc[1], prefilter_degree,
+                                    full_sphere(fct) && s->bc[0] == EU_BC_PERIODIC, iir_stream, st);
+  return { e, rc, prc };
+}
+
+// the precedence of a fill's errors: the plan's upload or a kernel launch (the message is set), the HIP error, the finish
+int fill_status(const fill_result &r, hipError_t e2)
+{
+  const hipError_t e = r.e != hipSuccess ? r.e : e2;
+  if (r.prc) return r.prc;
+  if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e));
+  if (r.rc) return fail(r.rc, "device set-up stage failed");
+  return EU_OK;
+}
+
+int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
+                const load_feed &feed, eu_source **out)
+{
+  int rc, bc0, bc1;
+  source_bcs(fct, &bc0, &bc1);
+  eu_source *s = nullptr;
+  if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  fill_scratch sc(false);            // freed by scope, after the synchronisation
+  const fill_result r = fill_source(s, prefilter_degree, feed, cur().stream, sc);
+  rc = fill_status(r, hipStreamSynchronize(cur().stream));
+  if (rc) { destroy_source(s); return rc; }
   *out = s;
+  return EU_OK;
+}
+
+// ---- what the feeds' entry points refuse, for a load and for a reload alike (`who` names the entry point) ----------
+
+// *ed: the edit as given, with the samples' channel count in place of its own; *edited: masks or a crop
+int check_samples_feed(const std::string &who, int nch, const eu_samples *smp, const eu_facet_edit *edit,
+                       eu_facet_edit *ed, bool *edited)
+{
+  int rc;
+  if (smp->bits != 8 && smp->bits != 16) return fail(EU_ERR_ARGUMENT, who + ": bits must be 8 or 16");
+  if (!smp->colour_table) return fail(EU_ERR_ARGUMENT, who + ": null colour table");
+  *ed = eu_facet_edit {};
+  if (edit) *ed = *edit;
+  ed->pixel_channels = smp->pixel_channels;
+  ed->pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(ed, nch, who.c_str(), &asked))) return rc;
+  if (smp->on_device && smp->bits == 16 && reinterpret_cast<uintptr_t>(smp->data) % 2)
+    return fail(EU_ERR_ARGUMENT, who + ": 16-bit samples on the device lie at an even address");
+  *edited = ed->npolygons > 0 || ed->crop_kind != 0;     // the alpha plane is wanted, not only the new channel
+  return EU_OK;
+}
+
+// the same for quads: three channels in place of the edit's own
+int check_rgbe_feed(const std::string &who, int nch, const eu_rgbe *px, const eu_facet_edit *edit, eu_facet_edit *ed,
+                    bool *edited)
+{
+  int rc;
+  if (nch != 3 && nch != 4)
+    return fail(EU_ERR_ARGUMENT, who + ": a facet of RGBE pixels has 3 channels, or 4 where it gains alpha");
+  *ed = eu_facet_edit {};
+  if (edit) *ed = *edit;
+  ed->pixel_channels = 3;
+  ed->pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(ed, nch, who.c_str(), &asked))) return rc;
+  if (px->on_device && reinterpret_cast<uintptr_t>(px->data) % 4)
+    return fail(EU_ERR_ARGUMENT, who + ": quads on the device lie on a 4-byte boundary");
+  *edited = ed->npolygons > 0 || ed->crop_kind != 0;
+  return EU_OK;
+}
+
+// the planes of a w x h frame, whatever is done with them (eu_hip_ycbcr_floats too)
+int check_ycbcr_planes(const std::string &who, const eu_ycbcr *px, int w, int h)
+{
+  if (!px) return fail(EU_ERR_ARGUMENT, who + ": null ycbcr");
+  if (!px->y || !px->cb || !px->cr) return fail(EU_ERR_ARGUMENT, who + ": null plane (y, cb, cr)");
+  if (!px->y_table || !px->c_table) return fail(EU_ERR_ARGUMENT, who + ": null table (y_table, c_table)");
+  if (px->bits != 8 && px->bits != 16) return fail(EU_ERR_ARGUMENT, who + ": bits must be 8 or 16");
+  if (px->c_step != 1 && px->c_step != 2) return fail(EU_ERR_ARGUMENT, who + ": c_step must be 1 or 2");
+  if (px->sub_x != 1 && px->sub_x != 2) return fail(EU_ERR_ARGUMENT, who + ": sub_x must be 1 or 2");
+  if (px->sub_y != 1 && px->sub_y != 2) return fail(EU_ERR_ARGUMENT, who + ": sub_y must be 1 or 2");
+  if (w <= 0 || h <= 0) return fail(EU_ERR_ARGUMENT, who + ": empty frame (width, height)");
+  const size_t sb = size_t(px->bits / 8), cw = (size_t(w) + px->sub_x - 1) / px->sub_x;
+  if (px->y_pitch < size_t(w) * sb) return fail(EU_ERR_ARGUMENT, who + ": y_pitch shorter than a row of luma samples");
+  if (px->c_pitch < ((cw - 1) * px->c_step + 1) * sb)
+    return fail(EU_ERR_ARGUMENT, who + ": c_pitch shorter than a row of chroma samples");
+  if (px->bits == 16 && ((reinterpret_cast<uintptr_t>(px->y) | reinterpret_cast<uintptr_t>(px->cb) |
+                          reinterpret_cast<uintptr_t>(px->cr)) & 1))
+    return fail(EU_ERR_ARGUMENT, who + ": 16-bit planes (y, cb, cr) lie at even addresses");
+  if (px->bits == 16 && ((px->y_pitch | px->c_pitch) & 1))
+    return fail(EU_ERR_ARGUMENT, who + ": 16-bit planes have even pitches (y_pitch, c_pitch)");
+  return EU_OK;
+}
+
+// the frame a facet's container takes: its window, or the stack of a cubemap's six faces
+void facet_frame(const eu_facet *f, int *w, int *h)
+{
+  const bool cube = eu_cube_source(f->projection);
+  *w = cube ? f->width : f->window_width;
+  *h = cube ? 6 * f->width : f->window_height;
+}
+
+int check_ycbcr_feed(const std::string &who, const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit,
+                     eu_facet_edit *ed, bool *edited)
+{
+  int rc, w, h;
+  if (fct->nchannels != 3 && fct->nchannels != 4)
+    return fail(EU_ERR_ARGUMENT, who + ": a facet of YCbCr pixels has 3 channels (nchannels), or 4 where it gains alpha");
+  facet_frame(fct, &w, &h);
+  if ((rc = check_ycbcr_planes(who, px, w, h))) return rc;
+  *ed = eu_facet_edit {};
+  if (edit) *ed = *edit;
+  ed->pixel_channels = 3;
+  ed->pixels_on_device = 0;
+  bool asked;
+  if ((rc = check_edit(ed, fct->nchannels, who.c_str(), &asked))) return rc;
+  *edited = ed->npolygons > 0 || ed->crop_kind != 0;
   return EU_OK;
 }
 
@@ -444,7 +671,7 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if (!pixels || !out) return fail(EU_ERR_ARGUMENT, "null argument");
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
-  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr, nullptr };
+  const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr, nullptr, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
@@ -514,7 +741,7 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
     return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
                               tile_size, out);
   if ((rc = ensure_init())) return rc;
-  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr, nullptr };
+  const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr, nullptr, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
@@ -524,23 +751,14 @@ int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const
   int rc;
   if ((rc = check_facet(fct))) return rc;
   if (!smp || !smp->data || !out) return fail(EU_ERR_ARGUMENT, "null argument");
-  if (smp->bits != 8 && smp->bits != 16) return fail(EU_ERR_ARGUMENT, "source_load_samples: bits must be 8 or 16");
-  if (!smp->colour_table) return fail(EU_ERR_ARGUMENT, "source_load_samples: null colour table");
-  // the edit as given, with the samples' channel count in place of its own
-  eu_facet_edit ed {};
-  if (edit) ed = *edit;
-  ed.pixel_channels = smp->pixel_channels;
-  ed.pixels_on_device = 0;
-  bool asked;
-  if ((rc = check_edit(&ed, fct->nchannels, "source_load_samples", &asked))) return rc;
-  if (smp->on_device && smp->bits == 16 && reinterpret_cast<uintptr_t>(smp->data) % 2)
-    return fail(EU_ERR_ARGUMENT, "source_load_samples: 16-bit samples on the device lie at an even address");
+  eu_facet_edit ed;
+  bool edited;
+  if ((rc = check_samples_feed("source_load_samples", fct->nchannels, smp, edit, &ed, &edited))) return rc;
   if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
-  const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
-  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp, nullptr };
+  const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp, nullptr, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
 }
 
@@ -550,24 +768,159 @@ int eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_fac
   int rc;
   if ((rc = check_facet(fct))) return rc;
   if (!px || !px->data || !out) return fail(EU_ERR_ARGUMENT, "null argument");
-  if (fct->nchannels != 3 && fct->nchannels != 4)
-    return fail(EU_ERR_ARGUMENT, "source_load_rgbe: a facet of RGBE pixels has 3 channels, or 4 where it gains alpha");
-  // the edit as given, with the three channels of a quad in place of its own
-  eu_facet_edit ed {};
-  if (edit) ed = *edit;
-  ed.pixel_channels = 3;
-  ed.pixels_on_device = 0;
-  bool asked;
-  if ((rc = check_edit(&ed, fct->nchannels, "source_load_rgbe", &asked))) return rc;
-  if (px->on_device && reinterpret_cast<uintptr_t>(px->data) % 4)
-    return fail(EU_ERR_ARGUMENT, "source_load_rgbe: quads on the device lie on a 4-byte boundary");
+  eu_facet_edit ed;
+  bool edited;
+  if ((rc = check_rgbe_feed("source_load_rgbe", fct->nchannels, px, edit, &ed, &edited))) return rc;
   if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
-  const bool edited = ed.npolygons > 0 || ed.crop_kind != 0;     // the alpha plane is wanted, not only the new channel
-  const load_feed feed { FEED_RGBE, "source_load_rgbe", px->data, px->on_device != 0, 3, &ed, edited, nullptr, px->colour_table };
+  const load_feed feed { FEED_RGBE, "source_load_rgbe", px->data, px->on_device != 0, 3, &ed, edited, nullptr, px->colour_table, nullptr };
   return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_source_load_ycbcr(const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit, int spline_degree,
+                             int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!px || !out) return fail(EU_ERR_ARGUMENT, "null argument");
+  eu_facet_edit ed;
+  bool edited;
+  if ((rc = check_ycbcr_feed("source_load_ycbcr", fct, px, edit, &ed, &edited))) return rc;
+  if (spline_degree < 0 || spline_degree > EU_MAX_DEGREE) return fail(EU_ERR_ARGUMENT, "spline degree out of range");
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
+  if ((rc = ensure_init())) return rc;
+  const load_feed feed { FEED_YCBCR, "source_load_ycbcr", px->y, px->on_device != 0, 3, &ed, edited, nullptr, nullptr, px };
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+}
+
+int eu_hip_ycbcr_floats(const eu_ycbcr *px, int width, int height, int nchannels, float *out)
+{
+  int rc;
+  if ((rc = check_ycbcr_planes("ycbcr_floats", px, width, height))) return rc;
+  if (nchannels != 3 && nchannels != 4) return fail(EU_ERR_ARGUMENT, "ycbcr_floats: nchannels must be 3 or 4");
+  if (!out) return fail(EU_ERR_ARGUMENT, "ycbcr_floats: null out");
+  if (px->on_device) return fail(EU_ERR_ARGUMENT, "ycbcr_floats: a host function, on_device must be 0");
+  eu_ycbcr_rows(px->y, px->cb, px->cr, px->y_pitch, px->c_pitch, px->c_step, px->sub_x, px->sub_y, px->bits, px->y_table,
+                px->c_table, px->m_rv, px->m_gu, px->m_gv, px->m_bu, width, height, nchannels, out);
+  return EU_OK;
+}
+
+// New pixels into a resident container: fill_source without new_source. Stream order ("A source refilled
+// in place"): `st` goes behind the renders that read the container, behind earlier reloads of it and of the scratch,
+// and behind the library's own stream; behind the call stands `written` (and reload.readers) on a caller's stream,
+// own_written on the library's own.
+int eu_hip_source_reload(eu_source *src, const eu_pixels *px, int prefilter_degree, void *stream)
+{
+  int rc;
+  if (!src) return fail(EU_ERR_HANDLE, "source_reload: null source (src)");
+  if (src->is_replica) return fail(EU_ERR_HANDLE, "source_reload: src is a copy on another device slot (is_replica): reload the original");
+  if (!px) return fail(EU_ERR_ARGUMENT, "source_reload: null pixels (px)");
+  const eu_facet *fct = &src->fct;
+  const int nch = src->nch;
+  eu_facet_edit ed {};
+  bool edited = false;
+  load_feed feed { FEED_HOST_FLOATS, "source_reload", nullptr, false, nch, nullptr, false, nullptr, nullptr, nullptr };
+  switch (px->kind) {
+    case EU_PX_FLOATS: {
+      if (!px->floats) return fail(EU_ERR_ARGUMENT, "source_reload: null floats");
+      if (px->edit) ed = *px->edit;
+      ed.pixel_channels = px->pixel_channels;
+      ed.pixels_on_device = px->on_device;
+      bool asked;
+      if ((rc = check_edit(&ed, nch, "source_reload", &asked))) return rc;
+      feed.data = px->floats; feed.on_device = px->on_device != 0; feed.src_ch = px->pixel_channels;
+      if (asked || feed.on_device) { feed.kind = FEED_EDITED_FLOATS; feed.edit = &ed; feed.alter = asked; }
+      edited = asked;
+      break;
+    }
+    case EU_PX_SAMPLES:
+      if (!px->samples) return fail(EU_ERR_ARGUMENT, "source_reload: kind EU_PX_SAMPLES without samples");
+      if (!px->samples->data) return fail(EU_ERR_ARGUMENT, "source_reload: null samples->data");
+      if ((rc = check_samples_feed("source_reload", nch, px->samples, px->edit, &ed, &edited))) return rc;
+      feed = load_feed { FEED_SAMPLES, "source_reload", px->samples->data, px->samples->on_device != 0,
+                         px->samples->pixel_channels, &ed, edited, px->samples, nullptr, nullptr };
+      break;
+    case EU_PX_RGBE:
+      if (!px->rgbe) return fail(EU_ERR_ARGUMENT, "source_reload: kind EU_PX_RGBE without rgbe");
+      if (!px->rgbe->data) return fail(EU_ERR_ARGUMENT, "source_reload: null rgbe->data");
+      if ((rc = check_rgbe_feed("source_reload", nch, px->rgbe, px->edit, &ed, &edited))) return rc;
+      feed = load_feed { FEED_RGBE, "source_reload", px->rgbe->data, px->rgbe->on_device != 0, 3, &ed, edited, nullptr,
+                         px->rgbe->colour_table, nullptr };
+      break;
+    case EU_PX_YCBCR:
+      if (!px->ycbcr) return fail(EU_ERR_ARGUMENT, "source_reload: kind EU_PX_YCBCR without ycbcr");
+      if ((rc = check_ycbcr_feed("source_reload", fct, px->ycbcr, px->edit, &ed, &edited))) return rc;
+      feed = load_feed { FEED_YCBCR, "source_reload", px->ycbcr->y, px->ycbcr->on_device != 0, 3, &ed, edited, nullptr,
+                         nullptr, px->ycbcr };
+      break;
+    default:
+      return fail(EU_ERR_ARGUMENT, "source_reload: unknown kind");
+  }
+  if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
+    return fail(EU_ERR_ARGUMENT, "source_reload: prefilter degree out of range (prefilter_degree)");
+  if ((rc = ensure_init())) return rc;
+  if (!src->dev) return fail(EU_ERR_HANDLE, "source_reload: the source has no container (src)");
+  if (src->slot != cur_slot_) return fail(EU_ERR_HANDLE, "source_reload: the source lives on another device slot (src)");
+  // copies on other device slots: their renders are through (eu_hip_render_devices waits for every slot); they go,
+  // and eu_hip_render_devices makes them again from the new content
+  for (int k = 0; k < EU_MAX_SLOTS; k++)
+    if (src->replica[k]) {
+      if (ctx_[k].stream) {
+        const int back = cur_slot_;
+        if ((rc = set_slot(k))) return rc;
+        const hipError_t es = hipStreamSynchronize(cur().stream);
+        if ((rc = set_slot(back))) return rc;
+        if (es != hipSuccess) return fail(EU_ERR_NO_DEVICE, std::string("source_reload: replica: ") + hipGetErrorString(es));
+      }
+      destroy_source(src->replica[k]);
+      src->replica[k] = nullptr;
+    }
+  context &c = cur();
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  // behind everything that reads or wrote the container and the scratch
+  HIPCHK(src->readers.order_after(st));
+  HIPCHK(src->written.order_after(st));
+  HIPCHK(c.reload.readers.order_after(st));
+  if (stream) {
+    // the library's own stream leaves no event of its own accord: a mark on it, which `st` waits for - not the host
+    HIPCHK(c.reload.own.note(c.stream));
+    HIPCHK(c.reload.own.order_after(st));
+  }
+  fill_scratch sc(true);
+  const fill_result r = fill_source(src, prefilter_degree, feed, st, sc);
+  // host pixels must not be read after the call, an edit's plan is the next edit's to rewrite, and a failure is
+  // reported when it has happened: those calls wait. Device pixels without masks or a crop stay queued.
+  const bool wait = !feed.on_device || feed.alter || r.e != hipSuccess || r.rc || r.prc;
+  rc = fill_status(r, wait ? hipStreamSynchronize(st) : hipSuccess);
+  if (stream) {
+    rc = note_caller(src->written, stream, rc);
+    rc = note_caller(c.reload.readers, stream, rc);
+  } else if (!wait) src->own_written = true;
+  if (rc) return fail(rc, g_err + " (source_reload: the handle stays valid, the container's content is unspecified)");
+  return EU_OK;
+}
+
+int eu_hip_reload_scratch_release(void)
+{
+  for (int k = 0; k < nslots_; k++) {
+    context &c = ctx_[k];
+    if (c.device < 0) continue;
+    if (!c.reload.tables.dev.p && !c.reload.block.p && !c.reload.staged.p && !c.reload.faces.p) continue;
+    const int back = cur_slot_;
+    int rc;
+    if ((rc = set_slot(k))) return rc;
+    hipError_t e = c.reload.readers.host_wait();
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    auto drop = [&](auto &b) { if (b.p) { const hipError_t f = hipFree(b.p); if (e == hipSuccess) e = f; } b.p = nullptr; b.cap = 0; };
+    drop(c.reload.tables.dev); drop(c.reload.block); drop(c.reload.staged); drop(c.reload.faces);
+    c.reload.tables.host.clear();
+    if ((rc = set_slot(back))) return rc;
+    if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, std::string("reload_scratch_release: ") + hipGetErrorString(e));
+  }
+  return EU_OK;
 }
 
 int eu_hip_source_alloc(const eu_facet *fct, int spline_degree, int support_min, int tile_size,
@@ -615,6 +968,9 @@ int eu_hip_source_download(const eu_source *src, float *container, size_t nfloat
 {
   if (!src || !container) return fail(EU_ERR_HANDLE, "null argument");
   if (nfloats != src->nfloats) return fail(EU_ERR_ARGUMENT, "container size mismatch");
+  // a reload may still be filling the container, on a caller's stream or on the library's own: the handle alone is safe
+  HIPCHK(src->written.host_wait());
+  if (src->own_written) HIPCHK(hipStreamSynchronize(ctx_[src->slot].stream));
   HIPCHK(hipMemcpy(container, src->dev, nfloats * sizeof(float), hipMemcpyDeviceToHost));
   return EU_OK;
 }
@@ -630,6 +986,9 @@ int eu_hip_source_info(const eu_source *src, eu_container *geom, int *nch)
 int eu_hip_source_release(eu_source *src)
 {
   if (!src) return EU_OK;
+  // whoever still reads or refills the container on a caller's stream is waited for by the events it left (hipFree
+  // waits for the device as well; this says so)
+  if (src->dev) { (void)src->readers.host_wait(); (void)src->written.host_wait(); }
   for (int k = 0; k < EU_MAX_SLOTS; k++) destroy_source(src->replica[k]);
   destroy_source(src);
   return EU_OK;
@@ -647,6 +1006,15 @@ int eu_hip_diag_host_source(const eu_facet *fct, int spline_degree, eu_source **
   if (!s) return fail(EU_ERR_MEMORY, "host allocation failed");
   *out = s;
   return EU_OK;
+}
+
+// DIAGNOSTIC (not declared in eu_hip.h): the same handle marked as a copy on another device slot, which only
+// eu_hip_render_devices makes - so that what the entry points refuse of such a handle can be exercised without a device
+int eu_hip_diag_host_replica(const eu_facet *fct, int spline_degree, eu_source **out)
+{
+  const int rc = eu_hip_diag_host_source(fct, spline_degree, out);
+  if (rc == EU_OK) (*out)->is_replica = true;
+  return rc;
 }
 
 // DIAGNOSTIC (not in eu_hip.h): the ray -> source coordinate stage of the kernels on

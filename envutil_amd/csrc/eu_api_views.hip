@@ -161,6 +161,7 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   HIPCHK(cur().views.col.reserve(col_floats * per_chunk));
   HIPCHK(cur().views.row.reserve(row_floats * per_chunk));
   if (!out_on_device) HIPCHK(cur().views.stage.reserve((size_t)per_chunk * frame_bytes / sizeof(float)));
+  if ((rc = order_sources(srcs, nsrc, st))) return rc;      // behind a reload of a source
   // the one host synchronisation of the call: the scalar blocks, the facets, and a new tap table, in flight from host vectors
   HIPCHK(cur().views.scal.reserve(sc.size()));
   if (multi) HIPCHK(cur().views.src.reserve(sd.size()));
@@ -191,7 +192,7 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   }
   if (!out_on_device) HIPCHK(hipStreamSynchronize(st));
   drain_on_exit.on = false;          // a device output stays queued: `st` goes on reading the view buffers
-  return note_caller(cur().views.readers, out_on_device ? stream : nullptr, EU_OK);
+  return note_readers(cur().views.readers, srcs, nsrc, out_on_device ? stream : nullptr, EU_OK);
 }
 
 extern "C" {

@@ -30,6 +30,14 @@ struct eu_source {
   int slot = 0;
   eu_source *replica[EU_MAX_SLOTS] = {};
   bool is_replica = false;
+  // what the container was built with, for eu_hip_source_reload (a cubemap's metrics follow from them)
+  int support_min = 0, tile_size = 0;
+  // the container can be refilled in place (eu_hip_source_reload), so it is guarded like the library's own buffers:
+  // `readers` is noted behind every job that leaves work reading it on a caller's stream, `written` behind a reload
+  // on a caller's stream; own_written: a reload is queued on the library's own stream, which leaves no event, and no
+  // caller's stream has waited for it since. Copies on other slots have neither: they are dropped by a reload.
+  eu_readers readers, written;
+  bool own_written = false;
 };
 
 namespace eu_host __attribute__((visibility("hidden"))) {
@@ -152,6 +160,16 @@ struct context {
     eu_dev_buf<int32_t> plan;                     // row plan of the last device alpha edit
     eu_readers readers;
   } alpha;
+  // eu_hip_source_reload: what a load frees by scope stays here and serves the next reload - the feed's tables (with
+  // their host copy: equal tables are not sent again), the bytes of a host image, the dense buffer in front of an
+  // edit and the six faces of a cubemap
+  struct {
+    held_table tables;
+    eu_dev_buf<char> block;
+    eu_dev_buf<float> staged, faces;
+    eu_readers readers;                           // all of them: behind every reload on a caller's stream
+    eu_readers own;                               // a mark on the library's own stream, for a caller's stream to wait for
+  } reload;
   // the way out of a frame: nothing here is read after the call that used it but scr, which `tables` guards
   struct {
     eu_dev_buf<float> stage;                      // host-output staging
@@ -177,6 +195,28 @@ inline int note_caller(eu_readers &r, void *stream, int rc)
 {
   const hipError_t e = stream ? r.note((hipStream_t)stream) : hipSuccess;
   return rc || e == hipSuccess ? rc : fail(EU_ERR_NO_DEVICE, std::string("stream order: ") + hipGetErrorString(e));
+}
+
+// Sources as a job's input. Before the job's first launch: `st` goes behind every reload of one of them - on a
+// caller's stream by the event it left, on the library's own stream by handle.
+inline int order_sources(eu_source *const *srcs, int nsrc, hipStream_t st)
+{
+  for (int f = 0; f < nsrc; f++) {
+    eu_source *s = srcs[f];
+    if (!s) continue;
+    if (s->own_written && st != cur().stream) { HIPCHK(hipStreamSynchronize(cur().stream)); s->own_written = false; }
+    HIPCHK(s->written.order_after(st));
+  }
+  return EU_OK;
+}
+// The end of such a job with result `rc`, where note_caller stands for the library's buffers `r`: the sources too
+// note that a caller's stream may still read them.
+inline int note_readers(eu_readers &r, eu_source *const *srcs, int nsrc, void *stream, int rc)
+{
+  rc = note_caller(r, stream, rc);
+  for (int f = 0; stream && f < nsrc; f++)
+    if (srcs[f]) rc = note_caller(srcs[f]->readers, stream, rc);
+  return rc;
 }
 
 // whatever happens after this, nothing of the call may still use the caller's host memory or a staging buffer when it returns
@@ -207,6 +247,8 @@ inline void destroy_source(eu_source *s)
 {
   if (!s) return;
   if (s->dev) (void)hipFree(s->dev);
+  if (s->readers.ev) (void)hipEventDestroy(s->readers.ev);
+  if (s->written.ev) (void)hipEventDestroy(s->written.ev);
   delete s;
 }
 

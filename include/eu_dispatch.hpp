@@ -108,6 +108,12 @@ struct facet_spec : public facet_base
   // indexed (E << 8) | mantissa for a file whose colour space is not the working one, nullptr for the plain decode.
   const void *rgbe = nullptr;
   const float *rgbe_table = nullptr;
+  // Or as the planes of a Y'CbCr frame (pixels, samples and rgbe nullptr): host planes, tables and matrix of an eu_ycbcr
+  // the caller keeps alive; a facet of 4 channels gains its alpha channel (eu_hip_source_load_ycbcr)
+  const eu_ycbcr *ycbcr = nullptr;
+  // The asset is resident and its picture has changed - the next frame of a sequence: payload() refills the resident
+  // container in place from the feed above (eu_hip_source_reload) where it would otherwise use it as it is
+  bool refill = false;
 };
 
 struct arguments : public facet_base
@@ -150,6 +156,10 @@ struct arguments : public facet_base
   // 3-channel image instead of a stepper's - x, y, z in the facet's frame, used as given (eu_hip_render_rays);
   // the output has the map's size. p_ray_map: ray_map_width x ray_map_height x 3 floats, caller-owned.
   std::string ray_map;
+  // --frames FIRST LAST (-1: none): a sequence rendered through one resident source; --ycbcr_matrix 601 | 709 | 2020
+  // (empty: 709 for heights of 720 and up, else 601) and --ycbcr_range limited | full (empty: what the stream says)
+  int frames_first = -1, frames_last = -1;
+  std::string ycbcr_matrix, ycbcr_range;
   const float *p_ray_map = nullptr;
   int ray_map_width = 0, ray_map_height = 0;
   // --layer IMAGE OUTPUT, repeatable (no counterpart in the reference): further pictures of the single facet's
@@ -290,10 +300,10 @@ struct hip_dispatch : public dispatch_base
     // the facet's source: loaded on first use, resident from then on (asset_handler)
     auto resident_source = [&](const facet_spec &fct) -> int {
       auto it = resident.find(fct.asset_key);
-      if (it == resident.end()) {
+      if (it == resident.end() || fct.refill) {
         eu_facet e = to_eu(fct);
         eu_source *s = nullptr;
-        int rc;
+        int rc = EU_OK;
         // PTO masks and lens crops edit the pixels at load time, as source_t's constructor does
         // (environment.h:700-890) - here on the device, on the way into the container
         const bool edit = (fct.has_pto_mask || fct.has_lens_crop) && !fct.pixels_prepared;
@@ -307,26 +317,52 @@ struct hip_dispatch : public dispatch_base
           ed.crop_x0 = fct.crop_x0; ed.crop_x1 = fct.crop_x1; ed.crop_y0 = fct.crop_y0; ed.crop_y1 = fct.crop_y1;
           ed.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
         }
+        // the feed: what the load calls take, and the same as an eu_pixels for a refill of a resident container
+        const bool refill = it != resident.end();
+        eu_samples sm {};
+        eu_rgbe px {};
+        eu_pixels feed {};
+        feed.edit = edit ? &ed : nullptr;
         if (fct.samples && !fct.pixels) {
           // integer samples: uploaded as they are, decoded on the device through the facet's tables and the same edit
-          eu_samples sm {};
           sm.data = fct.samples; sm.bits = fct.sample_bits; sm.big_endian = fct.samples_big_endian;
           sm.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
           sm.colour_table = fct.colour_table; sm.alpha_table = fct.alpha_table;
-          rc = eu_hip_source_load_samples(&e, &sm, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
-                                          args.support_min, args.tile_size, &s);
+          feed.kind = EU_PX_SAMPLES; feed.samples = &sm;
+          if (!refill)
+            rc = eu_hip_source_load_samples(&e, &sm, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
+                                            args.support_min, args.tile_size, &s);
         } else if (fct.rgbe && !fct.pixels) {
           // Radiance quads: uploaded as they are, decoded on the device, through the same edit
-          eu_rgbe px {};
           px.data = fct.rgbe; px.colour_table = fct.rgbe_table;
-          rc = eu_hip_source_load_rgbe(&e, &px, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
-                                       args.support_min, args.tile_size, &s);
-        } else if (edit) {
-          rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
+          feed.kind = EU_PX_RGBE; feed.rgbe = &px;
+          if (!refill)
+            rc = eu_hip_source_load_rgbe(&e, &px, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
                                          args.support_min, args.tile_size, &s);
+        } else if (fct.ycbcr && !fct.pixels) {
+          // the planes of a video frame: uploaded as their rows lie, decoded on the device, through the same edit
+          feed.kind = EU_PX_YCBCR; feed.ycbcr = fct.ycbcr;
+          if (!refill)
+            rc = eu_hip_source_load_ycbcr(&e, fct.ycbcr, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
+                                          args.support_min, args.tile_size, &s);
         } else {
-          rc = eu_hip_source_load(&e, fct.pixels, args.spline_degree, args.prefilter_degree,
-                                  args.support_min, args.tile_size, &s);
+          feed.kind = EU_PX_FLOATS; feed.floats = fct.pixels;
+          feed.pixel_channels = edit ? ed.pixel_channels : fct.nchannels;
+          if (refill) {}
+          else if (edit)
+            rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
+                                           args.support_min, args.tile_size, &s);
+          else
+            rc = eu_hip_source_load(&e, fct.pixels, args.spline_degree, args.prefilter_degree,
+                                    args.support_min, args.tile_size, &s);
+        }
+        if (refill) {
+          // the next frame of a sequence: the resident container refilled in place, then the facet as ever
+          rc = eu_hip_source_reload(it->second, &feed, args.prefilter_degree, nullptr);
+          if (rc == EU_OK) rc = eu_hip_source_update_facet(it->second, &e);
+          if (rc != EU_OK) return rc;
+          srcs.push_back(it->second);
+          return EU_OK;
         }
         if (rc != EU_OK) return rc;
         it = resident.emplace(fct.asset_key, s).first;

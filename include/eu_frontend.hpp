@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 #include "eu_dispatch.hpp"
+#include "eu_image_io.hpp"
 
 namespace project {
 
@@ -145,7 +146,8 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_precise", 0 }, { "--twine_width", 1 }, { "--twine_density", 1 }, { "--twine_sigma", 1 },
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
-    { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 } };
+    { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 }, { "--frames", 2 }, { "--ycbcr_matrix", 1 },
+    { "--ycbcr_range", 1 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
@@ -161,6 +163,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     else if (key == "--photo") photos.push_back(v[0]);
     else if (key == "--pto_line") addenda.push_back(v[0]);
     else if (key == "--oiio") continue;
+    else if (key == "--frames") { opt["--frames"] = v[0]; opt["--frames LAST"] = v[1]; }
     else opt[key] = it->second ? v[0] : "1";
   }
   auto str = [&](const char *k, const std::string &d) { auto it = opt.find(k); return it == opt.end() ? d : it->second; };
@@ -210,6 +213,27 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   if (a.projection == PRJ_NONE) { err = "unknown projection " + a.projection_str; return false; }
   if (a.pto_file.empty() && addenda.empty() && facets.empty() && photos.empty()) { err = "no facet, photo or PTO input"; return false; }
   if (a.output.empty() && a.split.empty()) { err = "no --output (or --split)"; return false; }
+  // --frames FIRST LAST: a sequence through ONE resident source, its image a numbered series or a .y4m stream. What
+  // the frame loop does not do is refused here, before any file is looked at, each with its own message
+  a.ycbcr_matrix = str("--ycbcr_matrix", "");
+  a.ycbcr_range = str("--ycbcr_range", "");
+  if (!a.ycbcr_matrix.empty() && a.ycbcr_matrix != "601" && a.ycbcr_matrix != "709" && a.ycbcr_matrix != "2020") {
+    err = "--ycbcr_matrix " + a.ycbcr_matrix + ": 601, 709 or 2020";
+    return false;
+  }
+  if (!a.ycbcr_range.empty() && a.ycbcr_range != "limited" && a.ycbcr_range != "full") {
+    err = "--ycbcr_range " + a.ycbcr_range + ": limited or full";
+    return false;
+  }
+  if (has("--frames")) {
+    if (!a.pto_file.empty() || !addenda.empty()) { err = "--frames does not go with --pto / --pto_line: a sequence has one --facet"; return false; }
+    if (facets.size() + photos.size() != 1) { err = "--frames renders the frames of ONE facet: " + std::to_string(facets.size() + photos.size()) + " given"; return false; }
+    if (!layers.empty()) { err = "--frames does not go with --layer"; return false; }
+    if (!a.split.empty()) { err = "--frames does not go with --split"; return false; }
+    if (has("--ray_map")) { err = "--frames does not go with --ray_map"; return false; }
+    if (!io::check_frames(opt["--frames"], opt["--frames LAST"], facets.empty() ? photos[0] : facets[0][0], a.output,
+                          a.frames_first, a.frames_last, err)) return false;
+  }
   bool ignore_p_line = false;
   a.solo = -1;
   if (a.width == 0) a.width = 1024;

@@ -22,7 +22,9 @@
  * render; the stepper tables of a job are uploaded synchronously before its launch. Behind
  * every call that leaves work on a caller's stream the library records an event of its own,
  * and it waits for those events before it rewrites a buffer such work may read, so jobs on
- * different streams never race on the library's own buffers. No stream handle is kept beyond
+ * different streams never race on the library's own buffers, nor on a source's container: every
+ * source notes the renders that read it on a caller's stream, eu_hip_source_reload goes behind
+ * them, and every render goes behind the reloads of its sources. No stream handle is kept beyond
  * the call that brought it: a stream may be destroyed once its own work is done.
  * eu_hip_sync() waits for the library's stream and for everything any call so far has left
  * on a caller's stream.
@@ -318,6 +320,39 @@ typedef struct eu_rgbe {
 } eu_rgbe;
 int  eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
                              int prefilter_degree, int support_min, int tile_size, eu_source **out);
+/* The same container from the planes of a Y'CbCr frame, as video decoders hand it out: planar (I420, I422, I444)
+ * or with interleaved chroma (NV12, P010; NV21 with cb == cr + 1 sample), 8-bit or 16-bit samples. The planes go to
+ * the device as their rows lie (a 2-D copy per plane) or are read where they lie there, and become floats
+ * (eu_ycbcr.hip) on the way into the container. With Y = y_table[y], U = c_table[cb], V = c_table[cr], every product
+ * and every sum a float32 operation rounded on its own (include/eu_ycbcr.h):
+ *   R = Y + m_rv * V        G = (Y + m_gu * U) + m_gv * V        B = Y + m_bu * U
+ * Chroma is replicated, not interpolated. The container is bit for bit the one eu_hip_source_load[_edited] builds
+ * from eu_hip_ycbcr_floats' output with the same edit (edit == NULL: none; edit->pixel_channels and
+ * edit->pixels_on_device are ignored in favour of px). fct->nchannels is 3, or 4: the facet gains alpha = 1.0f here.
+ * The frame has fct->window_width x window_height pixels; cubemaps: width x 6 width, the stack of faces as one image.
+ * Argument errors (EU_ERR_ARGUMENT) are reported before a device is looked for: null planes or tables, bits other
+ * than 8 or 16, c_step, sub_x or sub_y outside {1, 2}, pitches shorter than a row, 16-bit planes or pitches at odd
+ * addresses, nchannels other than 3 or 4, masks or a crop on a facet of 3 channels, degrees out of range. */
+typedef struct eu_ycbcr {
+  const void *y, *cb, *cr;      /* first sample of each plane                                        */
+  size_t y_pitch, c_pitch;      /* BYTES between rows of the luma plane / of both chroma planes       */
+  int32_t c_step;               /* samples from one chroma sample to the next in a row: 1 planar
+                                   (I420, I422, I444), 2 interleaved (NV12: cr == cb + 1 sample)      */
+  int32_t sub_x, sub_y;         /* 1 or 2 each: pixel (x, y) takes chroma sample (x / sub_x, y / sub_y);
+                                   the chroma planes hold ceil(w / sub_x) x ceil(h / sub_y) samples   */
+  int32_t bits;                 /* 8: uint8_t, 16: uint16_t in host order                            */
+  int32_t on_device;            /* all three planes are memory of the library's device               */
+  const float *y_table, *c_table; /* host, 1 << bits floats each: the float a luma / chroma sample
+                                   becomes - range, depth, bit alignment (P010) and the chroma offset
+                                   are the tables' business, the library knows none of them          */
+  float m_rv, m_gu, m_gv, m_bu; /* the matrix                                                         */
+} eu_ycbcr;
+int  eu_hip_source_load_ycbcr(const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit,
+                              int spline_degree, int prefilter_degree, int support_min, int tile_size,
+                              eu_source **out);
+/* HOST function, no device needed: the floats of a width x height frame of host planes, dense rows of nchannels
+ * (3, or 4 with alpha 1.0f) floats - the definition of what eu_hip_source_load_ycbcr loads. px->on_device must be 0. */
+int  eu_hip_ycbcr_floats(const eu_ycbcr *px, int width, int height, int nchannels, float *out);
 /* Adopt an already prefiltered and braced container (host pointer, shape as
  * eu_hip_container_geometry reports; cubemaps: the IR image section_px x
  * 6*section_px). This is what a bound reference hands over when it keeps its
@@ -344,6 +379,36 @@ int  eu_hip_source_download(const eu_source *src, float *container,
                             size_t nfloats);
 int  eu_hip_source_info(const eu_source *src, eu_container *geom, int *nch);
 int  eu_hip_source_release(eu_source *src);
+/* New pixels into a resident container: the second half of a load, without its first. After the call, in stream
+ * order behind it, the container of `src` is bit for bit the one the matching eu_hip_source_load* call builds from
+ * the same pixels for src's facet, degree, support_min and tile_size - core, frame, brace, a cubemap's support frame,
+ * zero slack behind it - whatever stood there before. Geometry, degree, boundary conditions, cube metrics and the
+ * device address stay. Nothing is allocated once the library's reload scratch has reached the feed's size, nothing
+ * is freed, and tables that repeat from call to call are not uploaded again.
+ * `stream` is a hipStream_t (NULL: the library's own); all device work of the call is queued on it, behind every
+ * render that still reads the container on any stream and behind the library's own stream; every later render of
+ * `src`, on any stream, goes behind the reload. With pixel data on the device and no masks or crop the call does not
+ * wait for the device; with host data or an edit it may block as the loads do - rely on neither: eu_hip_sync(), or
+ * synchronising `stream`, says the container is ready. Copies of `src` on other device slots are waited for and
+ * freed; eu_hip_render_devices makes them again on first use.
+ * Refused before a device is looked for, with a message that names the field: a null or replica handle
+ * (EU_ERR_HANDLE), an unknown kind, a missing feed struct, whatever the matching load call refuses, pixels whose
+ * channel count the facet cannot take (EU_ERR_ARGUMENT). A reload that fails on the device leaves the handle valid
+ * and the container's content unspecified. */
+enum { EU_PX_FLOATS = 0, EU_PX_SAMPLES = 1, EU_PX_RGBE = 2, EU_PX_YCBCR = 3 };
+typedef struct eu_pixels {
+  int32_t kind;                 /* EU_PX_* */
+  const void *floats;           /* EU_PX_FLOATS: as eu_hip_source_load[_edited] takes them      */
+  int32_t pixel_channels;       /* EU_PX_FLOATS: the facet's nchannels or one less              */
+  int32_t on_device;            /* EU_PX_FLOATS: `floats` is memory of the library's device     */
+  const eu_samples *samples;    /* EU_PX_SAMPLES */
+  const eu_rgbe *rgbe;          /* EU_PX_RGBE    */
+  const eu_ycbcr *ycbcr;        /* EU_PX_YCBCR   */
+  const eu_facet_edit *edit;    /* masks / crop, or NULL; same rules as the matching load call  */
+} eu_pixels;
+int  eu_hip_source_reload(eu_source *src, const eu_pixels *px, int prefilter_degree, void *stream);
+/* waits for every reload so far and frees the scratch they share ("A source refilled in place") */
+int  eu_hip_reload_scratch_release(void);
 
 /* ---- the hot path --------------------------------------------------------- */
 /* zimt::process(shape, stepper, environment|twine_t, storer): renders rows

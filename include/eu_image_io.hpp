@@ -42,6 +42,11 @@
 // write_rgbe() writes quads that eu_hip_render_rgbe encoded. The two pixel functions are those of eu_rgbe.h, for
 // read_one and write_one and for the device alike.
 //
+// Frames of a video: y4m_reader reads the FRAMEs of a YUV4MPEG2 stream (.y4m) forward, as the planes Y, Cb, Cr that
+// eu_hip_source_load_ycbcr / eu_hip_source_reload take; ycbcr_tables() and ycbcr_matrix() are the float64 expressions
+// of the Python binding's functions of the same names; frame_name() formats a name with exactly one integer
+// conversion, check_frames() is what --frames FIRST LAST asks of its arguments.
+//
 // Header-only, host code, no dependency on the HIP library.
 #ifndef EU_IMAGE_IO_HPP
 #define EU_IMAGE_IO_HPP
@@ -49,6 +54,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -216,11 +222,14 @@ inline bool cubeface_names(const std::string &fmt, std::vector<std::string> &nam
   return true;
 }
 
+inline bool probe_y4m(const std::string &name, int &width, int &height, int &nchannels, std::string &err);   // below
+
 // facet_base::get_image_metrics (envutil_basic.h:546-589): a name with a percent sign is a set
 // of six cube faces and reports the metrics of the first
 inline bool probe(const std::string &name, int &width, int &height, int &nchannels, std::string &err,
                   metadata *meta = nullptr)
 {
+  if (lower_ext(name) == "y4m") return probe_y4m(name, width, height, nchannels, err);
   header h;
   std::vector<std::string> faces;
   const bool series = name.find('%') != std::string::npos;
@@ -794,6 +803,226 @@ inline bool write_rgbe(const std::string &name, const uint8_t *src, int width, i
     return true;
   }
   return write_rgbe_one(name, src, width, height, err, meta);
+}
+
+// ---- frame sequences: numbered names and YUV4MPEG2 streams ---------------------------------------------------------
+
+// the conversions of a name: `ints` counts %[flags][width]d (or i, u), `others` every other '%'
+inline void count_conversions(const std::string &fmt, int &ints, int &others)
+{
+  ints = others = 0;
+  for (size_t i = 0; i < fmt.size(); i++) {
+    if (fmt[i] != '%') continue;
+    size_t k = i + 1;
+    while (k < fmt.size() && (fmt[k] == '0' || fmt[k] == '-' || fmt[k] == '+' || fmt[k] == ' ')) k++;
+    while (k < fmt.size() && fmt[k] >= '0' && fmt[k] <= '9') k++;
+    if (k < fmt.size() && std::strchr("diu", fmt[k]) && k - i <= 8) { ints++; i = k; }
+    else others++;
+  }
+}
+
+// the name of frame k: fmt holds exactly one integer conversion (%d, %04d, ...) and no other '%'
+inline bool frame_name(const std::string &fmt, int k, std::string &out, std::string &err)
+{
+  int ints = 0, others = 0;
+  count_conversions(fmt, ints, others);
+  if (ints != 1 || others != 0) {
+    err = "'" + fmt + "' holds " + (ints == 0 && others == 0 ? std::string("no conversion") : std::to_string(ints + others) + " conversions, " + std::to_string(ints) + " of them for an integer") +
+          ": the name of a frame sequence holds exactly one integer conversion (%d, %04d, ...)";
+    return false;
+  }
+  std::vector<char> buf(fmt.size() + 32);
+  std::snprintf(buf.data(), buf.size(), fmt.c_str(), k);
+  out = buf.data();
+  return true;
+}
+
+// a whole non-negative decimal number
+inline bool frame_number(const std::string &s, int &v)
+{
+  if (s.empty() || s.size() > 9) return false;
+  v = 0;
+  for (char c : s) { if (c < '0' || c > '9') return false; v = v * 10 + (c - '0'); }
+  return true;
+}
+
+// --frames FIRST LAST on the single facet's image `image` with the output `output`: both numbers at least 0 and
+// FIRST <= LAST; the image a .y4m stream or a name with one integer conversion (not the six-file cubemap name, %s);
+// the output a name with one integer conversion
+inline bool check_frames(const std::string &first_s, const std::string &last_s, const std::string &image,
+                         const std::string &output, int &first, int &last, std::string &err)
+{
+  if (!frame_number(first_s, first) || !frame_number(last_s, last)) {
+    err = "--frames FIRST LAST: two whole numbers, both at least 0 ('" + first_s + "', '" + last_s + "')";
+    return false;
+  }
+  if (first > last) { err = "--frames " + first_s + " " + last_s + ": FIRST is beyond LAST"; return false; }
+  std::string name;
+  if (lower_ext(image) != "y4m") {
+    if (image.find("%s") != std::string::npos) { err = "--frames: '" + image + "' names the six files of a cubemap (%s): a frame sequence is one file per frame"; return false; }
+    if (!frame_name(image, first, name, err)) { err = "--frames: the facet's image " + err; return false; }
+  }
+  if (!frame_name(output, first, name, err)) { err = "--frames: --output " + err; return false; }
+  return true;
+}
+
+// What a YUV4MPEG2 header says of its frames. Colour tags: C420, C420jpeg, C420mpeg2, C420paldv (4:2:0; the tags differ
+// in chroma siting, which replication does not read), C422, C444 - 8 bit - and C420p10 / p12 / p16, C422p10 / ..,
+// C444p10 / ..: 16-bit little-endian words with the code in the low bits. No tag: C420jpeg, as the format's tools
+// assume. Cmono, the alpha variants and everything else are refused. XCOLORRANGE=FULL: full range.
+struct y4m_info
+{
+  int width = 0, height = 0;
+  int sub_x = 2, sub_y = 2;
+  int bits = 8, depth = 8;         // bits of a stored sample (8 or 16), significant bits
+  bool full_range = false;
+  size_t y_bytes = 0, c_bytes = 0; // of the luma plane, of ONE chroma plane
+  size_t frame_bytes() const { return y_bytes + 2 * c_bytes; }
+};
+
+inline bool y4m_colour_tag(const std::string &tag, y4m_info &info, std::string &err)
+{
+  std::string base = tag;
+  int depth = 8;
+  const size_t p = tag.rfind('p');
+  if (p != std::string::npos && p > 0 && (tag.substr(p) == "p10" || tag.substr(p) == "p12" || tag.substr(p) == "p16")) {
+    base = tag.substr(0, p);
+    depth = std::atoi(tag.c_str() + p + 1);
+    if (base != "420" && base != "422" && base != "444") base = "?";     // C420jpegp10 and the like do not exist
+  }
+  if (base == "420" || (depth == 8 && (base == "420jpeg" || base == "420mpeg2" || base == "420paldv"))) { info.sub_x = 2; info.sub_y = 2; }
+  else if (base == "422") { info.sub_x = 2; info.sub_y = 1; }
+  else if (base == "444") { info.sub_x = 1; info.sub_y = 1; }
+  else {
+    err = "colour tag C" + tag + ": C420, C420jpeg, C420mpeg2, C420paldv, C422, C444 and the p10, p12, p16 forms of C420, C422, C444 are read" +
+          (tag.compare(0, 4, "mono") == 0 ? " (no chroma planes)" : tag.find("alpha") != std::string::npos ? " (no alpha plane)" : "");
+    return false;
+  }
+  info.depth = depth;
+  info.bits = depth == 8 ? 8 : 16;
+  return true;
+}
+
+// the stream header, one line without its newline: "YUV4MPEG2 W.. H.. [F.. I.. A..] [C..] [X..]"
+inline bool y4m_parse_header(const std::string &line, y4m_info &info, std::string &err)
+{
+  info = y4m_info();
+  if (line.compare(0, 9, "YUV4MPEG2") != 0 || (line.size() > 9 && line[9] != ' ')) { err = "not a YUV4MPEG2 stream"; return false; }
+  std::string tag = "420jpeg";
+  size_t p = 9;
+  while (p < line.size()) {
+    while (p < line.size() && line[p] == ' ') p++;
+    size_t q = line.find(' ', p);
+    if (q == std::string::npos) q = line.size();
+    if (q == p) break;
+    const std::string t = line.substr(p, q - p);
+    p = q;
+    const std::string v = t.substr(1);
+    if (t[0] == 'W' || t[0] == 'H') {
+      int n = 0;
+      if (!frame_number(v, n) || n < 1) { err = "bad frame size '" + t + "'"; return false; }
+      (t[0] == 'W' ? info.width : info.height) = n;
+    } else if (t[0] == 'C') tag = v;
+    else if (t == "XCOLORRANGE=FULL") info.full_range = true;
+  }
+  if (info.width < 1 || info.height < 1) { err = "the stream header gives no frame size (W, H)"; return false; }
+  if (!y4m_colour_tag(tag, info, err)) return false;
+  const size_t sb = size_t(info.bits / 8);
+  const size_t cw = (size_t(info.width) + info.sub_x - 1) / info.sub_x, ch = (size_t(info.height) + info.sub_y - 1) / info.sub_y;
+  info.y_bytes = size_t(info.width) * info.height * sb;
+  info.c_bytes = cw * ch * sb;
+  return true;
+}
+
+// A stream can only be read forward: frame(k) skips the frames in front of frame k and fails for one behind it.
+struct y4m_reader
+{
+  FILE *f = nullptr;
+  y4m_info info;
+  int next = 0;                    // the frame the file position stands in front of
+  std::string name;
+  y4m_reader() = default;
+  y4m_reader(const y4m_reader &) = delete;
+  y4m_reader &operator=(const y4m_reader &) = delete;
+  ~y4m_reader() { if (f) std::fclose(f); }
+
+  static bool line(FILE *f, std::string &s, size_t limit = 4096)
+  {
+    s.clear();
+    int c;
+    while ((c = std::fgetc(f)) != EOF && c != '\n') { if (s.size() >= limit) return false; s += char(c); }
+    return c == '\n';
+  }
+  bool open(const std::string &file, std::string &err)
+  {
+    if (f) { std::fclose(f); f = nullptr; }
+    name = file; next = 0;
+    f = std::fopen(file.c_str(), "rb");
+    if (!f) { err = "cannot open " + file; return false; }
+    std::string h;
+    if (!line(f, h)) { err = file + ": no stream header"; return false; }
+    if (!y4m_parse_header(h, info, err)) { err = file + ": " + err; return false; }
+    return true;
+  }
+  // the planes of frame k - Y, then Cb, then Cr, rows dense - into `planes` (resized to info.frame_bytes())
+  bool frame(int k, std::vector<uint8_t> &planes, std::string &err)
+  {
+    if (!f) { err = name + ": not open"; return false; }
+    if (k < next) { err = name + ": frame " + std::to_string(k) + " lies behind frame " + std::to_string(next) + ": a stream is read forward"; return false; }
+    try { planes.resize(info.frame_bytes()); } catch (const std::exception &) { err = name + ": out of memory"; return false; }
+    for (; next <= k; next++) {
+      std::string h;
+      if (!line(f, h) || h.compare(0, 5, "FRAME") != 0 || (h.size() > 5 && h[5] != ' ')) {
+        err = name + ": frame " + std::to_string(next) + ": " + (h.empty() && std::feof(f) ? "the stream ends in front of it" : "no FRAME header");
+        return false;
+      }
+      if (next < k) {
+        if (std::fseek(f, long(info.frame_bytes()), SEEK_CUR) != 0) { err = name + ": cannot skip frame " + std::to_string(next); return false; }
+      } else if (std::fread(planes.data(), 1, planes.size(), f) != planes.size()) {
+        err = name + ": frame " + std::to_string(k) + " is truncated";
+        return false;
+      }
+    }
+    return true;
+  }
+};
+
+// ycbcr_tables of the Python binding: float32 of a float64 expression of the code c = v. With s = 2^(depth - 8):
+// limited range (c - 16 s) / (219 s) and (c - 128 s) / (224 s), full range c / (2^depth - 1) and (c - 128 s) / (2^depth - 1)
+inline void ycbcr_tables(int bits, int depth, bool full_range, std::vector<float> &y_table, std::vector<float> &c_table)
+{
+  const size_t n = size_t(1) << bits;
+  y_table.resize(n); c_table.resize(n);
+  const double s = std::ldexp(1.0, depth - 8), top = std::ldexp(1.0, depth) - 1.0;
+  for (size_t v = 0; v < n; v++) {
+    const double c = double(v);
+    y_table[v] = float(full_range ? c / top : (c - 16.0 * s) / (219.0 * s));
+    c_table[v] = float(full_range ? (c - 128.0 * s) / top : (c - 128.0 * s) / (224.0 * s));
+  }
+}
+
+// ycbcr_matrix of the Python binding: "601", "709", "2020" -> m_rv, m_gu, m_gv, m_bu
+inline bool ycbcr_matrix(const std::string &name, float m[4], std::string &err)
+{
+  double kr, kb;
+  if (name == "601") { kr = 0.299; kb = 0.114; }
+  else if (name == "709") { kr = 0.2126; kb = 0.0722; }
+  else if (name == "2020") { kr = 0.2627; kb = 0.0593; }
+  else { err = "--ycbcr_matrix " + name + ": 601, 709 or 2020"; return false; }
+  const double kg = 1.0 - kr - kb;
+  m[0] = float(2.0 * (1.0 - kr));
+  m[1] = float(-2.0 * kb * (1.0 - kb) / kg);
+  m[2] = float(-2.0 * kr * (1.0 - kr) / kg);
+  m[3] = float(2.0 * (1.0 - kb));
+  return true;
+}
+
+inline bool probe_y4m(const std::string &name, int &width, int &height, int &nchannels, std::string &err)
+{
+  y4m_reader r;
+  if (!r.open(name, err)) return false;
+  width = r.info.width; height = r.info.height; nchannels = 3;
+  return true;
 }
 
 }  // namespace io

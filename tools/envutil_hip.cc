@@ -20,6 +20,7 @@
 #include <cstring>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 #include "eu_frontend.hpp"
@@ -195,9 +196,14 @@ static int run_payload(const std::string &output)
 static int core(int argc, const char *const *argv, bool pipe_mode = false)
 {
   std::string err;
-  image_probe probe = [&](const std::string &name, image_info &info) {
-    std::string e;
+  // with --frames a numbered name stands for its first frame (init_arguments checks name and numbers before it probes)
+  int probe_frame = -1;
+  for (int i = 1; i + 1 < argc; i++)
+    if (std::string(argv[i]) == "--frames" && !io::frame_number(argv[i + 1], probe_frame)) probe_frame = -1;
+  image_probe probe = [&](const std::string &given, image_info &info) {
+    std::string e, name = given;
     io::metadata m;
+    if (probe_frame >= 0 && io::lower_ext(given) != "y4m" && !io::frame_name(given, probe_frame, name, e)) return false;
     if (!io::probe(name, info.width, info.height, info.nchannels, e, &m)) return false;
     info.projection = m.projection; info.hfov = m.hfov;
     return true;
@@ -220,6 +226,17 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
       return 2;
     }
   }
+  const bool sequence = args.frames_first >= 0;
+  if (sequence) {
+    if (pipe_mode) {
+      std::fprintf(stderr, "envutil_hip: --frames does not go with pipe mode: one call renders the sequence, then the program ends\n");
+      return 2;
+    }
+    if (hip_dispatch::device_slots() > 1) {
+      std::fprintf(stderr, "envutil_hip: --frames renders on one device: set EU_HIP_DEVICES=1 on a host with several\n");
+      return 2;
+    }
+  }
   const auto *dp = static_cast<const hip_dispatch *>(get_dispatch());
   if (args.verbose) std::printf("using %s (%s)\n", dp->hwy_target_name.c_str(), dp->hwy_target_str.c_str());
   if (!args.twine_setup()) {
@@ -234,35 +251,71 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
   const size_t nfct = args.facet_spec_v.size(), nimg = nfct + args.layer_spec_v.size();
   std::vector<std::vector<float>> pixels(nimg), colour_tab(nimg), alpha_tab(nimg);
   std::vector<std::vector<uint8_t>> samples(nimg);
-  for (size_t k = 0; k < nimg; k++) {
-    facet_spec &f = k < nfct ? args.facet_spec_v[k] : args.layer_spec_v[k - nfct];
-    if (k < nfct && args.solo >= 0 && int(k) != args.solo) continue;
-    if (dp->resident.count(f.asset_key)) {
-      if (args.verbose) std::printf("asset %s is already resident\n", f.asset_key.c_str());
-      continue;
+  // ... or - a .y4m stream - the planes of one of its frames, with the tables and the matrix of the Y'CbCr feed
+  std::vector<std::unique_ptr<io::y4m_reader>> streams(nimg);
+  std::vector<eu_ycbcr> ycc(nimg);
+  enum { KIND_FLOATS, KIND_SAMPLES_8, KIND_SAMPLES_16, KIND_RGBE, KIND_YCBCR };
+  static const char *const kind_name[] = { "float pixels", "8-bit samples, decoded on the device", "16-bit samples, decoded on the device",
+                                           "RGBE pixels, decoded on the device", "YCbCr planes, decoded on the device" };
+  // image k's pixels out of `file` (a .y4m stream: its frame `frame`) into the buffers above and into f's feed
+  auto read_pixels = [&](size_t k, facet_spec &f, const std::string &file, int frame, int &kind, int &nch) -> bool {
+    f.pixels = nullptr; f.samples = nullptr; f.rgbe = nullptr; f.rgbe_table = nullptr; f.ycbcr = nullptr;
+    int w = 0, h = 0, maxval = 0, sbits = 0;
+    nch = 0;
+    std::string serr;
+    const bool as_ycbcr = io::lower_ext(file) == "y4m";
+    if (as_ycbcr) {
+      if (!streams[k]) {
+        streams[k].reset(new io::y4m_reader);
+        if (!streams[k]->open(file, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return false; }
+      }
+      io::y4m_reader &r = *streams[k];
+      if (!r.frame(frame, samples[k], err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return false; }
+      const io::y4m_info &yi = r.info;
+      w = yi.width; h = yi.height; nch = 3;
+      if (yi.bits == 16) {                          // the file's words are little-endian, the feed takes host order
+        const uint16_t one = 1;
+        if (!*reinterpret_cast<const uint8_t *>(&one))
+          for (size_t i = 0; i + 1 < samples[k].size(); i += 2) std::swap(samples[k][i], samples[k][i + 1]);
+      }
+      eu_ycbcr &y = ycc[k];
+      if (colour_tab[k].empty()) {
+        const bool full = args.ycbcr_range.empty() ? yi.full_range : args.ycbcr_range == "full";
+        const std::string matrix = !args.ycbcr_matrix.empty() ? args.ycbcr_matrix : h >= 720 ? "709" : "601";
+        io::ycbcr_tables(yi.bits, yi.depth, full, colour_tab[k], alpha_tab[k]);
+        float m[4];
+        if (!io::ycbcr_matrix(matrix, m, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return false; }
+        y = eu_ycbcr {};
+        y.m_rv = m[0]; y.m_gu = m[1]; y.m_gv = m[2]; y.m_bu = m[3];
+        if (args.verbose)
+          std::printf("%s: %d x %d, %d-bit 4:%s, matrix %s, %s range\n", file.c_str(), w, h, yi.depth,
+                      yi.sub_x == 1 ? "4:4" : yi.sub_y == 1 ? "2:2" : "2:0", matrix.c_str(), full ? "full" : "limited");
+      }
+      const size_t sb = size_t(yi.bits / 8), cw = (size_t(w) + yi.sub_x - 1) / yi.sub_x;
+      y.y = samples[k].data(); y.cb = samples[k].data() + yi.y_bytes; y.cr = samples[k].data() + yi.y_bytes + yi.c_bytes;
+      y.y_pitch = size_t(w) * sb; y.c_pitch = cw * sb;
+      y.c_step = 1; y.sub_x = yi.sub_x; y.sub_y = yi.sub_y; y.bits = yi.bits; y.on_device = 0;
+      y.y_table = colour_tab[k].data(); y.c_table = alpha_tab[k].data();
     }
-    f.pixels = nullptr; f.samples = nullptr; f.rgbe = nullptr; f.rgbe_table = nullptr;
-    int w = 0, h = 0, nch = 0, maxval = 0, sbits = 0;
     // an integer file goes up as it is and is widened and linearised on the device; whatever read_samples refuses
     // is left to the float route and to its messages
-    std::string serr;
-    const bool as_samples = io::read_samples(f.filename, samples[k], w, h, nch, maxval, sbits, serr);
+    const bool as_samples = !as_ycbcr && io::read_samples(file, samples[k], w, h, nch, maxval, sbits, serr);
     // ... and so does a Radiance picture, as its quads (they share the byte buffer: a file is one or the other)
-    const bool as_rgbe = !as_samples && io::read_rgbe(f.filename, samples[k], w, h, serr);
+    const bool as_rgbe = !as_ycbcr && !as_samples && io::read_rgbe(file, samples[k], w, h, serr);
     if (as_rgbe) nch = 3;
-    if (!as_samples && !as_rgbe && !io::read_image(f.filename, pixels[k], w, h, nch, err)) {
+    if (!as_ycbcr && !as_samples && !as_rgbe && !io::read_image(file, pixels[k], w, h, nch, err)) {
       std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
-      return 2;
+      return false;
     }
-    if (args.verbose)
-      std::printf("%s: %s\n", f.filename.c_str(), as_samples ? (sbits == 8 ? "8-bit samples, decoded on the device" : "16-bit samples, decoded on the device")
-                                                 : as_rgbe ? "RGBE pixels, decoded on the device" : "float pixels");
+    kind = as_ycbcr ? KIND_YCBCR : as_samples ? (sbits == 8 ? KIND_SAMPLES_8 : KIND_SAMPLES_16) : as_rgbe ? KIND_RGBE : KIND_FLOATS;
+    if (args.verbose) std::printf("%s: %s\n", file.c_str(), kind_name[kind]);
     // read_image_data: from the facet's colour space - Csp clause / --input_colour_space, else what the file's
-    // format says - to the working one (envutil_basic.h:950-977)
-    {
-      const std::string csp = f.colour_space.empty() ? io::file_colour_space(f.filename) : f.colour_space;
+    // format says - to the working one (envutil_basic.h:950-977). A video frame stays in its own non-linear space,
+    // as its tables leave it
+    if (!as_ycbcr) {
+      const std::string csp = f.colour_space.empty() ? io::file_colour_space(file) : f.colour_space;
       if (args.verbose && csp != args.working_colour_space)
-        std::printf("converting %s from %s to %s\n", f.filename.c_str(), csp.c_str(), args.working_colour_space.c_str());
+        std::printf("converting %s from %s to %s\n", file.c_str(), csp.c_str(), args.working_colour_space.c_str());
       io::colour_class ca, cb;
       bool same = false;
       const bool ok = as_samples ? io::sample_tables(sbits, maxval, csp, args.working_colour_space, colour_tab[k], alpha_tab[k], err)
@@ -271,29 +324,80 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
                                 (same || io::rgbe_table(csp, args.working_colour_space, colour_tab[k], err))
                                  : io::convert_colour(pixels[k].data(), size_t(w) * h, nch, csp, args.working_colour_space, err);
       if (!ok) {
-        std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
-        return 2;
+        std::fprintf(stderr, "envutil_hip: %s: %s\n", file.c_str(), err.c_str());
+        return false;
       }
     }
     const bool cube = f.projection == CUBEMAP || f.projection == BIATAN6;
     if (w != f.window_width || (cube ? h != 6 * w : h != f.window_height)) {
-      std::fprintf(stderr, "envutil_hip: %s is %d x %d, expected %d x %d\n", f.filename.c_str(), w, h,
+      std::fprintf(stderr, "envutil_hip: %s is %d x %d, expected %d x %d\n", file.c_str(), w, h,
                    f.window_width, cube ? 6 * f.window_width : f.window_height);
-      return 2;
+      return false;
     }
     // PTO masks and lens crops edit the loaded pixels (environment.h:700-890): the dispatch does that on the
     // device when it loads the facet, from the pixels at the file's own channel count
-    if (!check_facet_pixels(f, as_samples ? samples[k].size() / size_t(sbits / 8) : as_rgbe ? samples[k].size() / 4 * 3 : pixels[k].size(), nch, err)) {
-      std::fprintf(stderr, "envutil_hip: %s: %s\n", f.filename.c_str(), err.c_str());
-      return 2;
+    const size_t count = as_ycbcr ? size_t(w) * h * 3 : as_samples ? samples[k].size() / size_t(sbits / 8) : as_rgbe ? samples[k].size() / 4 * 3 : pixels[k].size();
+    if (!check_facet_pixels(f, count, nch, err)) {
+      std::fprintf(stderr, "envutil_hip: %s: %s\n", file.c_str(), err.c_str());
+      return false;
     }
-    if (as_samples) {
+    if (as_ycbcr) f.ycbcr = &ycc[k];
+    else if (as_samples) {
       f.samples = samples[k].data(); f.sample_bits = sbits; f.samples_big_endian = true;
       f.colour_table = colour_tab[k].data(); f.alpha_table = alpha_tab[k].data();
     } else if (as_rgbe) {
       f.rgbe = samples[k].data();
       f.rgbe_table = colour_tab[k].empty() ? nullptr : colour_tab[k].data();
     } else f.pixels = pixels[k].data();
+    return true;
+  };
+  int first_kind = 0, first_nch = 0;
+  for (size_t k = 0; k < nimg; k++) {
+    facet_spec &f = k < nfct ? args.facet_spec_v[k] : args.layer_spec_v[k - nfct];
+    if (k < nfct && args.solo >= 0 && int(k) != args.solo) continue;
+    if (dp->resident.count(f.asset_key)) {
+      if (args.verbose) std::printf("asset %s is already resident\n", f.asset_key.c_str());
+      continue;
+    }
+    // a sequence begins with its first frame; a .y4m facet without --frames is its frame 0
+    std::string file = f.filename;
+    if (sequence && io::lower_ext(file) != "y4m" && !io::frame_name(f.filename, args.frames_first, file, err)) {
+      std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+      return 2;
+    }
+    if (!read_pixels(k, f, file, sequence ? args.frames_first : 0, first_kind, first_nch)) return 2;
+  }
+
+  // --frames FIRST LAST: the first frame is a load, every later one new pixels into the resident container
+  // (eu_hip_source_reload, through the feed the file's type takes); each frame is rendered and written by the route
+  // the output's type takes - the files of one run per frame
+  if (sequence) {
+    facet_spec &f = args.facet_spec_v[0];
+    const std::string out_format = args.output;
+    for (int k = args.frames_first; k <= args.frames_last; k++) {
+      std::string file = f.filename, out;
+      const bool stream = io::lower_ext(file) == "y4m";
+      if (!stream && !io::frame_name(f.filename, k, file, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 2; }
+      if (!io::frame_name(out_format, k, out, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 2; }
+      if (k > args.frames_first) {
+        int kind = 0, nch = 0;
+        if (!read_pixels(0, f, file, k, kind, nch)) { std::fprintf(stderr, "envutil_hip: frame %d could not be read\n", k); return 2; }
+        if (kind != first_kind || nch != first_nch) {
+          std::fprintf(stderr, "envutil_hip: frame %d (%s) holds %s at %d channels, frame %d %s at %d: the frames of a sequence share size, channels and file type\n",
+                       k, file.c_str(), kind_name[kind], nch, args.frames_first, kind_name[first_kind], first_nch);
+          return 2;
+        }
+        f.refill = true;
+      }
+      if (args.verbose)
+        std::printf("frame %d: %s, %s\n", k, file.c_str(), f.refill ? "eu_hip_source_reload into the resident source" : "loaded as a new source");
+      args.output = out;
+      const int rc = run_payload(out);
+      if (rc) return rc;
+    }
+    f.refill = false;
+    args.output = out_format;
+    return 0;
   }
 
   // --ray_map FILE: a 3-channel PFM of rays in the facet's frame
@@ -355,7 +459,11 @@ int main(int argc, const char **argv)
         "  spline:   --degree D  --prefilter D  --support_min PX  --tile_size PX (cubemap sources)\n"
         "  twining:  --twine N (-1: automatic)  --twine_width F  --twine_density F  --twine_max N\n"
         "            --twine_sigma F  --twine_threshold F  --twine_normalize  --twine_precise  --twf_file FILE\n"
-        "  images:   .pfm .hdr (float), .pgm .ppm .pnm (8 / 16 bit), .pam (8 / 16 bit, alpha); a name with one %s\n"
+        "  frames:   --frames FIRST LAST  a sequence through ONE resident source: the single facet's image and --output hold\n"
+        "            one integer conversion each (%d, %04d, ...), or the image is a .y4m stream (YUV4MPEG2; read forward);\n"
+        "            the first frame is loaded, every later one refills the source in place\n"
+        "            --ycbcr_matrix 601|709|2020 (default: 709 from 720 rows on, else 601)  --ycbcr_range limited|full\n"
+        "  images:   .pfm .hdr (float), .pgm .ppm .pnm (8 / 16 bit), .pam (8 / 16 bit, alpha), .y4m (frame 0 without --frames); a name with one %s\n"
         "            stands for six cube faces: left right top bottom front back\n"
         "            .hdr / .pic and the integer formats go to and from the device as the file's own pixels\n"
         "  -v verbose; a trailing '-' reads one job per line from stdin (sources stay resident in HBM)");
