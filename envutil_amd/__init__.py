@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     encode_samples, render_samples, sample_steps, Encode,
     encode_rgbe, render_rgbe, Rgbe,
     Ycbcr, Pixels, ycbcr_matrix, ycbcr_tables, ycbcr_floats, reload_scratch_release,
+    YcbcrOut, ycbcr_forward, ycbcr_steps, ycbcr_planes, encode_ycbcr, render_ycbcr,
     layout_segments, facet_alpha, facet_alpha_dev, facet_alpha_rows, init_devices, device_slots, device_strips, render_devices,
     SPHERICAL, CYLINDRICAL, RECTILINEAR, STEREOGRAPHIC, FISHEYE, CUBEMAP, BIATAN6,
     BC_MIRROR, BC_PERIODIC, BC_REFLECT, BC_NATURAL, BC_CONSTANT,

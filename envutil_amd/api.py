@@ -156,6 +156,9 @@ def lib():
     L.eu_hip_encode_samples.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, vp, vp, C.c_size_t, i32, vp]
     L.eu_hip_render_rgbe.argtypes = [vp, vp, i32, vp, C.c_size_t, i32, vp]
     L.eu_hip_encode_rgbe.argtypes = [vp, C.c_size_t, i32, i32, i32, vp, C.c_size_t, i32, vp]
+    L.eu_hip_encode_ycbcr.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, vp, vp]
+    L.eu_hip_render_ycbcr.argtypes = [vp, vp, i32, vp, vp]
+    L.eu_hip_ycbcr_planes.argtypes = [vp, C.c_size_t, i32, i32, i32, vp]
     L.eu_hip_init_devices.argtypes = [vp, i32]
     L.eu_hip_render_devices.argtypes = [vp, vp, i32, vp, C.c_size_t, i32]
     L.eu_hip_device_strips.argtypes = [vp, vp, i32, vp, vp]
@@ -275,6 +278,16 @@ class Ycbcr(C.Structure):
                 ("bits", C.c_int32), ("on_device", C.c_int32),
                 ("y_table", C.c_void_p), ("c_table", C.c_void_p),
                 ("m_rv", C.c_float), ("m_gu", C.c_float), ("m_gv", C.c_float), ("m_bu", C.c_float)]
+
+
+class YcbcrOut(C.Structure):
+    """struct eu_ycbcr_out"""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p),
+                ("y_pitch", C.c_size_t), ("c_pitch", C.c_size_t),
+                ("c_step", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32),
+                ("bits", C.c_int32), ("shift", C.c_int32), ("on_device", C.c_int32),
+                ("y_steps", C.c_void_p), ("c_steps", C.c_void_p),
+                ("k_r", C.c_float), ("k_g", C.c_float), ("k_b", C.c_float), ("c_u", C.c_float), ("c_v", C.c_float)]
 
 
 PX_FLOATS, PX_SAMPLES, PX_RGBE, PX_YCBCR = 0, 1, 2, 3
@@ -444,6 +457,207 @@ def ycbcr_floats(y, chroma, matrix, y_table, c_table, nchannels=3):
     out = np.zeros((h, w, nchannels), np.float32)
     _check(lib().eu_hip_ycbcr_floats(C.byref(px), w, h, nchannels, _ptr(out)))
     return out
+
+
+def ycbcr_forward(name):
+    """(k_r, k_g, k_b, c_u, c_v) of BT.601, BT.709 or BT.2020 as float32 of the float64 values Kr, 1 - Kr - Kb, Kb,
+    1 / (2 (1 - Kb)), 1 / (2 (1 - Kr)): the way back from ycbcr_matrix(name)"""
+    if str(name) not in _YCBCR_K:
+        raise EuError(f"ycbcr_forward: {name!r} is none of '601', '709', '2020'")
+    kr, kb = _YCBCR_K[str(name)]
+    return tuple(np.float32(v) for v in (kr, 1.0 - kr - kb, kb, 1.0 / (2.0 * (1.0 - kb)), 1.0 / (2.0 * (1.0 - kr))))
+
+
+def ycbcr_steps(bits, depth=None, full_range=False):
+    """(y_steps, c_steps), 1 << bits float32 each: the step tables (eu_ycbcr_out) of the usual quantiser, the inverse
+    of ycbcr_tables(bits, depth, full_range). steps[k] is the smallest float32 v whose code
+    clip(floor(float64(v) * a + b + 0.5), 0, 2**depth - 1) (NaN: 0) is >= k, found by bisection over the float32 bit
+    patterns with that very expression as sample_steps does; steps[0] is -inf, entries behind 2**depth - 1 are NaN.
+    With s = 2**(depth - 8): limited range a, b = 219 s, 16 s for luma and 224 s, 128 s for chroma; full range
+    2**depth - 1, 0 and 2**depth - 1, 128 s. The codes sit in the LOW bits: a surface with the code in the high bits
+    (P010) takes them with shift = bits - depth."""
+    if bits not in (8, 16):
+        raise EuError("ycbcr_steps: bits is 8 or 16")
+    depth = bits if depth is None else int(depth)
+    if depth < 8 or depth > bits:
+        raise EuError("ycbcr_steps: depth is 8 .. bits")
+    n, top = 1 << bits, (1 << depth) - 1
+    s = 2.0 ** (depth - 8)
+    ab = ((float(top), 0.0), (float(top), 128.0 * s)) if full_range else ((219.0 * s, 16.0 * s), (224.0 * s, 128.0 * s))
+
+    def table(a, b):
+        def q(v):
+            with np.errstate(invalid="ignore", over="ignore"):
+                c = np.floor(v.astype(np.float64) * a + b + 0.5)
+                return np.where(np.isnan(c), 0.0, np.clip(c, 0.0, float(top))).astype(np.uint32)
+
+        want = np.arange(1, top + 1, dtype=np.uint32)
+        lo = np.full(top, _float_keys(np.float32(-np.inf))[()], np.uint64)
+        hi = np.full(top, _float_keys(np.float32(np.inf))[()], np.uint64)
+        while (lo < hi).any():
+            mid = (lo + hi) // 2
+            up = q(_key_floats(mid.astype(np.uint32))) >= want
+            hi = np.where(up, mid, hi)
+            lo = np.where(up, lo, mid + 1)
+        steps = np.full(n, np.nan, np.float32)
+        steps[0] = -np.inf
+        steps[1:top + 1] = _key_floats(lo.astype(np.uint32))
+        return steps
+
+    return table(*ab[0]), table(*ab[1])
+
+
+def _ycbcr_out_planes(who, out, h, w, subsampling, interleaved, bits, like_torch):
+    """(y, chroma) for a frame of h x w pixels: `out` checked against the shapes load_ycbcr takes, or new planes -
+    numpy arrays, or torch tensors on the device of `like_torch`"""
+    sx, sy = (int(v) for v in subsampling)
+    if sx not in (1, 2) or sy not in (1, 2):
+        raise EuError(f"{who}: subsampling is (sub_x, sub_y), 1 or 2 each")
+    if bits not in (8, 16):
+        raise EuError(f"{who}: bits is 8 or 16")
+    ch, cw = (h + sy - 1) // sy, (w + sx - 1) // sx
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise EuError(f"{who}: out is (y, chroma)")
+        y, chroma = out
+    elif like_torch is not None:
+        import torch
+        dt = {8: torch.uint8, 16: torch.uint16}[bits]
+        y = torch.empty((h, w), dtype=dt, device=like_torch.device)
+        chroma = (torch.empty((ch, cw, 2), dtype=dt, device=like_torch.device) if interleaved else
+                  (torch.empty((ch, cw), dtype=dt, device=like_torch.device),
+                   torch.empty((ch, cw), dtype=dt, device=like_torch.device)))
+    else:
+        dt = _SAMPLE_DTYPE[bits]
+        y = np.zeros((h, w), dt)
+        chroma = np.zeros((ch, cw, 2), dt) if interleaved else (np.zeros((ch, cw), dt), np.zeros((ch, cw), dt))
+    if isinstance(chroma, (tuple, list)):
+        if len(chroma) != 2:
+            raise EuError(f"{who}: chroma is a pair (cb, cr) or one (ch, cw, 2) array")
+        cb, cr = chroma
+    else:
+        if chroma.ndim != 3 or chroma.shape[2] != 2:
+            raise EuError(f"{who}: chroma is a pair (cb, cr) or one (ch, cw, 2) array")
+        cb, cr = chroma[:, :, 0], chroma[:, :, 1]
+    if tuple(y.shape) != (h, w) or tuple(cb.shape) != (ch, cw) or tuple(cr.shape) != (ch, cw):
+        raise EuError(f"{who}: the planes of a {w} x {h} frame are ({h}, {w}) luma and ({ch}, {cw}) chroma samples")
+    return y, chroma, cb, cr, sx, sy
+
+
+def _ycbcr_out_struct(who, forward, y, cb, cr, sx, sy, bits, shift, y_steps, c_steps, wait=True):
+    """(eu_ycbcr_out, what it points into) for planes as _ycbcr_out_planes returns them"""
+    on_device = _is_torch(y)
+    ya, yp, ystep, ybits = _plane(y, "y", on_device)
+    ba, bp, bstep, bbits = _plane(cb, "cb", on_device)
+    ra, rp, rstep, rbits = _plane(cr, "cr", on_device)
+    if ystep != 1:
+        raise EuError(f"{who}: the luma samples of a row are contiguous")
+    if (ybits, bbits, rbits) != (bits, bits, bits):
+        raise EuError(f"{who}: the three planes hold uint{bits} samples")
+    ch, cw = cb.shape
+    if y.shape[0] > 1 and ch > 1 and bp != rp:
+        raise EuError(f"{who}: both chroma planes have one row pitch")
+    if cw > 1 and bstep != rstep:
+        raise EuError(f"{who}: both chroma planes have one sample step")
+    if cw > 1:
+        step = bstep
+    else:                               # one sample per row: a pair where cb and cr lie side by side in a row
+        step = 2 if abs(ra - ba) == bits // 8 and (ch == 1 or min(bp, rp) >= bits // 4) else 1
+    if y_steps is None or c_steps is None:
+        dy, dc = ycbcr_steps(bits, bits - int(shift) if 0 <= int(shift) <= bits - 8 else None)
+        y_steps = dy if y_steps is None else y_steps
+        c_steps = dc if c_steps is None else c_steps
+    y_steps = np.ascontiguousarray(y_steps, np.float32)
+    c_steps = np.ascontiguousarray(c_steps, np.float32)
+    if y_steps.shape != (1 << bits,) or c_steps.shape != (1 << bits,):
+        raise EuError(f"{who}: a step table for {bits}-bit samples has {1 << bits} entries")
+    if len(forward) != 5:
+        raise EuError(f"{who}: forward is (k_r, k_g, k_b, c_u, c_v)")
+    if on_device:
+        _settle(y, wait)
+    o = YcbcrOut(ya, ba, ra, yp, bp if ch > 1 else max(bp, rp), step, sx, sy, bits, int(shift), int(on_device),
+                 y_steps.ctypes.data, c_steps.ctypes.data, *[float(np.float32(k)) for k in forward])
+    return o, (y, cb, cr, y_steps, c_steps)
+
+
+def _ycbcr_frame(who, frame):
+    if not _is_torch(frame) and not (isinstance(frame, np.ndarray) and frame.dtype == np.float32):
+        frame = np.ascontiguousarray(frame, np.float32)
+    if frame.ndim != 3 or frame.shape[2] not in (3, 4):
+        raise EuError(f"{who}: a frame has shape (h, w, 3) or (h, w, 4)")
+    return frame
+
+
+def ycbcr_planes(frame, forward, subsampling=(2, 2), interleaved=False, bits=8, shift=0, y_steps=None, c_steps=None,
+                 out=None):
+    """eu_hip_ycbcr_planes: the planes of a float frame on the host - what encode_ycbcr makes on the device, by
+    definition. Host function, no device needed. Arguments and result as encode_ycbcr, numpy only."""
+    frame = _ycbcr_frame("ycbcr_planes", frame)
+    if _is_torch(frame):
+        raise EuError("ycbcr_planes: a host function, the frame is a numpy array")
+    h, w, nch = frame.shape
+    y, chroma, cb, cr, sx, sy = _ycbcr_out_planes("ycbcr_planes", out, h, w, subsampling, interleaved, bits, None)
+    if h == 0 or w == 0:
+        return y, chroma
+    o, keep = _ycbcr_out_struct("ycbcr_planes", forward, y, cb, cr, sx, sy, bits, shift, y_steps, c_steps)
+    fptr, fstride, f_dev, lead, width, height = _grid(frame, "frame")
+    _check(lib().eu_hip_ycbcr_planes(C.c_void_p(fptr), fstride, w, h, nch, C.byref(o)))
+    return y, chroma
+
+
+def encode_ycbcr(frame, forward, subsampling=(2, 2), interleaved=False, bits=8, shift=0, y_steps=None, c_steps=None,
+                 out=None, stream=None):
+    """eu_hip_encode_ycbcr: a float frame to the planes of a Y'CbCr frame on the device, the mirror of load_ycbcr.
+    `frame`: float32 (h, w, 3) or (h, w, 4) (alpha is ignored), a numpy array or a torch tensor on the library's
+    device, rows possibly padded. forward: (k_r, k_g, k_b, c_u, c_v), see ycbcr_forward(). subsampling: (sub_x,
+    sub_y), 1 or 2 each - the chroma sample is the mean of its pixels, the edge replicated. y_steps / c_steps: float32
+    step tables of 1 << bits entries; without them ycbcr_steps(bits, bits - shift) (limited range). The stored sample is
+    code << shift (P010: bits 16, shift 6). Returns (y, chroma) in the shapes load_ycbcr takes: chroma is (cb, cr),
+    or with `interleaved` one (ch, cw, 2) array (NV12; for NV21 hand over out=(y, (vu[..., 1], vu[..., 0]))). New
+    numpy arrays for a numpy frame, new torch tensors for a torch frame, or `out` = (y, chroma), numpy arrays or
+    torch tensors on the device with their own strides. With frame and planes on the device the call is asynchronous
+    on `stream` (a torch stream or a hipStream_t address; None: the library's stream, after the tensors' current
+    stream has been waited for) until sync()."""
+    frame = _ycbcr_frame("encode_ycbcr", frame)
+    h, w, nch = frame.shape
+    y, chroma, cb, cr, sx, sy = _ycbcr_out_planes("encode_ycbcr", out, h, w, subsampling, interleaved, bits,
+                                                  frame if _is_torch(frame) else None)
+    if h == 0 or w == 0:
+        return y, chroma
+    o, keep = _ycbcr_out_struct("encode_ycbcr", forward, y, cb, cr, sx, sy, bits, shift, y_steps, c_steps,
+                                wait=stream is None)
+    if _is_torch(frame) and stream is not None:
+        st = tuple(frame.stride())
+        if not frame.is_cuda or st[2] != 1 or st[1] != nch or st[0] < w * nch:
+            raise EuError("encode_ycbcr: a torch frame is float32 on the device with dense pixels")
+        fptr, fstride, f_dev = frame.data_ptr(), st[0] * 4, True
+    else:
+        fptr, fstride, f_dev, lead, width, height = _grid(frame, "frame")
+    _check(lib().eu_hip_encode_ycbcr(C.c_void_p(fptr), fstride, int(f_dev), w, h, nch, C.byref(o), _stream_handle(stream)))
+    return y, chroma
+
+
+def render_ycbcr(args, sources, forward, subsampling=(2, 2), interleaved=False, bits=8, shift=0, y_steps=None,
+                 c_steps=None, out=None, stream=None, nchannels=None, row_begin=0, row_end=None, band=None):
+    """eu_hip_render_ycbcr: render() of a 3- or 4-channel target with the encode behind it on the device - the planes
+    of the rows row_begin .. row_end taken as an image of its own, byte for byte ycbcr_planes(render(...), ...),
+    without the float frame leaving the device. Keywords and result as encode_ycbcr; new planes are numpy arrays.
+    With `out` on the device the call is asynchronous on `stream` until sync(). Float frames only: no stage output,
+    not a tethered job."""
+    if not isinstance(sources, (list, tuple)):
+        sources = [sources]
+    if args.tethered:
+        raise EuError("render_ycbcr: a tethered job has its own format (render)")
+    t = args.target(nchannels or sources[0].fct.nchannels, row_begin, row_end, 0, band)
+    rows, w = t.row_end - t.row_begin, args.out_width
+    y, chroma, cb, cr, sx, sy = _ycbcr_out_planes("render_ycbcr", out, rows, w, subsampling, interleaved, bits, None)
+    if rows == 0 or w == 0:
+        return y, chroma
+    o, keep = _ycbcr_out_struct("render_ycbcr", forward, y, cb, cr, sx, sy, bits, shift, y_steps, c_steps,
+                                wait=stream is None)
+    arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
+    _check(lib().eu_hip_render_ycbcr(C.byref(t), arr, len(sources), C.byref(o), _stream_handle(stream)))
+    return y, chroma
 
 
 def reload_scratch_release():

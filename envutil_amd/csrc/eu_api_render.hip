@@ -5,6 +5,8 @@
 #include "eu_setup_math.h"
 #include "eu_encode.h"
 #include "eu_rgbe_dev.h"
+#include "eu_ycbcr_out.h"
+#include "../../include/eu_ycbcr.h"
 
 using namespace eu_host;
 
@@ -433,6 +435,58 @@ int order_encoders(hipStream_t st)
   return EU_OK;
 }
 
+// the launch of the Y'CbCr encode into the planes `d` names, without its frame
+eu_ycbcr_encode_params ycbcr_launch_params(const ycbcr_dst &d, const float *tables)
+{
+  const eu_ycbcr_out &o = *d.o;
+  eu_ycbcr_encode_params ep {};
+  ep.y = d.y; ep.cb = d.cb; ep.cr = d.cr; ep.y_pitch = d.y_pitch; ep.c_pitch = d.c_pitch;
+  ep.tables = tables;
+  ep.bits = o.bits; ep.shift = o.shift; ep.sub_x = o.sub_x; ep.sub_y = o.sub_y; ep.c_step = o.c_step;
+  ep.k_r = o.k_r; ep.k_g = o.k_g; ep.k_b = o.k_b; ep.c_u = o.c_u; ep.c_v = o.c_v;
+  return ep;
+}
+
+// Host planes are staged DENSE on the device, plane behind plane on 4-byte boundaries, and copied out per plane at the
+// caller's pitches; interleaved chroma is one plane of 2 cw samples per row that starts at the lower of cb and cr.
+struct ycbcr_stage {
+  size_t sb, sub_y, yrow, crow, cb_off, cr_off, total;   // bytes of a sample, of a dense luma / chroma row; plane offsets
+  bool pairs, v_first;
+  ycbcr_stage() : sb(1), sub_y(1), yrow(0), crow(0), cb_off(0), cr_off(0), total(0), pairs(false), v_first(false) {}
+  ycbcr_stage(const eu_ycbcr_out &o, size_t w, size_t rows)
+  {
+    sb = (size_t)o.bits / 8; sub_y = (size_t)o.sub_y;
+    pairs = o.c_step == 2;
+    v_first = pairs && reinterpret_cast<uintptr_t>(o.cr) < reinterpret_cast<uintptr_t>(o.cb);
+    const size_t cw = (w + o.sub_x - 1) / o.sub_x, crows = (rows + sub_y - 1) / sub_y;
+    yrow = w * sb;
+    crow = (pairs ? 2 : 1) * cw * sb;
+    cb_off = (rows * yrow + 3) / 4 * 4;
+    cr_off = pairs ? cb_off : cb_off + (crows * crow + 3) / 4 * 4;
+    total = cr_off + (crows * crow + 3) / 4 * 4;
+  }
+  // the planes of the staged rows from luma row `a` (a multiple of sub_y) on
+  ycbcr_dst at(const eu_ycbcr_out *o, char *base, size_t a) const
+  {
+    char *y = base + a * yrow, *c0 = base + cb_off + a / sub_y * crow, *c1 = base + cr_off + a / sub_y * crow;
+    if (pairs) return ycbcr_dst { o, y, v_first ? c0 + sb : c0, v_first ? c0 : c0 + sb, yrow, crow };
+    return ycbcr_dst { o, y, c0, c1, yrow, crow };
+  }
+  // the n luma rows staged from row `a` on, and their chroma rows, to the caller's planes from luma row `to` on
+  hipError_t copy_out(const eu_ycbcr_out &o, const char *base, size_t a, size_t to, size_t n, hipStream_t s) const
+  {
+    const size_t cn = (n + sub_y - 1) / sub_y;
+    hipError_t e = hipMemcpy2DAsync((char *)o.y + to * o.y_pitch, o.y_pitch, base + a * yrow, yrow, yrow, n, hipMemcpyDeviceToHost, s);
+    char *cb = (char *)(v_first ? o.cr : o.cb) + to / sub_y * o.c_pitch;
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(cb, o.c_pitch, base + cb_off + a / sub_y * crow, crow, crow, cn, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !pairs)
+      e = hipMemcpy2DAsync((char *)o.cr + to / sub_y * o.c_pitch, o.c_pitch, base + cr_off + a / sub_y * crow, crow, crow, cn,
+                           hipMemcpyDeviceToHost, s);
+    return e;
+  }
+};
+
 }  // namespace
 
 namespace eu_host __attribute__((visibility("hidden"))) {
@@ -440,9 +494,10 @@ namespace eu_host __attribute__((visibility("hidden"))) {
 // one job, everything on the device: float pixels straight into out_dev, or float pixels into the library's
 // frame buffer followed by a post-pass that writes out_dev - tethered, the to_screen_t pass and its packed words;
 // with `enc` (its tables are in enc.steps: upload_steps), the encode to integer samples; with `rgbe`, the encode to
-// Radiance quads (no tables; render_frame has ordered `st`)
+// Radiance quads (no tables; render_frame has ordered `st`); with `yc`, the encode to the planes `yc` names (out_dev is
+// not used; the tables are in enc.steps as for `enc`)
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
-                     const eu_switches &sw, hipStream_t st, const eu_encode *enc, bool rgbe)
+                     const eu_switches &sw, hipStream_t st, const eu_encode *enc, bool rgbe, const ycbcr_dst *yc)
 {
   int rc;
   const bool multi = nsrc > 1;
@@ -451,7 +506,7 @@ int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, flo
   float *fout = out_dev;
   size_t fstride = stride_bytes;
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
-  if (screen || enc || rgbe) {
+  if (screen || enc || rgbe || yc) {
     if (screen && !cur().lut) return fail(EU_ERR_NO_DEVICE, "sRGB table missing: library not initialised");
     // a post-pass queued on another stream may still read the frame buffer (render_frame has ordered `st` where enc or rgbe is set)
     if (screen && (rc = order_encoders(st))) return rc;
@@ -491,6 +546,12 @@ int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, flo
     ep.dst = reinterpret_cast<uint32_t *>(out_dev); ep.dst_stride_bytes = stride_bytes;
     ep.w = frame_w(trg); ep.h = (int)rows;
     if (eu_launch_rgbe_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+  }
+  if (yc && rows) {
+    eu_ycbcr_encode_params ep = ycbcr_launch_params(*yc, cur().enc.steps.dev.p);
+    ep.src = fout; ep.src_stride_bytes = fstride;
+    ep.w = frame_w(trg); ep.h = (int)rows; ep.nch = trg->nchannels;
+    if (eu_launch_ycbcr_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
   }
   return EU_OK;
 }
@@ -572,8 +633,11 @@ static int check_render_sources(const eu_target *trg, eu_source *const *srcs, in
 
 // The job of eu_hip_render, eu_hip_render_samples and eu_hip_render_rgbe behind their argument checks: `out` receives
 // rows of row_bytes bytes - floats or packed words, or, with `enc`, integer samples, or, with `rgbe`, Radiance quads.
+// With `yco`, `enc` holds its two tables (for the upload alone) and the planes it names receive the frame; `out`, row_bytes
+// and the stride are not used.
 static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out, size_t row_bytes,
-                        size_t out_row_stride_bytes, int out_on_device, void *stream, const eu_encode *enc, bool rgbe = false)
+                        size_t out_row_stride_bytes, int out_on_device, void *stream, const eu_encode *enc, bool rgbe = false,
+                        const eu_ycbcr_out *yco = nullptr)
 {
   int rc;
   hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
@@ -583,11 +647,16 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   if (rgbe && (rc = order_encoders(st))) return rc;
   // the sources may have been refilled in place (eu_hip_source_reload): `st` reads them behind that
   if ((rc = order_sources(srcs, nsrc, st))) return rc;
+  if (yco && out_on_device) {
+    const ycbcr_dst yd { yco, yco->y, yco->cb, yco->cr, yco->y_pitch, yco->c_pitch };
+    return note_readers(cur().tables, srcs, nsrc, stream, render_on_device(trg, srcs, nsrc, nullptr, 0, sw, st, nullptr, false, &yd));
+  }
   if (out_on_device)
     return note_readers(cur().tables, srcs, nsrc, stream, render_on_device(trg, srcs, nsrc, (float *)out, out_row_stride_bytes, sw, st, enc, rgbe));
   const size_t rows = (size_t)(trg->row_end - trg->row_begin);
   if (!rows) return EU_OK;
-  HIPCHK(cur().out.stage.reserve((rows * row_bytes + sizeof(float) - 1) / sizeof(float)));
+  const ycbcr_stage ys = yco ? ycbcr_stage(*yco, (size_t)frame_w(trg), rows) : ycbcr_stage();
+  HIPCHK(cur().out.stage.reserve(((yco ? ys.total : rows * row_bytes) + sizeof(float) - 1) / sizeof(float)));
   // The frame goes to the host in up to four row chunks: every chunk is a launch of its own
   // on `st`, and its copy (second stream, behind the chunk's event) runs while the later
   // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
@@ -606,11 +675,16 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
     tc.row_begin = trg->row_begin + (int)a;
     tc.row_end = trg->row_begin + (int)b;
     char *dst = (char *)cur().out.stage.p + a * row_bytes;
-    if ((rc = render_on_device(&tc, srcs, nsrc, (float *)dst, row_bytes, sw, st, enc, rgbe))) return rc;
+    if (yco) {                                    // `a` is a multiple of 8: no chunk splits a chroma row
+      const ycbcr_dst yd = ys.at(yco, (char *)cur().out.stage.p, a);
+      if ((rc = render_on_device(&tc, srcs, nsrc, nullptr, 0, sw, st, nullptr, false, &yd))) return rc;
+    } else if ((rc = render_on_device(&tc, srcs, nsrc, (float *)dst, row_bytes, sw, st, enc, rgbe))) return rc;
     HIPCHK(hipEventRecord(cur().out.chunk_done[c], st));
     HIPCHK(hipStreamWaitEvent(cur().out.copy, cur().out.chunk_done[c], 0));
-    HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, row_bytes,
-                            row_bytes, b - a, hipMemcpyDeviceToHost, cur().out.copy));
+    if (yco) HIPCHK(ys.copy_out(*yco, (const char *)cur().out.stage.p, a, a, b - a, cur().out.copy));
+    else
+      HIPCHK(hipMemcpy2DAsync((char *)out + a * out_row_stride_bytes, out_row_stride_bytes, dst, row_bytes,
+                              row_bytes, b - a, hipMemcpyDeviceToHost, cur().out.copy));
   }
   HIPCHK(hipStreamSynchronize(cur().out.copy));
   HIPCHK(hipStreamSynchronize(st));
@@ -702,6 +776,133 @@ int eu_hip_encode_samples(const float *frame, size_t frame_row_stride_bytes, int
   }
   HIPCHK(hipStreamSynchronize(st));
   return EU_OK;
+}
+
+// ---- Y'CbCr planes on the way out (eu_ycbcr_out.hip) -----------------------------------------------------------------
+// what the three entry points ask of `dst` for rows of `width` pixels of `nch` floats
+static int check_ycbcr_out(const char *who, const eu_ycbcr_out *o, int width, int nch)
+{
+  const std::string head = std::string(who) + ": ";
+  if (!o) return fail(EU_ERR_ARGUMENT, head + "null dst");
+  if (!o->y || !o->cb || !o->cr) return fail(EU_ERR_ARGUMENT, head + "null plane (y, cb, cr)");
+  if (!o->y_steps || !o->c_steps) return fail(EU_ERR_ARGUMENT, head + "null table (y_steps, c_steps)");
+  if (o->bits != 8 && o->bits != 16) return fail(EU_ERR_ARGUMENT, head + "bits must be 8 or 16");
+  if (o->shift < 0 || o->shift >= o->bits) return fail(EU_ERR_ARGUMENT, head + "shift must be 0 .. bits - 1");
+  if (o->sub_x != 1 && o->sub_x != 2) return fail(EU_ERR_ARGUMENT, head + "sub_x must be 1 or 2");
+  if (o->sub_y != 1 && o->sub_y != 2) return fail(EU_ERR_ARGUMENT, head + "sub_y must be 1 or 2");
+  if (o->c_step != 1 && o->c_step != 2) return fail(EU_ERR_ARGUMENT, head + "c_step must be 1 or 2");
+  const size_t sb = (size_t)o->bits / 8;
+  const uintptr_t ab = reinterpret_cast<uintptr_t>(o->cb), ar = reinterpret_cast<uintptr_t>(o->cr);
+  if (o->c_step == 2 && ar != ab + sb && ab != ar + sb)
+    return fail(EU_ERR_ARGUMENT, head + "c_step 2 is interleaved chroma: cr is cb plus or minus exactly one sample");
+  if (nch != 3 && nch != 4) return fail(EU_ERR_ARGUMENT, head + "nchannels must be 3 or 4");
+  if (width < 0 || (size_t)width * nch > (size_t(1) << 28)) return fail(EU_ERR_ARGUMENT, head + "rows of 0 .. 2^28 floats (width)");
+  if (width > 0) {
+    const size_t cw = ((size_t)width + o->sub_x - 1) / o->sub_x;
+    if (o->y_pitch < (size_t)width * sb) return fail(EU_ERR_ARGUMENT, head + "y_pitch shorter than a row of luma samples");
+    if (o->c_pitch < ((cw - 1) * o->c_step + 1) * sb) return fail(EU_ERR_ARGUMENT, head + "c_pitch shorter than a row of chroma samples");
+  }
+  if (o->bits == 16 && ((reinterpret_cast<uintptr_t>(o->y) | ab | ar) & 1))
+    return fail(EU_ERR_ARGUMENT, head + "16-bit planes (y, cb, cr) lie at even addresses");
+  if (o->bits == 16 && ((o->y_pitch | o->c_pitch) & 1))
+    return fail(EU_ERR_ARGUMENT, head + "16-bit planes have even pitches (y_pitch, c_pitch)");
+  int rc;
+  if ((rc = check_steps(o->y_steps, o->bits, who, "y"))) return rc;
+  if ((rc = check_steps(o->c_steps, o->bits, who, "c"))) return rc;
+  return EU_OK;
+}
+
+// ... and of the float frame that feeds them
+static int check_ycbcr_frame(const char *who, const float *frame, size_t stride, int width, int height, int nch)
+{
+  const std::string head = std::string(who) + ": ";
+  if (!frame) return fail(EU_ERR_ARGUMENT, head + "null frame");
+  if (height < 0) return fail(EU_ERR_ARGUMENT, head + "negative height");
+  if (stride < (size_t)width * nch * sizeof(float)) return fail(EU_ERR_ARGUMENT, head + "frame row stride smaller than a row");
+  if (stride % sizeof(float) || reinterpret_cast<uintptr_t>(frame) % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, head + "the frame and its row stride are multiples of 4 bytes");
+  return EU_OK;
+}
+
+int eu_hip_ycbcr_planes(const float *frame, size_t frame_row_stride_bytes, int width, int height, int nchannels,
+                        const eu_ycbcr_out *dst)
+{
+  int rc;
+  if ((rc = check_ycbcr_out("ycbcr_planes", dst, width, nchannels))) return rc;
+  if ((rc = check_ycbcr_frame("ycbcr_planes", frame, frame_row_stride_bytes, width, height, nchannels))) return rc;
+  if (dst->on_device) return fail(EU_ERR_ARGUMENT, "ycbcr_planes: a host function, on_device must be 0");
+  if (!width || !height) return EU_OK;
+  eu_ycbcr_planes_rows(frame, frame_row_stride_bytes, width, height, nchannels, dst->y, dst->cb, dst->cr, dst->y_pitch,
+                       dst->c_pitch, dst->c_step, dst->sub_x, dst->sub_y, dst->bits, dst->shift, dst->y_steps, dst->c_steps,
+                       dst->k_r, dst->k_g, dst->k_b, dst->c_u, dst->c_v);
+  return EU_OK;
+}
+
+int eu_hip_encode_ycbcr(const float *frame, size_t frame_row_stride_bytes, int frame_on_device, int width, int height,
+                        int nchannels, const eu_ycbcr_out *dst, void *stream)
+{
+  int rc;
+  if ((rc = check_ycbcr_out("encode_ycbcr", dst, width, nchannels))) return rc;
+  if ((rc = check_ycbcr_frame("encode_ycbcr", frame, frame_row_stride_bytes, width, height, nchannels))) return rc;
+  if (!width || !height) return EU_OK;
+  if ((rc = ensure_init())) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
+  const eu_encode tabs { dst->bits, 0, dst->y_steps, dst->c_steps };
+  if ((rc = upload_steps(&tabs, st))) return rc;
+  const ycbcr_dst whole { dst, dst->y, dst->cb, dst->cr, dst->y_pitch, dst->c_pitch };
+  if (frame_on_device && dst->on_device) {
+    eu_ycbcr_encode_params ep = ycbcr_launch_params(whole, cur().enc.steps.dev.p);
+    ep.src = frame; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.w = width; ep.h = height; ep.nch = nchannels;
+    if (eu_launch_ycbcr_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    return note_caller(cur().enc.readers, stream, EU_OK);
+  }
+  // A host buffer on either side: the chunks of eu_hip_encode_samples through its staging buffers, each a whole
+  // number of chroma rows - a chunk that split one would make two half-filled means of it
+  const size_t sb = (size_t)dst->bits / 8, cw = ((size_t)width + dst->sub_x - 1) / dst->sub_x;
+  const size_t in_row = (size_t)width * nchannels * sizeof(float), out_row = ((size_t)width + 2 * cw) * sb;
+  size_t fit = std::max<size_t>(1, EU_ENCODE_CHUNK_BYTES / (in_row + out_row));
+  fit = std::max<size_t>((size_t)dst->sub_y, fit / dst->sub_y * dst->sub_y);
+  const int ch = (int)std::min<size_t>((size_t)height, fit);
+  const ycbcr_stage ys(*dst, (size_t)width, (size_t)ch);
+  if (!frame_on_device) HIPCHK(cur().enc.frame.reserve((size_t)ch * width * nchannels));
+  if (!dst->on_device) HIPCHK(cur().enc.out.reserve((ys.total + 3) / 4));
+  drain drain_on_exit{ st, st };
+  for (int y0 = 0; y0 < height; y0 += ch) {
+    const int h = std::min(ch, height - y0);
+    const char *fin = (const char *)frame + (size_t)y0 * frame_row_stride_bytes;
+    const size_t c0 = (size_t)(y0 / dst->sub_y) * dst->c_pitch;
+    const ycbcr_dst yd = dst->on_device
+      ? ycbcr_dst { dst, (char *)dst->y + (size_t)y0 * dst->y_pitch, (char *)dst->cb + c0, (char *)dst->cr + c0, dst->y_pitch, dst->c_pitch }
+      : ys.at(dst, (char *)cur().enc.out.p, 0);
+    eu_ycbcr_encode_params ep = ycbcr_launch_params(yd, cur().enc.steps.dev.p);
+    ep.src = (const float *)fin; ep.src_stride_bytes = frame_row_stride_bytes;
+    ep.w = width; ep.h = h; ep.nch = nchannels;
+    if (!frame_on_device) {
+      ep.src = cur().enc.frame.p; ep.src_stride_bytes = in_row;
+      HIPCHK(hipMemcpy2DAsync(cur().enc.frame.p, in_row, fin, frame_row_stride_bytes, in_row, (size_t)h, hipMemcpyHostToDevice, st));
+    }
+    if (eu_launch_ycbcr_encode(&ep, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    if (!dst->on_device) HIPCHK(ys.copy_out(*dst, (const char *)cur().enc.out.p, 0, (size_t)y0, (size_t)h, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return EU_OK;
+}
+
+int eu_hip_render_ycbcr(const eu_target *trg, eu_source *const *srcs, int nsrc, const eu_ycbcr_out *dst, void *stream)
+{
+  int rc;
+  if (!trg) return fail(EU_ERR_ARGUMENT, "render_ycbcr: null target");
+  if (!srcs || nsrc < 1) return fail(EU_ERR_ARGUMENT, "render_ycbcr: no source");
+  if ((rc = check_target(trg))) return rc;
+  if (trg->stage) return fail(EU_ERR_ARGUMENT, "render_ycbcr: stage outputs are float only");
+  if (trg->out_format != EU_OUT_FLOAT) return fail(EU_ERR_ARGUMENT, "render_ycbcr: EU_OUT_SRGBA8 is a format of its own, not a frame to encode");
+  if ((rc = check_ycbcr_out("render_ycbcr", dst, frame_w(trg), trg->nchannels))) return rc;
+  if ((rc = check_render_sources(trg, srcs, nsrc))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (trg->row_end == trg->row_begin) return EU_OK;
+  const eu_encode tabs { dst->bits, 0, dst->y_steps, dst->c_steps };
+  return render_frame(trg, srcs, nsrc, nullptr, 0, 0, dst->on_device, stream, &tabs, false, dst);
 }
 
 // ---- Radiance RGBE quads on the way out (eu_rgbe.hip) -------------------------------------------------------------

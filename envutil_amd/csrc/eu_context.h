@@ -252,9 +252,18 @@ inline void destroy_source(eu_source *s)
   delete s;
 }
 
+// The planes one launch of the Y'CbCr encode writes (eu_ycbcr_out.hip): `o` says layout, depth and coefficients, the
+// pointers and pitches are those of the launch - the caller's planes on the device, or a staging buffer's.
+struct ycbcr_dst {
+  const eu_ycbcr_out *o;
+  void *y, *cb, *cr;
+  size_t y_pitch, c_pitch;
+};
+
 // eu_api_render.hip. One job, everything on the device: what eu_hip_render_devices takes from the render family
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
-                     const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr, bool rgbe = false);
+                     const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr, bool rgbe = false,
+                     const ycbcr_dst *yc = nullptr);
 
 // mean GPU time of `iters` calls of once() on the library's stream between two events, after one untimed call (which
 // builds whatever the first call builds: a plan's tables, derived copies)

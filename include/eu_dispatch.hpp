@@ -144,6 +144,12 @@ struct arguments : public facet_base
   // or as Radiance RGBE quads, encoded on the device (eu_hip_render_rgbe): width x height x 4 bytes, 3-channel
   // targets. Refused where p_output_samples is: --ray_map jobs, several GPUs.
   void *p_output_rgbe = nullptr;
+  // or as the planes of a Y'CbCr frame, encoded on the device (eu_hip_render_ycbcr): host planes, tables and
+  // coefficients of an eu_ycbcr_out the caller keeps alive; 3-channel targets. Refused where p_output_samples is.
+  const eu_ycbcr_out *p_output_ycbcr = nullptr;
+  // a .y4m --output: --y4m_format 420 | 422 | 444, --y4m_depth 8 | 10 | 12 | 16, --fps N[:D]
+  std::string y4m_format = "420";
+  int y4m_depth = 8, fps_num = 25, fps_den = 1;
   // PTO p-line crop (envutil_basic.h:684-687; envutil_payload.cc:440-474)
   bool store_cropped = false;
   int p_crop_x0 = 0, p_crop_x1 = 0, p_crop_y0 = 0, p_crop_y1 = 0;
@@ -291,7 +297,7 @@ struct hip_dispatch : public dispatch_base
   {
     if (projection != args.projection) return EU_ERR_ARGUMENT;
     if ((ninputs == 9) != !args.twine_spread.empty()) return EU_ERR_ARGUMENT;
-    if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples && !args.p_output_rgbe) return EU_ERR_ARGUMENT;
+    if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples && !args.p_output_rgbe && !args.p_output_ycbcr) return EU_ERR_ARGUMENT;
     // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
     if (args.synopsis != "panorama" && args.synopsis != "hdr_merge") return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
@@ -444,6 +450,11 @@ struct hip_dispatch : public dispatch_base
       if (slots > 1) return EU_ERR_ARGUMENT;
       return eu_hip_render_samples(&t, srcs.data(), int(srcs.size()), &args.output_encode, args.p_output_samples,
                                    size_t(w) * nchannels * size_t(args.output_encode.bits / 8), 0, nullptr);
+    }
+    if (args.p_output_ycbcr && !args.p_output) {
+      // Y'CbCr planes: encoded on the device behind the render, half the bytes of RGB8 at 4:2:0
+      if (slots > 1) return EU_ERR_ARGUMENT;
+      return eu_hip_render_ycbcr(&t, srcs.data(), int(srcs.size()), args.p_output_ycbcr, nullptr);
     }
     if (args.p_output_rgbe && !args.p_output) {
       // Radiance quads: encoded on the device behind the render, a third of the float frame's bytes

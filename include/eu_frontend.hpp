@@ -147,7 +147,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
     { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 }, { "--frames", 2 }, { "--ycbcr_matrix", 1 },
-    { "--ycbcr_range", 1 } };
+    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
@@ -223,6 +223,22 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   }
   if (!a.ycbcr_range.empty() && a.ycbcr_range != "limited" && a.ycbcr_range != "full") {
     err = "--ycbcr_range " + a.ycbcr_range + ": limited or full";
+    return false;
+  }
+  // a .y4m --output: what its stream header says
+  a.y4m_format = str("--y4m_format", "420");
+  a.y4m_depth = in("--y4m_depth", 8);
+  if (bad) return false;
+  if (a.y4m_format != "420" && a.y4m_format != "422" && a.y4m_format != "444") {
+    err = "--y4m_format " + a.y4m_format + ": 420, 422 or 444";
+    return false;
+  }
+  if (a.y4m_depth != 8 && a.y4m_depth != 10 && a.y4m_depth != 12 && a.y4m_depth != 16) {
+    err = "--y4m_depth " + str("--y4m_depth", "") + ": 8, 10, 12 or 16";
+    return false;
+  }
+  if (!io::parse_fps(str("--fps", "25:1"), a.fps_num, a.fps_den)) {
+    err = "--fps " + str("--fps", "") + ": N or N:D, whole numbers of at least 1";
     return false;
   }
   if (has("--frames")) {

@@ -611,6 +611,51 @@ int  eu_hip_encode_rgbe(const float *frame, size_t frame_row_stride_bytes, int f
 int  eu_hip_render_rgbe(const eu_target *trg, eu_source *const *srcs, int nsrc, void *out,
                         size_t out_row_stride_bytes, int out_on_device, void *stream);
 
+/* ---- the way out as Y'CbCr planes ------------------------------------------------ */
+/* Any float frame of 3 or 4 channels (alpha is ignored) to the planes of a Y'CbCr frame ON THE DEVICE
+ * (eu_ycbcr_out.hip), the mirror of eu_hip_source_load_ycbcr: what a hardware encoder takes as its input surface -
+ * planar (I420, I422, I444) or with interleaved chroma (NV12, NV21, P010). Every product and sum a float32 operation
+ * rounded on its own (include/eu_ycbcr.h):
+ *   Y = (k_r * R + k_g * G) + k_b * B        U = (B - Y) * c_u        V = (R - Y) * c_v
+ * Chroma is a box mean over sub_x x sub_y pixels with the edge replicated at odd sizes (include/eu_ycbcr.h has the
+ * order of the sums). Y goes through y_steps, the means of U and V through c_steps: tables of 1 << bits floats with
+ * eu_encode's semantics and validity rules (above). The stored sample is the low `bits` bits of code << shift, in
+ * host order. Range, depth and the chroma offset are the tables' business, the library knows none of them.
+ * The layout is eu_ycbcr's: rows y_pitch / c_pitch BYTES apart; c_step 1 planar; c_step 2 interleaved, and then cr
+ * is cb plus or minus exactly one sample. The chroma planes hold ceil(w / sub_x) x ceil(h / sub_y) samples. No byte
+ * outside the samples of a row of a plane is written; in interleaved chroma both samples of a pair are the call's.
+ * EU_ERR_ARGUMENT, before a device is looked for, each with a message of its own: null pointers, bits other than 8
+ * or 16, shift outside 0 .. bits - 1, sub_x or sub_y outside {1, 2}, c_step outside {1, 2} or an interleaved pair
+ * that is no pair, pitches shorter than a row, 16-bit planes or pitches at odd addresses, nchannels other than 3 or
+ * 4, a frame or a float stride that is no multiple of 4, an invalid table. width == 0 or height == 0 is EU_OK and
+ * writes nothing. */
+typedef struct eu_ycbcr_out {
+  void *y, *cb, *cr;            /* first sample of each plane                                              */
+  size_t y_pitch, c_pitch;      /* BYTES between rows of the luma plane / of both chroma planes            */
+  int32_t c_step;               /* 1 planar; 2 interleaved (NV12: cr == cb + 1 sample, NV21: cb == cr + 1) */
+  int32_t sub_x, sub_y;         /* 1 or 2 each                                                             */
+  int32_t bits;                 /* 8: uint8_t, 16: uint16_t in host order                                  */
+  int32_t shift;                /* 0 .. bits - 1: the sample is code << shift (P010: 6)                    */
+  int32_t on_device;            /* all three planes are memory of the library's device                     */
+  const float *y_steps, *c_steps; /* host, 1 << bits floats each                                           */
+  float k_r, k_g, k_b, c_u, c_v;  /* the forward coefficients                                              */
+} eu_ycbcr_out;
+/* Frame, strides, frame_on_device and `stream` as eu_hip_encode_samples. With frame and planes on the device the call
+ * is asynchronous on `stream` (NULL: the library's) until eu_hip_sync(); a host buffer on either side goes through
+ * bounded chunks of that call's staging buffers - whole chroma rows each - and the call returns when the planes are
+ * complete. */
+int  eu_hip_encode_ycbcr(const float *frame, size_t frame_row_stride_bytes, int frame_on_device, int width, int height,
+                         int nchannels, const eu_ycbcr_out *dst, void *stream);
+/* eu_hip_render with that encode behind it, as eu_hip_render_samples is built: every job eu_hip_render runs with a 3-
+ * or 4-channel target, the float frame in the library's frame buffer, the same pipeline of up to four row chunks for
+ * host planes. The planes are those of the rows row_begin .. row_end taken as an image of its own. EU_ERR_ARGUMENT,
+ * before a device is looked for: what eu_hip_render and eu_hip_encode_ycbcr refuse, stage != 0 and EU_OUT_SRGBA8. */
+int  eu_hip_render_ycbcr(const eu_target *trg, eu_source *const *srcs, int nsrc, const eu_ycbcr_out *dst, void *stream);
+/* HOST function, no device needed: the definition of the two calls above, one loop over eu_ycbcr.h's statement.
+ * dst->on_device must be 0. */
+int  eu_hip_ycbcr_planes(const float *frame, size_t frame_row_stride_bytes, int width, int height, int nchannels,
+                         const eu_ycbcr_out *dst);
+
 /* device memory helpers for hosts without a HIP binding of their own */
 int  eu_hip_malloc(void **p, size_t bytes);
 int  eu_hip_free(void *p);

@@ -848,7 +848,7 @@ inline bool frame_number(const std::string &s, int &v)
 
 // --frames FIRST LAST on the single facet's image `image` with the output `output`: both numbers at least 0 and
 // FIRST <= LAST; the image a .y4m stream or a name with one integer conversion (not the six-file cubemap name, %s);
-// the output a name with one integer conversion
+// the output a name with one integer conversion, or a .y4m stream
 inline bool check_frames(const std::string &first_s, const std::string &last_s, const std::string &image,
                          const std::string &output, int &first, int &last, std::string &err)
 {
@@ -862,7 +862,8 @@ inline bool check_frames(const std::string &first_s, const std::string &last_s, 
     if (image.find("%s") != std::string::npos) { err = "--frames: '" + image + "' names the six files of a cubemap (%s): a frame sequence is one file per frame"; return false; }
     if (!frame_name(image, first, name, err)) { err = "--frames: the facet's image " + err; return false; }
   }
-  if (!frame_name(output, first, name, err)) { err = "--frames: --output " + err; return false; }
+  // (a .y4m output is one stream that holds all frames: its name needs no conversion)
+  if (lower_ext(output) != "y4m" && !frame_name(output, first, name, err)) { err = "--frames: --output " + err; return false; }
   return true;
 }
 
@@ -1016,6 +1017,143 @@ inline bool ycbcr_matrix(const std::string &name, float m[4], std::string &err)
   m[3] = float(2.0 * (1.0 - kb));
   return true;
 }
+
+// ycbcr_forward of the Python binding: "601", "709", "2020" -> k_r, k_g, k_b, c_u, c_v (eu_hip.h: eu_ycbcr_out)
+inline bool ycbcr_forward(const std::string &name, float k[5], std::string &err)
+{
+  double kr, kb;
+  if (name == "601") { kr = 0.299; kb = 0.114; }
+  else if (name == "709") { kr = 0.2126; kb = 0.0722; }
+  else if (name == "2020") { kr = 0.2627; kb = 0.0593; }
+  else { err = "--ycbcr_matrix " + name + ": 601, 709 or 2020"; return false; }
+  k[0] = float(kr);
+  k[1] = float(1.0 - kr - kb);
+  k[2] = float(kb);
+  k[3] = float(1.0 / (2.0 * (1.0 - kb)));
+  k[4] = float(1.0 / (2.0 * (1.0 - kr)));
+  return true;
+}
+
+// ycbcr_steps of the Python binding, the inverse of ycbcr_tables: the step tables (eu_hip.h: eu_ycbcr_out) of the
+// quantiser code(v) = clip(floor(double(v) * a + b + 0.5), 0, 2^depth - 1), NaN -> 0, bisected over the float keys as
+// encode_steps bisects. With s = 2^(depth - 8): limited range a, b = 219 s, 16 s (luma) and 224 s, 128 s (chroma);
+// full range 2^depth - 1, 0 and 2^depth - 1, 128 s. steps[0] = -inf, NaN behind 2^depth - 1; codes in the low bits.
+inline bool ycbcr_steps(int bits, int depth, bool full_range, std::vector<float> &y_steps, std::vector<float> &c_steps)
+{
+  if ((bits != 8 && bits != 16) || depth < 8 || depth > bits) return false;
+  const size_t n = size_t(1) << bits;
+  const double s = std::ldexp(1.0, depth - 8), top = std::ldexp(1.0, depth) - 1.0;
+  const uint32_t lo_key = float_key(-HUGE_VALF), hi_key = float_key(HUGE_VALF);
+  auto build = [&](std::vector<float> &steps, double a, double b) {
+    auto q = [&](float v) -> double {
+      if (v != v) return 0.0;
+      const double c = std::floor(double(v) * a + b + 0.5);
+      return c < 0.0 ? 0.0 : c > top ? top : c;
+    };
+    steps.assign(n, std::nanf(""));
+    steps[0] = -HUGE_VALF;
+    uint32_t lo = lo_key;
+    for (unsigned k = 1; k <= unsigned(top); k++) {
+      uint32_t l = lo, h = hi_key;
+      while (l < h) {
+        const uint32_t m = l + (h - l) / 2;
+        if (q(key_float(m)) >= double(k)) h = m; else l = m + 1;
+      }
+      steps[k] = key_float(l);
+      lo = l;
+    }
+  };
+  build(y_steps, full_range ? top : 219.0 * s, full_range ? 0.0 : 16.0 * s);
+  build(c_steps, full_range ? top : 224.0 * s, 128.0 * s);
+  return true;
+}
+
+// "N" or "N:D", both whole and at least 1
+inline bool parse_fps(const std::string &s, int &num, int &den)
+{
+  const size_t c = s.find(':');
+  den = 1;
+  if (!frame_number(s.substr(0, c), num) || num < 1) return false;
+  return c == std::string::npos || (frame_number(s.substr(c + 1), den) && den >= 1);
+}
+
+// The counterpart of y4m_reader: a YUV4MPEG2 stream written frame by frame. format "420" | "422" | "444", depth 8, 10,
+// 12 or 16 - above 8 the samples are 16-bit little-endian words with the code in the low bits, the tags C420p10 and
+// so on that the reader accepts. 8-bit 4:2:0 is tagged C420jpeg: a box mean of the chroma is centre siting.
+struct y4m_writer
+{
+  FILE *f = nullptr;
+  y4m_info info;
+  int frames = 0;
+  std::string name, tag;
+  y4m_writer() = default;
+  y4m_writer(const y4m_writer &) = delete;
+  y4m_writer &operator=(const y4m_writer &) = delete;
+  ~y4m_writer() { if (f) std::fclose(f); }
+
+  // the frames' layout for a format and a depth, without a file: what open() writes planes of
+  static bool layout(int width, int height, const std::string &format, int depth, bool full_range, y4m_info &info,
+                     std::string &tag, std::string &err)
+  {
+    if (width < 1 || height < 1) { err = "a .y4m frame has at least one pixel"; return false; }
+    if (format != "420" && format != "422" && format != "444") { err = "--y4m_format " + format + ": 420, 422 or 444"; return false; }
+    if (depth != 8 && depth != 10 && depth != 12 && depth != 16) { err = "--y4m_depth " + std::to_string(depth) + ": 8, 10, 12 or 16"; return false; }
+    tag = depth == 8 ? (format == "420" ? "420jpeg" : format) : format + "p" + std::to_string(depth);
+    info = y4m_info();
+    info.width = width; info.height = height;
+    if (!y4m_colour_tag(tag, info, err)) return false;
+    info.full_range = full_range;
+    const size_t sb = size_t(info.bits / 8);
+    const size_t cw = (size_t(width) + info.sub_x - 1) / info.sub_x, ch = (size_t(height) + info.sub_y - 1) / info.sub_y;
+    info.y_bytes = size_t(width) * height * sb;
+    info.c_bytes = cw * ch * sb;
+    return true;
+  }
+  // the stream header, one line without its newline
+  static std::string header(const y4m_info &info, const std::string &tag, int fps_num, int fps_den)
+  {
+    return "YUV4MPEG2 W" + std::to_string(info.width) + " H" + std::to_string(info.height) + " F" + std::to_string(fps_num) +
+           ":" + std::to_string(fps_den) + " Ip A1:1 C" + tag + (info.full_range ? " XCOLORRANGE=FULL" : "");
+  }
+  bool open(const std::string &file, int width, int height, const std::string &format, int depth, bool full_range,
+            int fps_num, int fps_den, std::string &err)
+  {
+    if (f) { std::fclose(f); f = nullptr; }
+    name = file; frames = 0;
+    if (fps_num < 1 || fps_den < 1) { err = "--fps N[:D]: whole numbers, at least 1"; return false; }
+    if (!layout(width, height, format, depth, full_range, info, tag, err)) return false;
+    f = std::fopen(file.c_str(), "wb");
+    if (!f) { err = "cannot write " + file; return false; }
+    const std::string h = header(info, tag, fps_num, fps_den) + "\n";
+    if (std::fwrite(h.data(), 1, h.size(), f) != h.size()) { err = "cannot write " + file; return false; }
+    return true;
+  }
+  // one frame: the planes Y, Cb, Cr behind one another, rows dense, samples in HOST order (info.frame_bytes() bytes)
+  bool frame(const uint8_t *planes, std::string &err)
+  {
+    if (!f) { err = name + ": not open"; return false; }
+    bool ok = std::fwrite("FRAME\n", 1, 6, f) == 6;
+    const size_t nb = info.frame_bytes();
+    const uint16_t one = 1;
+    if (info.bits == 8 || *reinterpret_cast<const uint8_t *>(&one) == 1) ok = ok && std::fwrite(planes, 1, nb, f) == nb;
+    else {                                       // a big-endian host: low byte first
+      std::vector<uint8_t> le(nb);
+      for (size_t i = 0; i + 1 < nb; i += 2) { le[i] = planes[i + 1]; le[i + 1] = planes[i]; }
+      ok = ok && std::fwrite(le.data(), 1, nb, f) == nb;
+    }
+    if (!ok) { err = "cannot write " + name; return false; }
+    frames++;
+    return true;
+  }
+  bool close(std::string &err)
+  {
+    if (!f) return true;
+    const bool ok = std::fclose(f) == 0;
+    f = nullptr;
+    if (!ok) err = "cannot write " + name;
+    return ok;
+  }
+};
 
 inline bool probe_y4m(const std::string &name, int &width, int &height, int &nchannels, std::string &err)
 {

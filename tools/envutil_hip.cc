@@ -71,6 +71,67 @@ static std::string series_name(const std::string &fmt, int index)
   return buf.data();
 }
 
+// A .y4m --output: one stream for all frames of a run, opened by the first frame that is written (its size is the
+// frame's), closed by core()
+static std::unique_ptr<io::y4m_writer> y4m_sink;
+
+// One frame as the planes of the stream's format: rendered and encoded on the device (eu_hip_render_ycbcr), the bytes
+// of the file come down as they are. No colour conversion: the floats are encoded as they are, as a .y4m facet is
+// loaded as it is.
+static int run_payload_y4m(const std::string &output, int ow, int oh)
+{
+  std::string err;
+  const bool full = args.ycbcr_range == "full";
+  const std::string matrix = !args.ycbcr_matrix.empty() ? args.ycbcr_matrix : oh >= 720 ? "709" : "601";
+  if (!y4m_sink) {
+    y4m_sink.reset(new io::y4m_writer);
+    if (!y4m_sink->open(output, ow, oh, args.y4m_format, args.y4m_depth, full, args.fps_num, args.fps_den, err)) {
+      std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+      return 1;
+    }
+  }
+  io::y4m_writer &sink = *y4m_sink;
+  const io::y4m_info &yi = sink.info;
+  if (yi.width != ow || yi.height != oh) {
+    std::fprintf(stderr, "envutil_hip: %s holds frames of %d x %d, this one has %d x %d\n", output.c_str(), yi.width, yi.height, ow, oh);
+    return 1;
+  }
+  // (the tables of a depth and a range are kept: the frames of a sequence share them)
+  static std::map<std::string, std::pair<std::vector<float>, std::vector<float>>> kept;
+  const std::string key = std::to_string(yi.depth) + (full ? "f" : "l");
+  auto it = kept.find(key);
+  if (it == kept.end()) {
+    std::pair<std::vector<float>, std::vector<float>> t;
+    io::ycbcr_steps(yi.bits, yi.depth, full, t.first, t.second);
+    it = kept.emplace(key, std::move(t)).first;
+  }
+  float k[5];
+  if (!io::ycbcr_forward(matrix, k, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 1; }
+  std::vector<uint8_t> planes(yi.frame_bytes());
+  const size_t sb = size_t(yi.bits / 8), cw = (size_t(ow) + yi.sub_x - 1) / yi.sub_x;
+  eu_ycbcr_out o {};
+  o.y = planes.data(); o.cb = planes.data() + yi.y_bytes; o.cr = planes.data() + yi.y_bytes + yi.c_bytes;
+  o.y_pitch = size_t(ow) * sb; o.c_pitch = cw * sb;
+  o.c_step = 1; o.sub_x = yi.sub_x; o.sub_y = yi.sub_y; o.bits = yi.bits; o.shift = 0; o.on_device = 0;
+  o.y_steps = it->second.first.data(); o.c_steps = it->second.second.data();
+  o.k_r = k[0]; o.k_g = k[1]; o.k_b = k[2]; o.c_u = k[3]; o.c_v = k[4];
+  args.p_output_ycbcr = &o;
+  const int rc = get_dispatch()->payload(args.nchannels, args.twine ? 9 : 3, args.projection);
+  args.p_output_ycbcr = nullptr;
+  if (rc != 0) {
+    std::fprintf(stderr, "envutil_hip: render failed (%d): %s\n", rc, eu_hip_last_error());
+    return 1;
+  }
+  if (!sink.frame(planes.data(), err)) {
+    std::fprintf(stderr, "envutil_hip: %s\n", err.c_str());
+    return 1;
+  }
+  if (args.verbose)
+    std::printf("saved frame %d of %s (%d x %d, C%s, BT.%s %s range): Y'CbCr planes, encoded on the device\n", sink.frames - 1,
+                output.c_str(), ow, oh, sink.tag.c_str(), matrix.c_str(), full ? "full" : "limited");
+  return 0;
+}
+
 static int run_payload(const std::string &output)
 {
   int ow = args.width, oh = args.height;
@@ -78,6 +139,7 @@ static int run_payload(const std::string &output)
   const bool ray_map = args.p_ray_map != nullptr;            // --ray_map: the output has the map's size
   if (ray_map) { ow = args.ray_map_width; oh = args.ray_map_height; }
   std::string err;
+  if (io::lower_ext(output) == "y4m") return run_payload_y4m(output, ow, oh);    // (core() has refused what does not go with it)
   const bool cube = (args.projection == CUBEMAP || args.projection == BIATAN6) && !args.store_cropped && !ray_map;
   // save_array attaches the target's projection and hfov (degrees) to the file (envutil_basic.h:770-772)
   io::metadata meta;
@@ -226,6 +288,46 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
       return 2;
     }
   }
+  // A .y4m --output is written through eu_hip_render_ycbcr. What that route does not do is refused here, each with
+  // its own message.
+  const bool y4m_out = io::lower_ext(args.output) == "y4m";
+  y4m_sink.reset();
+  for (const std::string &name : args.layer_output_v)
+    if (io::lower_ext(name) == "y4m") {
+      std::fprintf(stderr, "envutil_hip: --layer %s: the pictures of --layer leave by the float route, a .y4m stream is the --output's alone\n", name.c_str());
+      return 2;
+    }
+  if (io::lower_ext(args.split) == "y4m" || (y4m_out && !args.split.empty())) {
+    std::fprintf(stderr, "envutil_hip: --split does not go with a .y4m output: its jobs differ in size, a stream holds frames of one size\n");
+    return 2;
+  }
+  if (y4m_out) {
+    if (pipe_mode) {
+      std::fprintf(stderr, "envutil_hip: a .y4m output does not go with pipe mode: one call writes the stream, then the program ends\n");
+      return 2;
+    }
+    if (!args.ray_map.empty()) {
+      std::fprintf(stderr, "envutil_hip: a .y4m output does not go with --ray_map: a ray map's output is a float image\n");
+      return 2;
+    }
+    if (args.nchannels != 3) {
+      std::fprintf(stderr, "envutil_hip: a .y4m output holds 3 channels, the target has %d (--nchannels 3)\n", args.nchannels);
+      return 2;
+    }
+    if (hip_dispatch::device_slots() > 1) {
+      std::fprintf(stderr, "envutil_hip: a .y4m output is encoded on one device: set EU_HIP_DEVICES=1 on a host with several\n");
+      return 2;
+    }
+  }
+  struct close_sink {
+    ~close_sink()
+    {
+      std::string e;
+      if (y4m_sink && !y4m_sink->close(e)) std::fprintf(stderr, "envutil_hip: %s\n", e.c_str());
+      if (y4m_sink && !y4m_sink->frames && !y4m_sink->name.empty()) std::remove(y4m_sink->name.c_str());   // no frame: no stream
+      y4m_sink.reset();
+    }
+  } close_sink_on_exit;
   const bool sequence = args.frames_first >= 0;
   if (sequence) {
     if (pipe_mode) {
@@ -378,7 +480,8 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
       std::string file = f.filename, out;
       const bool stream = io::lower_ext(file) == "y4m";
       if (!stream && !io::frame_name(f.filename, k, file, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 2; }
-      if (!io::frame_name(out_format, k, out, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 2; }
+      if (y4m_out) out = out_format;              // one stream holds all frames
+      else if (!io::frame_name(out_format, k, out, err)) { std::fprintf(stderr, "envutil_hip: %s\n", err.c_str()); return 2; }
       if (k > args.frames_first) {
         int kind = 0, nch = 0;
         if (!read_pixels(0, f, file, k, kind, nch)) { std::fprintf(stderr, "envutil_hip: frame %d could not be read\n", k); return 2; }
@@ -463,6 +566,9 @@ int main(int argc, const char **argv)
         "            one integer conversion each (%d, %04d, ...), or the image is a .y4m stream (YUV4MPEG2; read forward);\n"
         "            the first frame is loaded, every later one refills the source in place\n"
         "            --ycbcr_matrix 601|709|2020 (default: 709 from 720 rows on, else 601)  --ycbcr_range limited|full\n"
+        "  video out: an --output ending in .y4m is a YUV4MPEG2 stream, encoded on the device; with --frames one stream\n"
+        "            holds all frames. --y4m_format 420|422|444  --y4m_depth 8|10|12|16  --fps N[:D] (default 25:1);\n"
+        "            --ycbcr_matrix / --ycbcr_range say matrix and range (default: by the output's rows, limited)\n"
         "  images:   .pfm .hdr (float), .pgm .ppm .pnm (8 / 16 bit), .pam (8 / 16 bit, alpha), .y4m (frame 0 without --frames); a name with one %s\n"
         "            stands for six cube faces: left right top bottom front back\n"
         "            .hdr / .pic and the integer formats go to and from the device as the file's own pixels\n"
