@@ -54,7 +54,8 @@ class Target(C.Structure):
                 ("crop_w", C.c_int32), ("crop_h", C.c_int32),
                 ("out_format", C.c_int32),
                 ("band_rows", C.c_int32), ("band_count", C.c_int32), ("band_index", C.c_int32),
-                ("synopsis", C.c_int32), ("single", C.POINTER(Facet))]
+                ("synopsis", C.c_int32), ("single", C.POINTER(Facet)),
+                ("feather", C.c_double)]
 
 
 class Rays(C.Structure):
@@ -74,7 +75,7 @@ class View(C.Structure):
 
 ROW_FLOATS = 24     # floats per row-table entry (EU_ROW_FLOATS)
 OUT_FLOAT, OUT_SRGBA8 = 0, 1
-SYN_PANORAMA, SYN_HDR_MERGE = 0, 1
+SYN_PANORAMA, SYN_HDR_MERGE, SYN_FEATHER = 0, 1, 2
 
 
 def lib_path():
@@ -1059,17 +1060,23 @@ class arguments:
     def __init__(self, projection, width, height, hfov, yaw=0.0, pitch=0.0, roll=0.0,
                  spline_degree=1, prefilter_degree=None, twine=0, twine_width=1.0,
                  twine_sigma=0.0, twine_threshold=0.0, support_min=8, tile_size=64,
-                 crop=None, tethered=False, synopsis="panorama", single=None):
+                 crop=None, tethered=False, synopsis="panorama", single=None, feather=0.0):
         # store_cropped + p_crop_x0/x1/y0/y1 (envutil_basic.h:684-687) as
         # (x0, x1, y0, y1); tethered: the job writes packed sRGBA8 words
         # (args.p_screen_data, envutil_payload.cc:524-530)
         self.store_cropped = crop is not None
         self.p_crop = tuple(crop) if crop is not None else None
         self.tethered = tethered
-        # args.synopsis (envutil_main.cc:232): how several facets are composed, "panorama" or "hdr_merge"
-        if synopsis not in ("panorama", "hdr_merge"):
-            raise ValueError("synopsis must be panorama or hdr_merge")
+        # args.synopsis (envutil_main.cc:232): how several facets are composed, "panorama" or "hdr_merge" - and
+        # "feather", this project's own: feathered seams (eu_hip.h, eu_target::feather)
+        if synopsis not in ("panorama", "hdr_merge", "feather"):
+            raise ValueError("synopsis must be panorama, hdr_merge or feather")
         self.synopsis = synopsis
+        # the width of the feathering ramp in source pixels; 0: half the shorter side of each facet's window
+        feather = float(feather)
+        if not math.isfinite(feather) or feather < 0.0:
+            raise ValueError("feather must be a finite width in source pixels, 0 for the default")
+        self.feather = feather
         # args.single: the facet_spec this target recreates ((facet_base&) args = fspec, envutil_main.cc:1161-1180);
         # projection, size, hfov and orientation of the target must be the facet's own (see for_single)
         self.single = single
@@ -1114,7 +1121,8 @@ class arguments:
             x0, x1, y0, y1 = self.p_crop
             t.crop_x0, t.crop_y0, t.crop_w, t.crop_h = x0, y0, x1 - x0, y1 - y0
         t.out_format = OUT_SRGBA8 if self.tethered else OUT_FLOAT
-        t.synopsis = SYN_HDR_MERGE if self.synopsis == "hdr_merge" else SYN_PANORAMA
+        t.synopsis = {"panorama": SYN_PANORAMA, "hdr_merge": SYN_HDR_MERGE, "feather": SYN_FEATHER}[self.synopsis]
+        t.feather = self.feather
         if self.single is not None:
             self._single_c = self.single.c_struct()          # kept alive with the arguments object
             t.single = C.pointer(self._single_c)

@@ -62,6 +62,17 @@ int local_rows(int height, int band_rows, int band_count, int band_index)
   return rows;
 }
 
+// the synopsis and its width: asked on its own by the entry points that look for a device before they look at
+// the target (eu_hip_render, eu_hip_render_devices), so that these refusals need none
+int check_synopsis(const eu_target *t)
+{
+  if (t->synopsis != EU_SYN_PANORAMA && t->synopsis != EU_SYN_HDR_MERGE && t->synopsis != EU_SYN_FEATHER)
+    return fail(EU_ERR_ARGUMENT, "unknown synopsis");
+  if (!std::isfinite(t->feather) || t->feather < 0.0)
+    return fail(EU_ERR_ARGUMENT, "feather must be a finite width in source pixels, 0 for the default");
+  return EU_OK;
+}
+
 int check_target(const eu_target *t)
 {
   if (t->nchannels < 1 || t->nchannels > 4) return fail(EU_ERR_ARGUMENT, "target channels must be 1..4");
@@ -83,8 +94,7 @@ int check_target(const eu_target *t)
     return fail(EU_ERR_ARGUMENT, "bad twining tap table");
   if ((t->projection == EU_CUBEMAP || t->projection == EU_BIATAN6) && t->height != 6 * t->width)
     return fail(EU_ERR_ARGUMENT, "cubemap targets are 1:6");
-  if (t->synopsis != EU_SYN_PANORAMA && t->synopsis != EU_SYN_HDR_MERGE)
-    return fail(EU_ERR_ARGUMENT, "unknown synopsis");
+  { int rcs = check_synopsis(t); if (rcs) return rcs; }
   if (t->out_format != EU_OUT_FLOAT && t->out_format != EU_OUT_SRGBA8)
     return fail(EU_ERR_ARGUMENT, "unknown output format");
   if (t->out_format == EU_OUT_SRGBA8 && t->stage)
@@ -108,7 +118,7 @@ std::vector<float> biased_taps(const float *taps, int ntaps)
 void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_multi_params *p)
 {
   p->nch = t->nchannels; p->nfct = nsrc; p->plus = (t->nchannels == 2 || t->nchannels == 4);
-  p->hdr = t->synopsis == EU_SYN_HDR_MERGE;
+  p->mode = t->synopsis == EU_SYN_HDR_MERGE ? EU_MODE_HDR : t->synopsis == EU_SYN_FEATHER ? EU_MODE_FEATHER : EU_MODE_PANORAMA;
   float lowest = 100000.0f, highest = -1.0f;
   p->hdr_low = p->hdr_high = -1;
   for (int f = 0; f < nsrc; f++) {
@@ -116,6 +126,29 @@ void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_mult
     if (b < lowest) { lowest = b; p->hdr_low = f; }
     if (b > highest) { highest = b; p->hdr_high = f; }
   }
+}
+
+// The edge weight's constants per facet (eu_synopsis_feather). The width is the target's `feather` in source
+// pixels; 0: half the shorter side of that facet's window, so that the ramp reaches the centre. An axis has no
+// border where the facet wraps or closes there: axis 0 where the load chose PERIODIC, axis 1 for a full sphere
+// (the load's own condition for the spherical prefilter), both for cube sources and wherever the mask is
+// constant true.
+std::vector<eu_feather_dev> feather_table(const eu_target *t, eu_source *const *srcs, int nsrc)
+{
+  std::vector<eu_feather_dev> v((size_t)nsrc);
+  for (int f = 0; f < nsrc; f++) {
+    const eu_source *s = srcs[f];
+    const eu_facet &fc = s->fct;
+    const bool closed = eu_cube_source(fc.projection) || s->sd.mask_all;
+    const bool wrap0 = closed || s->bc[0] == EU_BC_PERIODIC;
+    const bool wrap1 = closed || (full_sphere(&fc) && s->bc[0] == EU_BC_PERIODIC);
+    const double width_px = t->feather > 0.0 ? t->feather : 0.5 * (double)std::min(fc.window_width, fc.window_height);
+    v[f].rcp = (float)(1.0 / width_px);
+    v[f].lim_x = (float)fc.window_width - 0.5f;
+    v[f].lim_y = (float)fc.window_height - 0.5f;
+    v[f].border = (wrap0 ? 0 : 1) | (wrap1 ? 0 : 2);
+  }
+  return v;
 }
 
 }  // namespace eu_host

@@ -128,6 +128,7 @@ int eu_hip_render_devices(const eu_target *trg, eu_source *const *srcs, int nsrc
                           size_t out_row_stride_bytes, int out_on_device)
 {
   int rc;
+  if (trg && (rc = check_synopsis(trg))) return rc;      // before a device is looked for
   if ((rc = ensure_init())) return rc;
   if (nslots_ <= 1) return eu_hip_render(trg, srcs, nsrc, out, out_row_stride_bytes, out_on_device, nullptr);
   if (!trg || !srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "no source / no output");

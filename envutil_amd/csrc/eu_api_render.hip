@@ -62,6 +62,7 @@ std::vector<unsigned char> plan_key_of(const eu_target *t, eu_source *const *src
   eu_target tk = *t;
   tk.taps = nullptr; tk.single = nullptr; tk.row_begin = 0; tk.row_end = 0; tk.stage = 0; tk.nchannels = 0; tk.out_format = 0;
   tk.band_rows = 0; tk.band_count = 0; tk.band_index = 0;
+  tk.feather = 0.0;                 // the synopsis' business: no table depends on it
   unsigned char *q = key.data();
   memcpy(q, &tk, sizeof tk); q += sizeof tk;
   if (multi) { memcpy(q, &nsrc, sizeof(int)); q += sizeof(int); }
@@ -289,10 +290,18 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     HIPCHK(mp.gen.reserve((size_t)nsrc));
     HIPCHK(hipMemcpyAsync(mp.gen.p, gv.data(), sizeof(eu_generic) * (size_t)nsrc, hipMemcpyHostToDevice, cur().stream));
   }
+  // the feathered synopsis' edge-weight table: the job's, like the two above
+  const bool feather = t->synopsis == EU_SYN_FEATHER;
+  const std::vector<eu_feather_dev> fth = feather ? feather_table(t, srcs, nsrc) : std::vector<eu_feather_dev>();
+  if (feather) {
+    HIPCHK(mp.fth.reserve((size_t)nsrc));
+    HIPCHK(hipMemcpyAsync(mp.fth.p, fth.data(), sizeof(eu_feather_dev) * (size_t)nsrc, hipMemcpyHostToDevice, cur().stream));
+  }
   HIPCHK(hipStreamSynchronize(cur().stream));
   eu_inv_planar inv;
   { int rci = build_inv_planar(t, &inv); if (rci) return rci; }
   memset(p, 0, sizeof *p);
+  p->fth = feather ? mp.fth.p : nullptr;
   p->gen = any_generic ? mp.gen.p : nullptr;
   p->rej = any_rej ? mp.rej.p : nullptr;
   p->inv = inv;
@@ -695,6 +704,7 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
                   size_t out_row_stride_bytes, int out_on_device, void *stream)
 {
   int rc;
+  if (trg && (rc = check_synopsis(trg))) return rc;      // before a device is looked for
   if ((rc = ensure_init())) return rc;
   if (!trg) return fail(EU_ERR_ARGUMENT, "null target");
   if (!srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "no source / no output");

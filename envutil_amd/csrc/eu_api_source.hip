@@ -192,10 +192,7 @@ void source_bcs(const eu_facet *f, int *bc0, int *bc1)
 // scheme, everything else bspline::prefilter(). A stronger test than source_bcs', and a separate one.
 // (a full-sphere image smaller than its frame - 2 x 1, 4 x 2, 6 x 3 for degree 3 - takes the sequential forms of
 // the pole rows and of the horizontal bracing: eu_setup.hip, pole_rows_seq_kernel / brace_seq_kernel)
-bool full_sphere(const eu_facet *f)
-{
-  return f->projection == EU_SPHERICAL && std::fabs(f->hfov - 2.0 * M_PI) < .000001 && f->width == 2 * f->height;
-}
+// (full_sphere: eu_context.h - the feathered synopsis asks the same question)
 
 // ---- PTO masks and lens crops on the device (eu_alpha.hip) ----------------------------------------
 

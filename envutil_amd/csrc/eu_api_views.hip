@@ -152,6 +152,8 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   std::vector<eu_src_dev> sd;
   if (multi)
     for (int f = 0; f < nsrc; f++) sd.push_back(srcs[f]->sd);
+  const bool feather = multi && trg->synopsis == EU_SYN_FEATHER;
+  const std::vector<eu_feather_dev> fth = feather ? feather_table(trg, srcs, nsrc) : std::vector<eu_feather_dev>();
   std::vector<float> taps;
   drain drain_on_exit{ st, st };          // the host vectors above are among what the call lets go of
   // the view buffers are rewritten on `st`, and reserve() may free them: the view calls before this one have to be
@@ -167,6 +169,10 @@ static int run_view_sequence(const char *who, const eu_target *trg, const eu_vie
   if (multi) HIPCHK(cur().views.src.reserve(sd.size()));
   HIPCHK(hipMemcpyAsync(cur().views.scal.p, sc.data(), sc.size() * sizeof(eu_view_dev), hipMemcpyHostToDevice, st));
   if (multi) HIPCHK(hipMemcpyAsync(cur().views.src.p, sd.data(), sd.size() * sizeof(eu_src_dev), hipMemcpyHostToDevice, st));
+  if (feather) {
+    HIPCHK(cur().views.fth.reserve(fth.size()));
+    HIPCHK(hipMemcpyAsync(cur().views.fth.p, fth.data(), fth.size() * sizeof(eu_feather_dev), hipMemcpyHostToDevice, st));
+  }
   if ((rc = upload_view_taps(trg, st, &taps))) return rc;
   HIPCHK(hipStreamSynchronize(st));
 
@@ -258,6 +264,7 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
       p.width = trg->width; p.height = trg->height; p.row_begin = 0; p.row_end = trg->height;
       p.form = form; p.norm_mode = norm_mode; p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps;
       fill_synopsis(trg, srcs, nsrc, &p);
+      p.fth = p.mode == EU_MODE_FEATHER ? cur().views.fth.p : nullptr;
       p.col = cur().views.col.p; p.row = cur().views.row.p; p.taps = cur().views.taps.dev.p; p.srcs = cur().views.src.p;
     }
     int launch(int nv, const eu_view_strides &vs, const eu_switches &, hipStream_t st)

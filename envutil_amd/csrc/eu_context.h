@@ -115,6 +115,7 @@ struct context {
     eu_dev_buf<eu_src_dev> src;                   // the facets' evaluator parameters
     eu_dev_buf<float> rej;                        // early-miss tables
     eu_dev_buf<eu_generic> gen;                   // the translated facets' transformations
+    eu_dev_buf<eu_feather_dev> fth;               // the feathered synopsis' edge-weight table
   } mplan;
   struct {
     eu_dev_buf<int> wl;                           // eu_render4.hip work list (count, done, tile ids)
@@ -135,7 +136,8 @@ struct context {
     eu_dev_buf<float> col, row, stage;
     held_table taps;
     eu_dev_buf<eu_src_dev> src;
-    eu_readers readers;                           // scal, col, row, taps, src
+    eu_dev_buf<eu_feather_dev> fth;               // the feathered synopsis' edge-weight table
+    eu_readers readers;                           // scal, col, row, taps, src, fth
   } views;
   // eu_hip_render_layers: the one camera's stepper tables (built on the host per call), the tap table, the layer
   // table and the staging of a host output - all its own, like the view calls' buffers
@@ -239,8 +241,18 @@ inline size_t frame_row_bytes(const eu_target *t)
 
 int local_rows(int height, int band_rows, int band_count, int band_index);
 int check_target(const eu_target *t);
+int check_synopsis(const eu_target *t);
 std::vector<float> biased_taps(const float *taps, int ntaps);
 void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_multi_params *p);
+
+// the source is a full sphere: the load gives it the two-axis periodic prefilter and pole rows (eu_api_source.hip),
+// and the feathered synopsis gives it no border on axis 1
+inline bool full_sphere(const eu_facet *f)
+{
+  return f->projection == EU_SPHERICAL && std::fabs(f->hfov - 2.0 * M_PI) < .000001 && f->width == 2 * f->height;
+}
+// the per-job table of the feathered synopsis (eu_feather_dev, eu_launch.h), one entry per facet
+std::vector<eu_feather_dev> feather_table(const eu_target *t, eu_source *const *srcs, int nsrc);
 
 // the handle and its container (not the copies on other device slots: eu_hip_source_release)
 inline void destroy_source(eu_source *s)

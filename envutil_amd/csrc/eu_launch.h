@@ -14,6 +14,18 @@
 #define EU_REJ_HDR 16
 #define EU_REJ_STRIDE (EU_REJ_HDR + EU_REJ_N)
 
+// how a multi-facet job composes its facets: eu_target::synopsis (EU_SYN_*), one kernel family per mode
+enum { EU_MODE_PANORAMA = 0, EU_MODE_HDR = 1, EU_MODE_FEATHER = 2 };
+
+// feathered seams (eu_synopsis_feather): what the edge weight of one facet needs. It belongs to the JOB - the
+// width is the target's - and not to the resident source, so it travels beside eu_src_dev: 16 bytes per facet,
+// read wave-uniformly through the scalar cache.
+struct eu_feather_dev {
+  float rcp;                 // float(1.0 / width_px): the ramp's slope per window pixel
+  float lim_x, lim_y;        // float(window size) - 0.5f: the far border in pixel coordinates
+  int border;                // bit 0: axis 0 has a border, bit 1: axis 1; 0: the weight is 1
+};
+
 struct eu_multi_params {
   int width, height, row_begin, row_end;
   int form, norm_mode, twine, ntaps, nch, nfct, plus;
@@ -25,7 +37,9 @@ struct eu_multi_params {
   long long out_stride;
   int tiles_x, tiles_y;
   int band_shift, band_count, band_index;   // eu_frame_row
-  int hdr, hdr_low, hdr_high;               // _hdr_merge_syn: the facets that rule the shadows / the highlights
+  int mode;                                 // EU_MODE_*
+  int hdr_low, hdr_high;                    // _hdr_merge_syn: the facets that rule the shadows / the highlights
+  const eu_feather_dev *fth;                // [nfct], EU_MODE_FEATHER only: the job's edge-weight table
   const eu_generic *gen;                    // [nfct] or nullptr: facets stepped by generic_stepper (translation)
   eu_inv_planar inv;                        // tf22 of a --single job
   const float *rej;                         // [nfct][EU_REJ_STRIDE] or nullptr: early-miss tables (eu_multi_maybe)

@@ -508,6 +508,90 @@ __device__ __forceinline__ void eu_synopsis_hdr(const eu_multi_params &p, const 
   }
 }
 
+__device__ __forceinline__ float eu_std_min(float a, float b) { return b < a ? b : a; }
+
+#define EU_FEATHER_FLOOR 0x1p-16f
+
+// Feathered seams. No counterpart in the reference: the definition is this project's own (DESIGN.md 1,
+// tests/feather_model.py restates it in numpy). Every facet the ray HITS is weighted by its distance to the
+// nearest border of the facet's window, a ramp of the job's width clamped to [2^-16, 1]; a miss contributes nothing
+// at all (unlike eu_synopsis_hdr, where it is a zero pixel) - also for a facet of another channel count. With
+// alpha the weight is alpha * ramp on the de-associated colour, as _hdr_merge_syn treats alpha. A pixel that one
+// facet alone covers is that facet's pixel as it is, so where facets do not overlap the frame is eu_synopsis's.
+// Per pixel, nothing per vector, nothing kept per facet: no limit on the facets, no dynamic LDS.
+// Every operation is one of its own (-ffp-contract=off); the facets are walked in job order.
+template <int NCH, int DEG, bool GEN>
+__device__ __forceinline__ void eu_synopsis_feather(const eu_multi_params &p, const eu_pix &px,
+                                                    bool tap, float cx, float cy, float *out)
+{
+  constexpr bool alpha = NCH == 2 || NCH == 4;
+  constexpr int ncol = alpha ? NCH - 1 : NCH;
+  float qsum = 0.0f, amax = 0.0f;
+  float acc[ncol], one[NCH];
+  int count = 0;
+#pragma unroll
+  for (int c = 0; c < ncol; c++) acc[c] = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NCH; c++) one[c] = 0.0f;
+#pragma unroll 1
+  for (int f = 0; f < p.nfct; f++) {
+    float rx, ry, rz, sx = 0.0f, sy = 0.0f;
+    int face;
+    eu_syn_ray<GEN>(p, f, px, tap, cx, cy, rx, ry, rz);
+    const eu_src_dev &s = p.srcs[f];
+    bool hit = false;
+    if (!s.mask_all) {
+      // whole wavefront provably outside the facet's window: no exact test
+      if (__ballot(eu_multi_maybe(p, f, s, rx, ry, rz))) hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    } else {
+      hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    }
+    if (!__ballot(hit)) continue;               // a wavefront without a hit: no gathers
+    float v[NCH];
+    eu_env_facet<NCH, DEG>(s, hit, sx, sy, v);
+    const eu_feather_dev &w = p.fth[f];         // f is wave-uniform: scalar loads
+    float e = 1.0f;
+    if (w.border) {
+      const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
+      const float d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
+      e = d * w.rcp;
+      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
+      e = e > 1.0f ? 1.0f : e;
+    }
+    if (hit) {
+      float q = e;
+      if constexpr (!alpha) {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) acc[c] = acc[c] + v[c] * q;
+      } else {
+        const float a = v[NCH - 1];
+        q = a * e;
+#pragma unroll
+        for (int c = 0; c < ncol; c++) {
+          float dc = 0.0f;
+          if (a > 0.000001f) dc = v[c] / a;
+          acc[c] = acc[c] + dc * q;
+        }
+        amax = eu_std_max(amax, a);
+      }
+      qsum = qsum + q;
+      if (count == 0) {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) one[c] = v[c];
+      }
+      count++;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < ncol; c++) {
+    float t = acc[c] / qsum;
+    if (!(qsum > 0.0f)) t = 0.0f;
+    if constexpr (alpha) t = t * amax;
+    out[c] = count == 1 ? one[c] : t;           // (no facet: acc, qsum and `one` are zero)
+  }
+  if constexpr (alpha) out[NCH - 1] = count == 1 ? one[NCH - 1] : amax;
+}
+
 // The synopsis kernels are bound by the latency of their gathers (six 1-GB sources,
 // little locality) more than by anything else: capping the registers for 5 waves per
 // SIMD (a few spills) beats the 2-3 waves the allocator settles on by itself - config 5:
@@ -517,39 +601,39 @@ __device__ __forceinline__ void eu_synopsis_hdr(const eu_multi_params &p, const 
 #endif
 #define EU_MULTI_OCC __attribute__((amdgpu_waves_per_eu(EU_MULTI_WAVES, EU_MULTI_WAVES)))
 
-// The instantiation of a job, for both launchers: launch.go<DEG, HDR, GEN, BIG>(bytes of dynamic LDS) starts
-// the launcher's own kernel (the view form has no generic stepper and maps GEN onto the one it has).
+// The instantiation of a job, for both launchers: launch.go<DEG, SYN, GEN, BIG>(bytes of dynamic LDS) starts
+// the launcher's own kernel (the view form has no generic stepper and maps GEN onto the one it has). SYN is the
+// job's EU_MODE_*; hdr_merge and feather have the same set: degrees 0 to 3, the run-time degree, GEN.
 template <bool PLUS, class L>
 static int eu_multi_ladder(const eu_multi_params &p, int degree, const L &launch)
 {
-  if (PLUS && !p.hdr && p.nfct > EU_MULTI_MAXF) {
+  const bool pano = p.mode == EU_MODE_PANORAMA;
+  if (PLUS && pano && p.nfct > EU_MULTI_MAXF) {
     // the one instantiation serves jobs with and without generic-stepper facets
-    if constexpr (PLUS) launch.template go<-1, false, true, true>(0);
+    if constexpr (PLUS) launch.template go<-1, EU_MODE_PANORAMA, true, true>(0);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   // alpha compositing keeps z (and, for up to EU_MULTI_KEEP facets, the source coordinate) of every facet per
   // thread in LDS
-  const size_t lds = PLUS && !p.hdr ? (size_t)(p.nfct <= EU_MULTI_KEEP ? 3 : 1) * p.nfct * 256 * sizeof(float) : 0;
-  if (p.gen) {
-    if (p.hdr) launch.template go<-1, true, true, false>(lds);
-    else launch.template go<-1, false, true, false>(lds);
-  } else if (p.hdr) {
-    switch (degree) {
-      case 0: launch.template go<0, true, false, false>(lds); break;
-      case 1: launch.template go<1, true, false, false>(lds); break;
-      case 2: launch.template go<2, true, false, false>(lds); break;
-      case 3: launch.template go<3, true, false, false>(lds); break;
-      default: launch.template go<-1, true, false, false>(lds); break;
-    }
-  } else {
-    switch (degree) {
-      case 0: launch.template go<0, false, false, false>(lds); break;
-      case 1: launch.template go<1, false, false, false>(lds); break;
-      case 2: launch.template go<2, false, false, false>(lds); break;
-      case 3: launch.template go<3, false, false, false>(lds); break;
-      default: launch.template go<-1, false, false, false>(lds); break;
-    }
+  const size_t lds = PLUS && pano ? (size_t)(p.nfct <= EU_MULTI_KEEP ? 3 : 1) * p.nfct * 256 * sizeof(float) : 0;
+#define EU_LADDER_MODE(M)                                                            \
+  if (p.gen) launch.template go<-1, M, true, false>(lds);                            \
+  else switch (degree) {                                                             \
+    case 0: launch.template go<0, M, false, false>(lds); break;                      \
+    case 1: launch.template go<1, M, false, false>(lds); break;                      \
+    case 2: launch.template go<2, M, false, false>(lds); break;                      \
+    case 3: launch.template go<3, M, false, false>(lds); break;                      \
+    default: launch.template go<-1, M, false, false>(lds); break;                    \
   }
+  if (p.mode == EU_MODE_FEATHER) {
+    if (!p.fth) return -2;
+    EU_LADDER_MODE(EU_MODE_FEATHER)
+  } else if (p.mode == EU_MODE_HDR) {
+    EU_LADDER_MODE(EU_MODE_HDR)
+  } else {
+    EU_LADDER_MODE(EU_MODE_PANORAMA)
+  }
+#undef EU_LADDER_MODE
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -34,7 +34,7 @@ __device__ unsigned long long eu_multi_stamp_acc[1024 * 4];      // sharded by w
 // GEN: some facet of the job is stepped by generic_stepper (translation, --single); only the run-time-degree
 // variants are instantiated with it
 // BIG: alpha compositing of more than 64 facets (eu_synopsis_big)
-template <int NCH, int DEG, bool PLUS, bool HDR, bool GEN, bool BIG>
+template <int NCH, int DEG, bool PLUS, int SYN, bool GEN, bool BIG>
 __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const eu_multi_params p)
 {
   extern __shared__ float eu_dyn_lds[];
@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
   sl.sy = sl.sx + p.nfct * 256;
   float out[NCH];
   if (!p.twine) {
-    if constexpr (HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, false, 0.0f, 0.0f, out);
+    if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, GEN>(p, px, false, 0.0f, 0.0f, out);
+    else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, false, 0.0f, 0.0f, out);
     else if constexpr (BIG) eu_synopsis_big<NCH, DEG, GEN>(p, px, live, false, 0.0f, 0.0f, sl, out);
     else eu_synopsis<NCH, DEG, PLUS, GEN>(p, px, live, false, 0.0f, 0.0f, sl, out);
   } else {
@@ -65,7 +66,8 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
     for (int k = 0; k < p.ntaps; k++) {
       const float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
       float help[NCH];
-      if constexpr (HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, true, cx, cy, help);
+      if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, GEN>(p, px, true, cx, cy, help);
+      else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, true, cx, cy, help);
       else if constexpr (BIG) eu_synopsis_big<NCH, DEG, GEN>(p, px, live, true, cx, cy, sl, help);
       else eu_synopsis<NCH, DEG, PLUS, GEN>(p, px, live, true, cx, cy, sl, help);
 #pragma unroll
@@ -80,11 +82,11 @@ template <int NCH, bool PLUS>
 struct launch_multi {
   const eu_multi_params &p;
   hipStream_t st;
-  template <int DEG, bool HDR, bool GEN, bool BIG>
+  template <int DEG, int SYN, bool GEN, bool BIG>
   void go(size_t lds) const
   {
     dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS)), block(256);
-    hipLaunchKernelGGL((eu_render_multi_kernel<NCH, DEG, PLUS, HDR, GEN, BIG>), grid, block, lds, st, p);
+    hipLaunchKernelGGL((eu_render_multi_kernel<NCH, DEG, PLUS, SYN, GEN, BIG>), grid, block, lds, st, p);
   }
 };
 

@@ -5,7 +5,7 @@
 // (eu_render_views.hip) builds them from one scalar block per (view, facet); the kernel below has the view on
 // blockIdx.y and offsets col, row and out by it.
 //
-//   eu_views_multi_kernel<NCH, DEG, PLUS, HDR, BIG>   eu_render_multi_kernel's body on the tables of view blockIdx.y
+//   eu_views_multi_kernel<NCH, DEG, PLUS, SYN, BIG>   eu_render_multi_kernel's body on the tables of view blockIdx.y
 //
 // It calls the device functions of eu_multi_dev.h with GEN = false (a facet with translation is refused: it is
 // stepped by the generic stepper, whose tf3d_t is host work per view) and without early-miss tables. The
@@ -30,7 +30,7 @@
 
 #ifdef EU_MULTI_NCH
 
-template <int NCH, int DEG, bool PLUS, bool HDR, bool BIG>
+template <int NCH, int DEG, bool PLUS, int SYN, bool BIG>
 __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const eu_multi_params p0, const eu_view_strides vs)
 {
   extern __shared__ float eu_dyn_lds[];
@@ -58,7 +58,8 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
   sl.sy = sl.sx + p.nfct * 256;
   float out[NCH];
   if (!p.twine) {
-    if constexpr (HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, false, 0.0f, 0.0f, out);
+    if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, false>(p, px, false, 0.0f, 0.0f, out);
+    else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, false, 0.0f, 0.0f, out);
     else if constexpr (BIG) eu_synopsis_big<NCH, DEG, false>(p, px, live, false, 0.0f, 0.0f, sl, out);
     else eu_synopsis<NCH, DEG, PLUS, false>(p, px, live, false, 0.0f, 0.0f, sl, out);
   } else {
@@ -67,7 +68,8 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
     for (int k = 0; k < p.ntaps; k++) {
       const float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
       float help[NCH];
-      if constexpr (HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, true, cx, cy, help);
+      if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, false>(p, px, true, cx, cy, help);
+      else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, true, cx, cy, help);
       else if constexpr (BIG) eu_synopsis_big<NCH, DEG, false>(p, px, live, true, cx, cy, sl, help);
       else eu_synopsis<NCH, DEG, PLUS, false>(p, px, live, true, cx, cy, sl, help);
 #pragma unroll
@@ -78,18 +80,18 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
   eu_put<NCH>(p.out + (long long)(px.y - p.row_begin) * p.out_stride, px.x, out);
 }
 
-// GEN falls away: the one kernel of each (DEG, HDR, BIG)
+// GEN falls away: the one kernel of each (DEG, SYN, BIG)
 template <int NCH, bool PLUS>
 struct launch_views_multi {
   const eu_multi_params &p;
   const eu_view_strides &vs;
   int nviews;
   hipStream_t st;
-  template <int DEG, bool HDR, bool GEN, bool BIG>
+  template <int DEG, int SYN, bool GEN, bool BIG>
   void go(size_t lds) const
   {
     dim3 grid((unsigned)eu_xcd_grid(p.tiles_x, p.tiles_y, EU_UNIT_ROWS), (unsigned)nviews), block(256);
-    hipLaunchKernelGGL((eu_views_multi_kernel<NCH, DEG, PLUS, HDR, BIG>), grid, block, lds, st, p, vs);
+    hipLaunchKernelGGL((eu_views_multi_kernel<NCH, DEG, PLUS, SYN, BIG>), grid, block, lds, st, p, vs);
   }
 };
 

@@ -128,6 +128,9 @@ struct arguments : public facet_base
   std::string output, split, synopsis = "panorama", pto_file, twf_file, projection_str;
   // envutil_main.cc:400-437: the working space and the output's default to "Linear", the input's to "" (the file's own)
   std::string input_colour_space, working_colour_space = "Linear", colour_space = "Linear";
+  // --synopsis feather: the width of the blending ramp in source pixels, 0: half the shorter side of each facet's
+  // window (eu_target::feather)
+  double feather = 0.0;
   int solo = -1, single = -1, mask_for = -1;
   std::vector<std::array<float, 3>> twine_spread;
   int support_min = 8, tile_size = 64;
@@ -299,7 +302,8 @@ struct hip_dispatch : public dispatch_base
     if ((ninputs == 9) != !args.twine_spread.empty()) return EU_ERR_ARGUMENT;
     if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples && !args.p_output_rgbe && !args.p_output_ycbcr) return EU_ERR_ARGUMENT;
     // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
-    if (args.synopsis != "panorama" && args.synopsis != "hdr_merge") return EU_ERR_ARGUMENT;
+    // ("feather" is this project's own: eu_target::feather)
+    if (args.synopsis != "panorama" && args.synopsis != "hdr_merge" && args.synopsis != "feather") return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
     if (args.single >= int(args.facet_spec_v.size()) || args.solo >= int(args.facet_spec_v.size())) return EU_ERR_ARGUMENT;
     std::vector<eu_source *> srcs;
@@ -420,7 +424,8 @@ struct hip_dispatch : public dispatch_base
       t.crop_x0 = args.p_crop_x0; t.crop_y0 = args.p_crop_y0; t.crop_w = w; t.crop_h = h;
     }
     t.row_begin = 0; t.row_end = h; t.stage = 0;
-    t.synopsis = args.synopsis == "hdr_merge" ? EU_SYN_HDR_MERGE : EU_SYN_PANORAMA;
+    t.synopsis = args.synopsis == "hdr_merge" ? EU_SYN_HDR_MERGE : args.synopsis == "feather" ? EU_SYN_FEATHER : EU_SYN_PANORAMA;
+    t.feather = args.feather;
     // --single: args carries the facet's geometry ((facet_base&) args = fspec); its lens and translation
     // parameters reach the library through eu_target.single
     eu_facet single_fct {};

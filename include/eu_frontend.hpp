@@ -147,7 +147,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
     { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 }, { "--frames", 2 }, { "--ycbcr_matrix", 1 },
-    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 } };
+    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 }, { "--feather", 1 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
@@ -207,7 +207,17 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   a.yaw = fl("--yaw", 0.0f); a.pitch = fl("--pitch", 0.0f); a.roll = fl("--roll", 0.0f);
   a.brighten = fl("--brighten", 1.0f);
   a.projection_str = str("--projection", "rectilinear");
+  // --synopsis feather (no counterpart in the reference: eu_hip.h, eu_target::feather) and its --feather WIDTH in
+  // source pixels, 0 for the default. ArgParse's get<float> again; a double from there on, as the library takes it
+  a.feather = fl("--feather", 0.0f);
   if (bad) return false;
+  if (has("--feather")) {
+    if (!std::isfinite(a.feather) || a.feather < 0.0) {
+      err = "--feather " + opt["--feather"] + ": a width in source pixels, 0 (the default: half the facet's shorter side) or more";
+      return false;
+    }
+    if (a.synopsis != "feather") { err = "--feather goes with --synopsis feather"; return false; }
+  }
   if (a.prefilter_degree < 0) a.prefilter_degree = a.spline_degree;
   a.projection = projection_t(projection_index(a.projection_str));
   if (a.projection == PRJ_NONE) { err = "unknown projection " + a.projection_str; return false; }

@@ -142,7 +142,9 @@ typedef struct eu_target {
   /* args.synopsis (envutil_main.cc:232, dispatched at envutil_payload.cc:2302-2318): how a job
    * with several facets composes them. EU_SYN_PANORAMA: voronoi_syn (1/3 channels) or
    * voronoi_syn_plus (2/4 channels); EU_SYN_HDR_MERGE: _hdr_merge_syn (envutil_payload.cc:
-   * 1325-1626), the quality-weighted sum of ALL facets. Ignored for single-facet jobs.        */
+   * 1325-1626), the quality-weighted sum of ALL facets; EU_SYN_FEATHER: feathered seams, this library's own
+   * (the reference has no blending): every facet the ray hits, weighted by its distance to the nearest border
+   * of the facet's window - see `feather` below. Ignored for single-facet jobs.                 */
   int32_t synopsis;
   /* args.single (envutil_main.cc:1161-1180; envutil_payload.cc:2058-2069): the target RECREATES this facet.
    * Projection, size, extent and orientation above are then the facet's own ((facet_base&) args = fspec);
@@ -151,6 +153,20 @@ typedef struct eu_target {
    * tf_ex_facet with the inverse planar transformation (pto_planar<T, L, true>, inverse_lcp) and the
    * inverse translation. Host pointer, read during the call; NULL: an ordinary target.            */
   const eu_facet *single;
+  /* EU_SYN_FEATHER: the width of the blending ramp in SOURCE pixels; 0, the default: half the shorter side of
+   * each facet's window, so that the ramp reaches the window's centre. Per facet the ray hits, in float32, one
+   * operation at a time, facets in job order:
+   *   dx = min(sx + 0.5, (window_width - 0.5) - sx), dy likewise   (sx, sy: the source coordinate, centres whole)
+   *   d  = the smaller over the axes that have a border - not axis 0 of a 360-degree spherical / cylindrical
+   *        source, not axis 1 of a full sphere, neither of a cubemap or of a fisheye of 360 degrees or more
+   *   e  = clamp(d * float(1.0 / width), 2^-16, 1), or 1 without a bordered axis
+   *   no alpha: acc += pixel * e, qsum += e;   alpha a: acc += (a > 1e-6 ? colour / a : 0) * (a * e),
+   *   qsum += a * e, amax = max(amax, a)
+   * and the pixel is acc / qsum (0 unless qsum > 0), with alpha times amax and alpha = amax. A miss contributes
+   * nothing; a pixel ONE facet hits is that facet's pixel as it is; none: zeros. With --mask_for N (mask_paint)
+   * the frame is facet N's normalised blend weight. Negative or non-finite: EU_ERR_ARGUMENT. Other synopses and
+   * single-facet jobs ignore the field, but the plan cache hashes the structure's bytes: set it (0) always.  */
+  double feather;
 } eu_target;
 
 /* How the library would lay the job's rows out (eu_api_render.hip: launch-level choice between
@@ -189,7 +205,7 @@ unsigned long long eu_hip_listed_tiles(void);
 int  eu_hip_band_rows(int height, int band_rows, int band_count, int band_index);
 
 enum { EU_OUT_FLOAT = 0, EU_OUT_SRGBA8 = 1 };
-enum { EU_SYN_PANORAMA = 0, EU_SYN_HDR_MERGE = 1 };
+enum { EU_SYN_PANORAMA = 0, EU_SYN_HDR_MERGE = 1, EU_SYN_FEATHER = 2 };
 
 /* ---- device / lifecycle ------------------------------------------------- */
 int  eu_hip_device_count(void);
@@ -498,8 +514,8 @@ typedef struct eu_view {
 int  eu_hip_render_views(const eu_target *trg, const eu_view *views, int nviews, eu_source *src, float *out,
                          size_t out_row_stride_bytes, size_t out_view_stride_bytes, int out_on_device, void *stream);
 /* The same for a multi-facet job: view k is bit for bit the frame eu_hip_render(trg', srcs, nsrc, ...) gives, trg'
- * being `trg` with view k's orientation and extent; trg->synopsis selects panorama (voronoi_syn / voronoi_syn_plus)
- * or hdr_merge as there. Layout, strides, `out_on_device` and `stream` are those of eu_hip_render_views. nsrc == 1
+ * being `trg` with view k's orientation and extent; trg->synopsis selects panorama (voronoi_syn / voronoi_syn_plus),
+ * hdr_merge or feather as there. Layout, strides, `out_on_device` and `stream` are those of eu_hip_render_views. nsrc == 1
  * forwards to eu_hip_render_views. Per (view, facet) the host computes one block of scalars - the basis
  * rotate(r_cam(view), r_fct(facet)) - and nothing else; the facets' parameters and the tap table go up once per
  * call. A view's tables take nsrc * (6 * width + 24 * height) * 4 bytes of the EU_HIP_VIEWS_MAX_KB bound.

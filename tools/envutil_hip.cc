@@ -341,6 +341,12 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
   }
   const auto *dp = static_cast<const hip_dispatch *>(get_dispatch());
   if (args.verbose) std::printf("using %s (%s)\n", dp->hwy_target_name.c_str(), dp->hwy_target_str.c_str());
+  if (args.verbose && args.facet_spec_v.size() > 1) {
+    // how the facets are composed; feather: the ramp's width in source pixels
+    if (args.synopsis != "feather") std::printf("synopsis %s\n", args.synopsis.c_str());
+    else if (args.feather > 0.0) std::printf("synopsis feather, width %g source pixels\n", args.feather);
+    else std::printf("synopsis feather, width: half of each facet's shorter side\n");
+  }
   if (!args.twine_setup()) {
     std::fprintf(stderr, "envutil_hip: cannot read the tap table %s\n", args.twf_file.c_str());
     return 2;
@@ -552,7 +558,8 @@ int main(int argc, const char **argv)
         "envutil_hip - envutil's reprojection on an MI355X (options as in envutil, envutil_main.cc:190-372)\n"
         "  source:   --facet IMAGE PROJECTION HFOV YAW PITCH ROLL (repeatable) | --photo IMAGE | --pto FILE [--pto_line LINE]\n"
         "            projections: spherical cylindrical rectilinear stereographic fisheye cubemap biatan6\n"
-        "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge\n"
+        "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge|feather\n"
+        "            --feather WIDTH  with --synopsis feather: the blending ramp in source pixels (0: half the shorter side)\n"
         "  rays:     --ray_map FILE.pfm  the single facet's image at the rays x y z of a 3-channel PFM, in the facet's\n"
         "            frame (no yaw / pitch / roll, no twining); the output has the map's size\n"
         "  layers:   --layer IMAGE OUTPUT (repeatable)  a further picture of the single facet's geometry - same size and\n"
