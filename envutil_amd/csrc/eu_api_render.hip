@@ -368,24 +368,28 @@ int launch_staged(const eu_render_params *p, const eu_switches &sw, hipStream_t 
   const unsigned long long ntiles = eu_staged_tiles(p->width, p->row_begin, p->row_end);
   if (ntiles > EU4_WL_MAX_TILES) return -2;
   // every tile of the launch may be listed: the capacity holds for all of them (eu_worklist.h). A buffer that grows
-  // starts with an empty header - the entries need no clearing, the counters say how many of them count - and a
-  // smaller job behind a larger one finds the lists emptied by the larger one's last workgroup
-  const size_t need = eu_render4_worklist_ints((size_t)ntiles);
+  // starts with both sets of counters empty - the entries need no clearing, the counters say how many of them count -
+  // and a smaller job behind a larger one finds its set emptied by the second kernel of the pair before it
+  const size_t need = eu_render4_worklist_buffer_ints((size_t)ntiles);
   if (cur().staged.wl.cap < need) {
     if (cur().staged.wl_pair.host_wait() != hipSuccess || cur().staged.wl.reserve(need) != hipSuccess) return -1;
-    if (hipMemsetAsync(cur().staged.wl.p, 0, eu_render4_worklist_header_ints() * sizeof(int), st) != hipSuccess) {
+    if (hipMemsetAsync(cur().staged.wl.p, 0, eu_render4_worklist_clear_ints() * sizeof(int), st) != hipSuccess) {
       cur().staged.wl.cap = 0;
       return -1;
     }
   }
   eu_render_params q = *p;
-  q.wl = cur().staged.wl.p;
+  const int set = cur().staged.parity;
+  q.wl = EU4_WL_SET(cur().staged.wl.p, set);
   // the work list, the persistent kernel's queues and the cached plans belong to ONE launch pair at a time: `st` waits
   // for the pair before, the event moves behind this one - on any stream, for eu_hip_listed_tiles() the library's own too
   if (cur().staged.wl_pair.order_after(st) != hipSuccess) return -1;
-  const int rc = eu_launch_render4(&q, &sw, cur().plan.h_row.data(), cur().plan.h_row.size(), cur().plan.h_col.data(),
-                                   cur().plan.h_col.size(), cur().plan.plan_gen, st, launches);
-  if (rc || !*launches) return rc;
+  const int rc = eu_launch_render4(&q, EU4_WL_SET(cur().staged.wl.p, set ^ 1), &sw, cur().plan.h_row.data(), cur().plan.h_row.size(),
+                                   cur().plan.h_col.data(), cur().plan.h_col.size(), cur().plan.plan_gen, st, launches);
+  if (rc || !*launches || !ntiles) return rc;     // (a job of no tiles launches nothing)
+  // both launches went out: the pair behind this one takes the set this one has emptied
+  cur().staged.last_set = set;
+  cur().staged.parity = set ^ 1;
   return cur().staged.wl_pair.note(st) != hipSuccess ? -1 : 0;
 }
 
@@ -1026,12 +1030,18 @@ unsigned long long eu_hip_launch_count(void) { return cur().launches; }
 
 unsigned long long eu_hip_listed_tiles(void)
 {
-  // the direct-gather kernel's last workgroup leaves the sum of the lists' counters in the header; the event
-  // behind the pair is the library's own (the caller's stream may be gone by now)
-  int n = 0;
-  if (!cur().staged.wl.p || !cur().staged.wl_pair.recorded || cur().staged.wl_pair.host_wait() != hipSuccess) return 0;
-  if (hipMemcpy(&n, cur().staged.wl.p + EU4_WL_LISTED, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  return n > 0 ? (unsigned long long)n : 0ull;
+  // the last pair's set of counters stays as that pair left it until the next pair's second kernel empties it: the
+  // lists' counters come to the host and are added up here (a diagnostic call; 64 KB). The event behind the pair is
+  // the library's own (the caller's stream may be gone by now)
+  if (!cur().staged.wl.p || cur().staged.last_set < 0 || !cur().staged.wl_pair.recorded ||
+      cur().staged.wl_pair.host_wait() != hipSuccess)
+    return 0;
+  std::vector<int> h((size_t)EU4_WL_SHARD(EU4_SHARDS));
+  if (hipMemcpy(h.data(), EU4_WL_SET(cur().staged.wl.p, cur().staged.last_set), h.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  unsigned long long n = 0;
+  for (int s = 0; s < EU4_SHARDS; s++) n += (unsigned long long)std::max(0, h[(size_t)EU4_WL_SHARD(s)]);
+  return n;
 }
 
 int eu_hip_render_timed(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev,

@@ -118,7 +118,9 @@ struct context {
     eu_dev_buf<eu_feather_dev> fth;               // the feathered synopsis' edge-weight table
   } mplan;
   struct {
-    eu_dev_buf<int> wl;                           // eu_render4.hip work list (count, done, tile ids)
+    eu_dev_buf<int> wl;                           // eu_render4.hip work list: two sets of counters, tile ids (eu_worklist.h)
+    int parity = 0;                               // the set the NEXT launch pair uses; moves when both launches went out
+    int last_set = -1;                            // the set the last pair used, for eu_hip_listed_tiles(); -1: no pair yet
     eu_readers wl_pair;                           // wl and the staged kernels' cached plans: behind EVERY launch pair
   } staged;
   // eu_hip_render_rays keeps its own tap table (the plan's is part of the cached plan of eu_hip_render) and its

@@ -93,8 +93,10 @@ int eu_launch_render2(const eu_render_params *p, const eu_switches *sw, void *st
 // h_row, h_col: the host copies of the plan's row table (whole frame) and column table, plan_gen: changes whenever the stepper tables
 // change. *launches: kernels launched for the job - 0 where the plan of a lat/lon job says that the
 // direct-gather kernels are faster (eu_staged_worth; the plan stays cached). The cached plans and p->wl belong to
-// one launch pair at a time: the caller has ordered `stream` behind the pair launched before (launch_staged)
-int eu_launch_render4(const eu_render_params *p, const eu_switches *sw, const float *h_row, size_t h_row_floats,
+// one launch pair at a time: the caller has ordered `stream` behind the pair launched before (launch_staged).
+// p->wl is this pair's set of the work list's two, wl_next the other one, whose counters the pair empties for the
+// pair behind it (eu_worklist.h)
+int eu_launch_render4(const eu_render_params *p, int *wl_next, const eu_switches *sw, const float *h_row, size_t h_row_floats,
                       const float *h_col, size_t h_col_floats, unsigned long long plan_gen, void *stream, int *launches);
 // path: an eu_ray_path, as eu_select_ray_path() chose it
 int eu_launch_render_rays(const eu_rays_params *p, int path, void *stream);

@@ -37,6 +37,7 @@
 #include <vector>
 #include <algorithm>
 #include "eu_packed_dev.h"
+#include "eu_quad_gather.h"
 #include "eu_launch.h"
 #include "eu_polar_groups.h"
 
@@ -327,8 +328,9 @@ __global__ __launch_bounds__(64 * EU4_WAVES0, EU4_OCC0) void eu_render4s_kernel(
 
 // one 16x8 tile by direct gathers: (d+1)^2 taps from global memory, every scalar fallback of the
 // coordinate arithmetic (the work-list kernel's tile)
+// qrec: the wave's area for the pixel records of eu_quad_gather.h (degrees 2 and 3)
 template <int NCH, int DEG, int PRJ>
-__device__ __forceinline__ void eu4_direct_tile(const eu_render_params &p, const float *atab, int tile_y, int x0, int lane)
+__device__ __forceinline__ void eu4_direct_tile(const eu_render_params &p, const float *atab, float *qrec, int tile_y, int x0, int lane)
 {
   const eu_src_dev &s = p.src;
   const int lx = lane & 7, ly = lane >> 3;
@@ -364,11 +366,40 @@ __device__ __forceinline__ void eu4_direct_tile(const eu_render_params &p, const
   eu_f2 sx, sy;
   eu_i2 hit = eu_coord2<PRJ>(s, ry, sx, sy, atab);
   hit = hit & (eu_i2){ va ? -1 : 0, vb ? -1 : 0 };
-  float pxa[NCH], pxb[NCH];
-  eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
-  float *const orow = p.out + (long long)(yc - p.row_begin) * p.out_stride;
-  if (va) eu_put<NCH>(orow, xa, pxa);
-  if (vb) eu_put<NCH>(orow, xb, pxb);
+  if constexpr (DEG >= 2) {
+    // the windows' rows fetched by lane quads: records of the lane's two pixels, then 16 pixels - one tile row - per
+    // step with four lanes each. The wave reads what it wrote itself: its LDS operations complete in order
+    eu_qg_records<NCH, DEG>(s, sx, sy, hit, va, vb, qrec, lane);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int rows = min(EU4_TH, p.row_end - (p.row_begin + tile_y * EU4_TH));
+    const int i = lane & 3, xq = x0 + (lane >> 2);
+    float *orow = p.out + (long long)(tile_y * EU4_TH) * p.out_stride;
+    // two steps per turn: both steps' loads are in flight before the first sum
+    auto finish = [&](const eu_qg_taps<NCH, DEG> &w) {
+      float px[NCH];
+      eu_qg_sum<NCH, DEG>(s, w, px);
+      if (i == DEG && (w.flags & EU_QG_VALID)) eu_put<NCH>(orow, xq, px);
+      orow += p.out_stride;
+    };
+#pragma unroll 1
+    for (int k = 0; k < rows; k += 2) {
+      eu_qg_taps<NCH, DEG> wa, wb;
+      const bool two = k + 1 < rows;
+      eu_qg_fetch<NCH, DEG>(s, qrec, k * EU4_TW + (lane >> 2), i, wa);
+      if (two) eu_qg_fetch<NCH, DEG>(s, qrec, (k + 1) * EU4_TW + (lane >> 2), i, wb);
+      finish(wa);
+      if (two) finish(wb);
+    }
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    float pxa[NCH], pxb[NCH];
+    eu_eval2<NCH, DEG>(s, sx, sy, hit, pxa, pxb);
+    float *const orow = p.out + (long long)(yc - p.row_begin) * p.out_stride;
+    if (va) eu_put<NCH>(orow, xa, pxa);
+    if (vb) eu_put<NCH>(orow, xb, pxb);
+  }
 }
 
 #include "eu_share_groups.h"
@@ -430,19 +461,25 @@ __global__ __launch_bounds__(256) void eu_colplan_kernel(const eu_render_params 
 
 // ---------------------------------------------------------------------------
 // the direct-gather kernel: the tiles of the work list, (d+1)^2 taps from global memory,
-// every scalar fallback of the coordinate arithmetic; the last workgroup to finish
-// notes how many tiles the lists held and empties them for the next launch pair
+// every scalar fallback of the coordinate arithmetic. The lists it reads stay as they are
+// (eu_hip_listed_tiles adds them up); the launch empties the OTHER set of counters, `wl_next`,
+// for the pair behind it (eu_worklist.h): plain stores, nobody waits for anybody
 // ---------------------------------------------------------------------------
 template <int NCH, int DEG, int PRJ>
-__global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_params p, const eu4_plan w)
+__global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_params p, const eu4_plan w, int *wl_next)
 {
   __shared__ __attribute__((aligned(16))) float atab[EU_ATAN_TAB_FLOATS];
   if constexpr (PRJ != EU_CUBEMAP) {
     if (threadIdx.x < EU_ATAN_TAB_ENTRIES) eu_atan_tab_entry(threadIdx.x, atab + 8 * threadIdx.x);
   }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < EU4_WL_COUNTERS; i += (int)gridDim.x * 256)
+    __hip_atomic_store(wl_next + 16 * i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // the pixel records of a wave's tile (eu_quad_gather.h): 6 KB per wave
+  __shared__ __attribute__((aligned(16))) float qrec_all[DEG >= 2 ? EU4_WAVES * EU4_TW * EU4_TH * EU_QG_REC : 4];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // this wave's list: waves gid, gid + EU4_SHARDS, ... share list gid % EU4_SHARDS
+  float *const qrec = qrec_all + (DEG >= 2 ? wave * (EU4_TW * EU4_TH * EU_QG_REC) : 0);
   const int gid = blockIdx.x * EU4_WAVES + wave;
   const int sh = gid & (EU4_SHARDS - 1);
   const int nwork = __builtin_amdgcn_readfirstlane(
@@ -453,22 +490,7 @@ __global__ __launch_bounds__(256, 4) void eu_render4d_kernel(const eu_render_par
     const int id = __builtin_amdgcn_readfirstlane(p.wl[EU4_WL_ENTRIES + (size_t)k * EU4_SHARDS + sh]);
     const int tile_y = id / w.tiles16;
     const int x0 = (id - tile_y * w.tiles16) * EU4_TW;
-    eu4_direct_tile<NCH, DEG, PRJ>(p, atab, tile_y, x0, lane);
-  }
-  __shared__ int last, listed;
-  __syncthreads();
-  if (threadIdx.x == 0) { listed = 0; last = atomicAdd(p.wl + EU4_WL_DONE1, 1) == (int)gridDim.x - 1; }
-  __syncthreads();
-  if (last) {
-    // what the lists held, for eu_hip_listed_tiles(): every thread adds up the counters it is about to clear
-    int mine = 0;
-    for (int i = threadIdx.x; i < EU4_SHARDS; i += 256)
-      mine += __hip_atomic_load(p.wl + EU4_WL_SHARD(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    atomicAdd(&listed, mine);
-    for (int i = threadIdx.x; i <= EU4_SHARDS + 8; i += 256)         // the lists, the counter of this kernel, the staged kernel's queues
-      __hip_atomic_store(p.wl + 16 * i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(p.wl + EU4_WL_LISTED, listed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    eu4_direct_tile<NCH, DEG, PRJ>(p, atab, qrec, tile_y, x0, lane);
   }
 }
 
@@ -490,7 +512,7 @@ extern "C" unsigned long long eu_hip_boxtab_tiles(void) { return (unsigned long 
 #endif
 
 template <int NCH, int DEG, int PRJ>
-static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
+static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, int *wl_next, hipStream_t st)
 {
   // lat/lon sources: the persistent staged kernel (headline 1.13 vs 1.22 ms for the launch-level hybrid of the
   // direct-gather kernels); cubemap / biatan6 sources: one tile per workgroup (config 3 1.00 vs 1.22 ms)
@@ -530,33 +552,34 @@ static int launch4_ndp(const eu_render_params &p, const eu4_plan &w, hipStream_t
     hipLaunchKernelGGL((eu_render4s_kernel<NCH, DEG, PRJ>), grid, dim3(64 * EU4_WAVES0), 0, st, p, w);
   }
   if (hipGetLastError() != hipSuccess) return -1;
-  hipLaunchKernelGGL((eu_render4d_kernel<NCH, DEG, PRJ>), dim3(EU4_DIRECT_WGS), dim3(256), 0, st, p, w);
+  hipLaunchKernelGGL((eu_render4d_kernel<NCH, DEG, PRJ>), dim3(EU4_DIRECT_WGS), dim3(256), 0, st, p, w, wl_next);
   if (hipGetLastError() != hipSuccess) {
-    // the staged kernel has filled the lists and nobody will empty them: the next job must not append to them
-    (void)hipMemsetAsync(p.wl, 0, EU4_WL_ENTRIES * sizeof(int), st);
+    // the staged kernel has filled this set's lists and nobody has emptied the other's: the next job must not append to
+    // either (the caller does not advance the parity, so it is this set again)
+    (void)hipMemsetAsync(std::min(p.wl, wl_next), 0, eu_render4_worklist_clear_ints() * sizeof(int), st);
     return -1;
   }
   return 0;
 }
 
 template <int NCH, int DEG>
-static int launch4_nd(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
+static int launch4_nd(const eu_render_params &p, const eu4_plan &w, int *wl_next, hipStream_t st)
 {
   switch (p.src.prj) {
-    case EU_SPHERICAL: return launch4_ndp<NCH, DEG, EU_SPHERICAL>(p, w, st);
-    case EU_CUBEMAP: return launch4_ndp<NCH, DEG, EU_CUBEMAP>(p, w, st);
-    case EU_BIATAN6: return launch4_ndp<NCH, DEG, EU_BIATAN6>(p, w, st);
+    case EU_SPHERICAL: return launch4_ndp<NCH, DEG, EU_SPHERICAL>(p, w, wl_next, st);
+    case EU_CUBEMAP: return launch4_ndp<NCH, DEG, EU_CUBEMAP>(p, w, wl_next, st);
+    case EU_BIATAN6: return launch4_ndp<NCH, DEG, EU_BIATAN6>(p, w, wl_next, st);
   }
   return -2;
 }
 
 template <int NCH>
-static int launch4_n(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
+static int launch4_n(const eu_render_params &p, const eu4_plan &w, int *wl_next, hipStream_t st)
 {
   switch (p.src.degree) {
-    case 1: return launch4_nd<NCH, 1>(p, w, st);
-    case 2: return launch4_nd<NCH, 2>(p, w, st);
-    case 3: return launch4_nd<NCH, 3>(p, w, st);
+    case 1: return launch4_nd<NCH, 1>(p, w, wl_next, st);
+    case 2: return launch4_nd<NCH, 2>(p, w, wl_next, st);
+    case 3: return launch4_nd<NCH, 3>(p, w, wl_next, st);
   }
   return -2;
 }
@@ -755,18 +778,18 @@ void eu4_fill_plan(eu4_plan &w)
   w.l2p_magic = (1ull << 40) / (unsigned long long)w.l2p_bpe + 1;
 }
 
-int launch4(const eu_render_params &p, const eu4_plan &w, hipStream_t st)
+int launch4(const eu_render_params &p, const eu4_plan &w, int *wl_next, hipStream_t st)
 {
   switch (p.nch) {
-    case 3: return launch4_n<3>(p, w, st);
-    case 4: return launch4_n<4>(p, w, st);
+    case 3: return launch4_n<3>(p, w, wl_next, st);
+    case 4: return launch4_n<4>(p, w, wl_next, st);
   }
   return -2;
 }
 
 #ifdef EU5_STAMPS
 // diagnostic build: stamps of every tile, averaged per pass count / plan kind after the launch
-int launch4_stamped(const eu_render_params &p, eu4_plan &w, hipStream_t st)
+int launch4_stamped(const eu_render_params &p, eu4_plan &w, int *wl_next, hipStream_t st)
 {
   static unsigned long long *d_st = nullptr; static size_t st_cap = 0; static int dumps = 0;
   const size_t ntile_st = (size_t)w.tiles16 * p.tiles_y * 8;
@@ -774,7 +797,7 @@ int launch4_stamped(const eu_render_params &p, eu4_plan &w, hipStream_t st)
   if (st_cap < nst) { if (d_st) (void)hipFree(d_st); if (hipMalloc((void **)&d_st, nst * 8) != hipSuccess) return -1; st_cap = nst; }
   (void)hipMemsetAsync(d_st, 0, nst * 8, st);
   w.stamps = d_st;
-  const int rc_ = launch4(p, w, st);
+  const int rc_ = launch4(p, w, wl_next, st);
   if (rc_ == 0 && dumps < 2 && nst >= 8 * 4096) {
     dumps++;
     std::vector<unsigned long long> h(nst);
@@ -811,14 +834,14 @@ int launch4_stamped(const eu_render_params &p, eu4_plan &w, hipStream_t st)
 #endif
 }  // namespace
 
-extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *sw, const float *h_row, size_t h_row_floats,
+extern "C" int eu_launch_render4(const eu_render_params *pp, int *wl_next, const eu_switches *sw, const float *h_row, size_t h_row_floats,
                                  const float *h_col, size_t h_col_floats, unsigned long long plan_gen, void *stream, int *launches)
 {
   eu_render_params p = *pp;
   eu4_followers_last = 0; eu4_polar_last = 0;
   eu4_boxtab_last = 0; eu4_boxtab_tiles_last = 0;
   *launches = 2;
-  if (!eu_staged_covers(p) || !p.wl) return -2;
+  if (!eu_staged_covers(p) || !p.wl || !wl_next) return -2;
   p.tiles_y = (p.row_end - p.row_begin + EU4_TH - 1) / EU4_TH;
   eu4_plan w;
   w.tiles16 = (p.width + EU4_TW - 1) / EU4_TW;
@@ -841,8 +864,8 @@ extern "C" int eu_launch_render4(const eu_render_params *pp, const eu_switches *
   eu4_polar_plan = g4.polar_follower_tiles;
   eu4_boxtab_tiles_last = w.boxtab ? g4.boxtab_tiles : 0;
 #ifdef EU5_STAMPS
-  return launch4_stamped(p, w, st);
+  return launch4_stamped(p, w, wl_next, st);
 #else
-  return launch4(p, w, st);
+  return launch4(p, w, wl_next, st);
 #endif
 }

@@ -21,11 +21,18 @@
 #define EU4_SHARDS 1024
 // layout (ints); every counter on a 64-byte line of its own
 #define EU4_WL_SHARD(s) (16 * (s))                       // entries in list s
-#define EU4_WL_DONE1 (16 * EU4_SHARDS)                   // finished workgroups, direct-gather kernel
 #define EU4_WL_DYN(x) (16 * (EU4_SHARDS + 1 + (x)))       // eu_render5_kernel: next batch of XCD x's second loop, x = 0 .. 7
-#define EU4_WL_LISTED (16 * (EU4_SHARDS + 9))            // tiles the last launch pair listed: written when the lists are
-                                                         // emptied, kept until the next pair ends (eu_hip_listed_tiles)
+#define EU4_WL_COUNTERS (EU4_SHARDS + 9)                 // the lines that hold a counter: the lists, one spare, the queues
 #define EU4_WL_ENTRIES (16 * (EU4_SHARDS + 16))          // entry k of list s at + k * EU4_SHARDS + s
+// The buffer holds TWO sets of this layout, the second EU4_WL_SET_INTS ints behind the first: its counters are the
+// words 8 of the lines whose words 0 are the first set's (a line still serves one list or one queue), its entries
+// lie over the first set's, shifted. Launch pair n appends to and reads set n % 2, and its direct-gather kernel
+// stores zeros to the counters of the other set - pair n - 1's, which is through, and pair n + 1's, which starts
+// behind this kernel - so nobody counts finished workgroups to find the one that may empty the lists (2048 returning
+// atomics on one word, ~88 per microsecond, with every workgroup waiting for its own). The entries need no set of
+// their own: a pair's entries are dead when its second kernel ends, the counters are what eu_hip_listed_tiles() adds up.
+#define EU4_WL_SET_INTS 8
+#define EU4_WL_SET(buf, parity) ((buf) + ((parity) & 1) * EU4_WL_SET_INTS)
 
 // A tile id is an int: a launch has at most this many wave tiles (eu_select.h: eu_staged_covers)
 #define EU4_WL_MAX_TILES ((size_t)INT_MAX)
@@ -80,5 +87,13 @@ inline size_t eu_render4_worklist_ints(size_t ntiles)
   if (ntiles > EU4_WL_MAX_TILES) return 0;
   return EU4_WL_ENTRIES + census.fullest(ntiles) * EU4_SHARDS;
 }
+
+// ints of the buffer that holds both sets for such a launch (0 as above), and of what a host clears to empty both
+inline size_t eu_render4_worklist_buffer_ints(size_t ntiles)
+{
+  const size_t one = eu_render4_worklist_ints(ntiles);
+  return one ? one + EU4_WL_SET_INTS : 0;
+}
+inline size_t eu_render4_worklist_clear_ints(void) { return eu_render4_worklist_header_ints() + EU4_WL_SET_INTS; }
 
 #endif
