@@ -219,6 +219,40 @@ void test_paths()
   { eu_render_params p = headline(); p.src.degree = 2; expect("headline quadratic", p, d, EU_PATH_STAGED); }
 }
 
+// degrees 0 and 4 to 9 have no packed and no staged kernel (eu_packed_covers_source): whatever EU_HIP_R4, EU_HIP_HYBRID,
+// EU_HIP_KERNEL and EU_HIP_DIRECT say, and whatever the plan said, BASELINE's jobs at those degrees are the general kernel's
+void test_high_degrees()
+{
+  const eu_render_params base[6] = { headline(), config1(), config3(), config4(), twined(headline(), EU_NORM_DIV),
+                                     [] { eu_render_params p = config3(); p.src.prj = EU_BIATAN6; return p; }() };
+  const int degrees[7] = { 0, 4, 5, 6, 7, 8, 9 };
+  int n = 0, bad = 0;
+  for (const eu_render_params &b : base)
+    for (int deg : degrees)
+      for (int nch = 1; nch <= 4; nch++)
+        for (int r4 = -1; r4 <= 2; r4++)
+          for (int hybrid = 0; hybrid <= 2; hybrid++)
+            for (int kernel = 0; kernel <= 1; kernel++)
+              for (int direct = 0; direct <= 1; direct++)
+                for (int allowed = 0; allowed <= 1; allowed++) {
+                  eu_render_params p = b;
+                  p.src.degree = deg;
+                  p.nch = p.nch_out = p.src.nch = nch; p.src.es0 = nch;
+                  eu_switches s = defaults();
+                  s.r4 = r4; s.hybrid = hybrid; s.force_general = kernel; s.direct = direct;
+                  n++;
+                  if (eu_select_path(p, s, allowed != 0) != EU_PATH_GENERAL || eu_packed_covers(p) || eu_staged_covers(p) ||
+                      eu_packed_covers_source(p.src, p.nch, p.nch_out)) {
+                    bad++;
+                    printf("FAILED: degree %d nch %d R4=%d HYBRID=%d KERNEL=%d DIRECT=%d staged_allowed %d -> %s\n", deg, nch, r4,
+                           hybrid, kernel, direct, allowed, name(eu_select_path(p, s, allowed != 0)));
+                  }
+                }
+  char what[96];
+  snprintf(what, sizeof what, "high degrees: %d combinations, all general", n);
+  check(bad == 0 && n == 6 * 7 * 4 * 4 * 3 * 2 * 2 * 2, what);
+}
+
 void test_profiles()
 {
   check(eu_staged_default(headline()) && eu_staged_fast_profile(headline()), "headline: default staged job, FAST profile");
@@ -387,6 +421,7 @@ void test_read()
 int main()
 {
   test_paths();
+  test_high_degrees();
   test_profiles();
   test_runs();
   test_read();

@@ -92,6 +92,34 @@ void test_paths()
   }
 }
 
+// degrees 0 and 4 to 9: never the packed form, whatever the switches say
+void test_high_degrees()
+{
+  const int prjs[3] = { EU_SPHERICAL, EU_CUBEMAP, EU_BIATAN6 };
+  const int degrees[7] = { 0, 4, 5, 6, 7, 8, 9 };
+  int n = 0, bad = 0;
+  for (int prj : prjs)
+    for (int deg : degrees)
+      for (int nch = 1; nch <= 4; nch++)
+        for (int nin : { 3, 9 })
+          for (int r4 = -1; r4 <= 2; r4++)
+            for (int hybrid = 0; hybrid <= 2; hybrid++)
+              for (int kernel = 0; kernel <= 1; kernel++)
+                for (int direct = 0; direct <= 1; direct++) {
+                  eu_switches s = defaults();
+                  s.r4 = r4; s.hybrid = hybrid; s.force_general = kernel; s.direct = direct;
+                  n++;
+                  if (eu_select_ray_path(job(prj, deg, nch, nch, nin), s) != EU_RAYS_GENERAL) {
+                    bad++;
+                    printf("FAILED: prj %d degree %d nch %d ninputs %d R4=%d HYBRID=%d KERNEL=%d DIRECT=%d -> packed\n", prj, deg, nch,
+                           nin, r4, hybrid, kernel, direct);
+                  }
+                }
+  char what[96];
+  snprintf(what, sizeof what, "high degrees: %d combinations, all general", n);
+  check(bad == 0 && n == 3 * 7 * 4 * 2 * 4 * 3 * 2 * 2, what);
+}
+
 float from_bits(uint32_t u) { float f; memcpy(&f, &u, sizeof f); return f; }
 
 // every exponent class, both signs; `finite`: the class is a finite number, `zero`: +-0
@@ -170,6 +198,7 @@ int main(int argc, char **argv)
     return 0;
   }
   test_paths();
+  test_high_degrees();
   test_predicate();
   printf(failures ? "%d FAILED\n" : "all ok\n", failures);
   return failures ? 1 : 0;

@@ -80,6 +80,36 @@ void test_paths()
   { eu_render_params p = job(EU_FORM_BA, EU_SPHERICAL, 3, 3, 3, 0); p.src.es0 = 4; expect("texels not dense", p, d, EU_VIEWS_GENERAL); }
 }
 
+// degrees 0 and 4 to 9: never the packed form, whatever the switches say
+void test_high_degrees()
+{
+  const int prjs[3] = { EU_SPHERICAL, EU_CUBEMAP, EU_BIATAN6 };
+  const int forms[2] = { EU_FORM_BCA, EU_FORM_BA };
+  const int degrees[7] = { 0, 4, 5, 6, 7, 8, 9 };
+  int n = 0, bad = 0;
+  for (int prj : prjs)
+    for (int form : forms)
+      for (int deg : degrees)
+        for (int nch = 1; nch <= 4; nch++)
+          for (int twine = 0; twine < 2; twine++)
+            for (int r4 = -1; r4 <= 2; r4++)
+              for (int hybrid = 0; hybrid <= 2; hybrid++)
+                for (int kernel = 0; kernel <= 1; kernel++)
+                  for (int direct = 0; direct <= 1; direct++) {
+                    eu_switches s = defaults();
+                    s.r4 = r4; s.hybrid = hybrid; s.force_general = kernel; s.direct = direct;
+                    n++;
+                    if (eu_select_view_path(job(form, prj, deg, nch, nch, twine), s) != EU_VIEWS_GENERAL) {
+                      bad++;
+                      printf("FAILED: source %d form %d degree %d nch %d twine %d R4=%d HYBRID=%d KERNEL=%d DIRECT=%d -> packed\n", prj,
+                             form, deg, nch, twine, r4, hybrid, kernel, direct);
+                    }
+                  }
+  char what[96];
+  snprintf(what, sizeof what, "high degrees: %d combinations, all general", n);
+  check(bad == 0 && n == 3 * 2 * 7 * 4 * 2 * 4 * 3 * 2 * 2, what);
+}
+
 void test_switch()
 {
   unsetenv("EU_HIP_VIEWS_MAX_KB");
@@ -117,6 +147,7 @@ void test_chunks()
 int main()
 {
   test_paths();
+  test_high_degrees();
   test_switch();
   test_chunks();
   printf(failures ? "%d checks FAILED\n" : "all ok\n", failures);

@@ -30,6 +30,8 @@ def test_select_layer_path_chunks_and_switch_host_program():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and "all ok" in r.stdout
     assert r.stdout.count("-> packed") >= 144 and r.stdout.count("-> general") >= 14
+    # degrees 0 and 4 to 9 under every EU_HIP_R4 / HYBRID / KERNEL / DIRECT combination: never packed
+    assert "ok: high degrees: 16128 combinations, all general" in r.stdout
     assert r.stdout.count("EU_HIP_LAYERS_MAX") >= 5 + 6 * 4 * 9
     assert int(re.search(r"^EU_LAYERS_GROUP (\d+)$", r.stdout, re.M).group(1)) in (1, 2, 4)
 

@@ -21,7 +21,7 @@ def test_prefilter_brace_eval_sweep(shape):
     w, h, n = shape
     rng = np.random.default_rng(w * 1000 + h)
     core = rng.random((h, w, n), dtype=np.float32)
-    for deg in range(0, 8):
+    for deg in range(0, 10):
         for pdeg in sorted({deg, 0, 3}):
             for b0, b1 in [(1, 2), (2, 2), (0, 0), (3, 3), (1, 1), (2, 3)]:
                 r = refz.RefSpline(core, deg, b0, b1) if refz.available() else None
@@ -42,7 +42,7 @@ def test_spherical_prefilter_sweep(shape):
     w, h, n = shape
     rng = np.random.default_rng(w)
     core = rng.random((h, w, n), dtype=np.float32)
-    for deg in range(0, 6):
+    for deg in range(0, 10):
         for pdeg in sorted({deg, 3, 1}):
             r = refz.RefSpline(core, deg, 1, 2) if refz.available() else None
             o = euo.BSpline(core, deg, euo.PERIODIC, euo.REFLECT)

@@ -35,6 +35,8 @@ def test_select_ray_path_and_miss_predicate_host_program():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and "all ok" in r.stdout
     assert r.stdout.count("-> packed") >= 72 and r.stdout.count("-> general") >= 12
+    # degrees 0 and 4 to 9 under every EU_HIP_R4 / HYBRID / KERNEL / DIRECT combination: never packed
+    assert "ok: high degrees: 8064 combinations, all general" in r.stdout
 
 
 # The calls below run in a child process that is asked not to see a device (HIP_VISIBLE_DEVICES=-1), so that

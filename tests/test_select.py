@@ -19,3 +19,5 @@ def test_select_host_program():
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and "all ok" in r.stdout
+    # degrees 0 and 4 to 9 under every EU_HIP_R4 / HYBRID / KERNEL / DIRECT combination: never packed, never staged
+    assert "ok: high degrees: 16128 combinations, all general" in r.stdout

@@ -29,6 +29,8 @@ def test_select_view_path_chunks_and_switch_host_program():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FAILED" not in r.stdout and "all ok" in r.stdout
     assert r.stdout.count("-> packed") >= 144 and r.stdout.count("-> general") >= 14
+    # degrees 0 and 4 to 9 under every EU_HIP_R4 / HYBRID / KERNEL / DIRECT combination: never packed
+    assert "ok: high degrees: 16128 combinations, all general" in r.stdout
     assert r.stdout.count("EU_HIP_VIEWS_MAX_KB") >= 6
 
 
