@@ -15,7 +15,8 @@ from .api import (  # noqa: F401
     lib, lib_path, make_spread, render, render_timed, render_rays, render_rays_timed, render_views, render_layers, view_tables, View, sync, listed_tiles, launch_count, Rays, build, band_rows, band_frame_rows,
     encode_samples, render_samples, sample_steps, Encode,
     encode_rgbe, render_rgbe, Rgbe,
-    Ycbcr, Pixels, ycbcr_matrix, ycbcr_tables, ycbcr_floats, reload_scratch_release,
+    Ycbcr, Pixels, ycbcr_matrix, ycbcr_tables, ycbcr_floats, reload_scratch_release, blend_layers, multiband_levels, multiband_scratch_bytes,
+    multiband_scratch_release,
     YcbcrOut, ycbcr_forward, ycbcr_steps, ycbcr_planes, encode_ycbcr, render_ycbcr,
     layout_segments, facet_alpha, facet_alpha_dev, facet_alpha_rows, init_devices, device_slots, device_strips, render_devices,
     SPHERICAL, CYLINDRICAL, RECTILINEAR, STEREOGRAPHIC, FISHEYE, CUBEMAP, BIATAN6,

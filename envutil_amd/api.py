@@ -45,6 +45,7 @@ class Container(C.Structure):
 class Target(C.Structure):
     """struct eu_target"""
     _fields_ = [("projection", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("bands", C.c_int32),       # in what was the alignment gap in front of x0: size and offsets stay
                 ("x0", C.c_double), ("x1", C.c_double), ("y0", C.c_double), ("y1", C.c_double),
                 ("yaw", C.c_double), ("pitch", C.c_double), ("roll", C.c_double),
                 ("nchannels", C.c_int32), ("ntaps", C.c_int32),
@@ -75,7 +76,7 @@ class View(C.Structure):
 
 ROW_FLOATS = 24     # floats per row-table entry (EU_ROW_FLOATS)
 OUT_FLOAT, OUT_SRGBA8 = 0, 1
-SYN_PANORAMA, SYN_HDR_MERGE, SYN_FEATHER = 0, 1, 2
+SYN_PANORAMA, SYN_HDR_MERGE, SYN_FEATHER, SYN_MULTIBAND = 0, 1, 2, 4       # (3 is not assigned)
 
 
 def lib_path():
@@ -171,6 +172,11 @@ def lib():
     L.eu_hip_render_layers.argtypes = [vp, vp, i32, vp, C.c_size_t, C.c_size_t, i32, vp]
     L.eu_hip_view_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.eu_hip_layout_segments.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.eu_hip_blend_layers.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, i32, i32, i32, i32, i32,
+                                      i32, i32, vp, C.c_size_t, i32, vp]
+    L.eu_hip_multiband_scratch_bytes.argtypes = [vp, i32]
+    L.eu_hip_multiband_scratch_bytes.restype = C.c_size_t
+    L.eu_hip_multiband_levels.argtypes = [i32, i32, i32, i32]
     L.eu_hip_band_rows.argtypes = [i32, i32, i32, i32]
     L.eu_hip_band_rows.restype = i32
     L.eu_hip_malloc.argtypes = [vp, C.c_size_t]
@@ -1060,7 +1066,7 @@ class arguments:
     def __init__(self, projection, width, height, hfov, yaw=0.0, pitch=0.0, roll=0.0,
                  spline_degree=1, prefilter_degree=None, twine=0, twine_width=1.0,
                  twine_sigma=0.0, twine_threshold=0.0, support_min=8, tile_size=64,
-                 crop=None, tethered=False, synopsis="panorama", single=None, feather=0.0):
+                 crop=None, tethered=False, synopsis="panorama", single=None, feather=0.0, bands=0):
         # store_cropped + p_crop_x0/x1/y0/y1 (envutil_basic.h:684-687) as
         # (x0, x1, y0, y1); tethered: the job writes packed sRGBA8 words
         # (args.p_screen_data, envutil_payload.cc:524-530)
@@ -1069,9 +1075,14 @@ class arguments:
         self.tethered = tethered
         # args.synopsis (envutil_main.cc:232): how several facets are composed, "panorama" or "hdr_merge" - and
         # "feather", this project's own: feathered seams (eu_hip.h, eu_target::feather)
-        if synopsis not in ("panorama", "hdr_merge", "feather"):
-            raise ValueError("synopsis must be panorama, hdr_merge or feather")
+        # and "multiband", also this project's own: Burt-Adelson blending over `bands` pyramid levels (eu_target::bands)
+        if synopsis not in ("panorama", "hdr_merge", "feather", "multiband"):
+            raise ValueError("synopsis must be panorama, hdr_merge, feather or multiband")
         self.synopsis = synopsis
+        # the pyramid levels of the multiband synopsis above level 0; 0: as many as the frame allows, 8 at the most
+        if int(bands) != bands or bands < 0:
+            raise ValueError("bands must be a whole number of pyramid levels, 0 for the default")
+        self.bands = int(bands)
         # the width of the feathering ramp in source pixels; 0: half the shorter side of each facet's window
         feather = float(feather)
         if not math.isfinite(feather) or feather < 0.0:
@@ -1121,8 +1132,10 @@ class arguments:
             x0, x1, y0, y1 = self.p_crop
             t.crop_x0, t.crop_y0, t.crop_w, t.crop_h = x0, y0, x1 - x0, y1 - y0
         t.out_format = OUT_SRGBA8 if self.tethered else OUT_FLOAT
-        t.synopsis = {"panorama": SYN_PANORAMA, "hdr_merge": SYN_HDR_MERGE, "feather": SYN_FEATHER}[self.synopsis]
+        t.synopsis = {"panorama": SYN_PANORAMA, "hdr_merge": SYN_HDR_MERGE, "feather": SYN_FEATHER,
+                      "multiband": SYN_MULTIBAND}[self.synopsis]
         t.feather = self.feather
+        t.bands = self.bands
         if self.single is not None:
             self._single_c = self.single.c_struct()          # kept alive with the arguments object
             t.single = C.pointer(self._single_c)
@@ -1198,6 +1211,75 @@ def render(args, sources, nchannels=None, row_begin=0, row_end=None, stage=0, ou
     arr = (C.c_void_p * len(sources))(*[s.handle for s in sources])
     _check(lib().eu_hip_render(C.byref(t), arr, len(sources), out.ctypes.data_as(C.c_void_p),
                                w * och * 4, 0, None))
+    return out
+
+
+def multiband_levels(width, height, bands=0, wrap=False):
+    """eu_hip_multiband_levels: the pyramid levels above level 0 that a width x height frame gets for `bands`"""
+    return _check(lib().eu_hip_multiband_levels(width, height, bands, int(bool(wrap))))
+
+
+def multiband_scratch_bytes(args, nsources, nchannels=3):
+    """eu_hip_multiband_scratch_bytes: device scratch of a multiband job of `nsources` facets on this target"""
+    t = args.target(nchannels)
+    return int(lib().eu_hip_multiband_scratch_bytes(C.byref(t), nsources))
+
+
+def multiband_scratch_release():
+    """eu_hip_multiband_scratch_release: waits for every multiband job so far and frees the scratch they share"""
+    _check(lib().eu_hip_multiband_scratch_release())
+
+
+def _strided(a, what, tail):
+    """(address, strides in bytes, on_device) of a float32 array, numpy or torch on the device, whose last
+    len(tail) axes are dense with the shape `tail`"""
+    dev = _is_torch(a)
+    if dev:
+        import torch
+        if not a.is_cuda or a.dtype != torch.float32:
+            raise EuError(f"blend_layers: {what} is float32, numpy or on the device")
+        strides = tuple(4 * k for k in a.stride())
+        _settle(a)
+        ptr = a.data_ptr()
+    else:
+        if a.dtype != np.float32:
+            raise EuError(f"blend_layers: {what} is float32")
+        strides, ptr = tuple(a.strides), a.ctypes.data
+    dense = 4
+    for n, st in zip((1,) + tuple(tail[:0:-1]), strides[::-1]):
+        dense *= n
+        if st != dense:
+            raise EuError(f"blend_layers: the pixels of {what} are dense, only rows and pictures may be padded")
+    return ptr, strides, dev
+
+
+def blend_layers(colour, weight, bands=0, wrap=False, out=None, stream=None):
+    """eu_hip_blend_layers: multi-band blending of the caller's own remapped pictures - the pyramid a multiband render
+    runs behind its stage A (eu_hip.h, eu_target::bands). colour (N, H, W, C) plays the facets' colour, weight
+    (N, H, W) their weight Q (what is not positive counts as 0); float32, both numpy or both torch tensors on the
+    library's device; rows and pictures may be padded. wrap: column indices wrap (a 360-degree frame). Returns the
+    (H, W, C) frame: a new numpy array (a new device tensor for device input), or `out`, numpy or torch, rows may be
+    padded. With everything on the device the call is asynchronous on `stream` until sync()."""
+    if not _is_torch(colour):
+        colour, weight = np.asarray(colour), np.asarray(weight)
+    if _is_torch(colour) != _is_torch(weight):
+        raise EuError("blend_layers: colour and weight lie on the same side")
+    if colour.ndim != 4 or weight.ndim != 3 or tuple(colour.shape[:3]) != tuple(weight.shape):
+        raise EuError("blend_layers: colour is (N, H, W, C) and weight (N, H, W)")
+    n, h, w, c = (int(k) for k in colour.shape)
+    cptr, cst, dev = _strided(colour, "colour", (w, c))
+    wptr, wst, _ = _strided(weight, "weight", (w,))
+    if out is None:
+        if dev:
+            import torch
+            out = torch.empty((h, w, c), dtype=torch.float32, device=colour.device)
+        else:
+            out = np.zeros((h, w, c), np.float32)
+    if tuple(out.shape) != (h, w, c):
+        raise EuError(f"blend_layers: out has shape {tuple(out.shape)}, expected {(h, w, c)}")
+    optr, ost, o_dev = _strided(out, "out", (w, c))
+    _check(lib().eu_hip_blend_layers(C.c_void_p(cptr), cst[1], cst[0], C.c_void_p(wptr), wst[1], wst[0], int(dev), n, w, h, c,
+                                     int(bands), int(bool(wrap)), C.c_void_p(optr), ost[0], int(o_dev), _stream_handle(stream)))
     return out
 
 

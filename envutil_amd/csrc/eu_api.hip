@@ -4,7 +4,7 @@
 // EU_ERR_NO_DEVICE.
 // This file: the state and the helpers the call families share (eu_context.h), initialisation, the pure queries,
 // memory. The families: eu_api_source.hip, eu_api_render.hip, eu_api_devices.hip, eu_api_rays.hip, eu_api_views.hip,
-// eu_api_layers.hip.
+// eu_api_layers.hip, eu_api_multiband.hip.
 
 #include "eu_context.h"
 #include "eu_setup_math.h"
@@ -66,11 +66,39 @@ int local_rows(int height, int band_rows, int band_count, int band_index)
 // the target (eu_hip_render, eu_hip_render_devices), so that these refusals need none
 int check_synopsis(const eu_target *t)
 {
-  if (t->synopsis != EU_SYN_PANORAMA && t->synopsis != EU_SYN_HDR_MERGE && t->synopsis != EU_SYN_FEATHER)
+  if (t->synopsis != EU_SYN_PANORAMA && t->synopsis != EU_SYN_HDR_MERGE && t->synopsis != EU_SYN_FEATHER &&
+      t->synopsis != EU_SYN_MULTIBAND)
     return fail(EU_ERR_ARGUMENT, "unknown synopsis");
   if (!std::isfinite(t->feather) || t->feather < 0.0)
     return fail(EU_ERR_ARGUMENT, "feather must be a finite width in source pixels, 0 for the default");
+  if (t->synopsis == EU_SYN_MULTIBAND && t->bands < 0)
+    return fail(EU_ERR_ARGUMENT, "bands must be 0 (the default) or the number of pyramid levels");
   return EU_OK;
+}
+
+// What a multi-band job cannot be, because its pyramid needs the whole float frame at once; each with a message
+// of its own, and without a device. Single-facet jobs ignore the synopsis.
+int check_multiband(const eu_target *t, eu_source *const *srcs, int nsrc)
+{
+  if (t->synopsis != EU_SYN_MULTIBAND || nsrc < 2) return EU_OK;
+  if (t->ntaps > 0) return fail(EU_ERR_ARGUMENT, "multiband: no twining - the pyramid blends whole frames, not tap rays");
+  if (t->band_count > 1) return fail(EU_ERR_ARGUMENT, "multiband: no row bands - the pyramid needs the whole frame");
+  if (t->crop_w > 0) return fail(EU_ERR_ARGUMENT, "multiband: no crop window - the pyramid needs the whole frame");
+  if (t->row_begin != 0 || t->row_end != t->height)
+    return fail(EU_ERR_ARGUMENT, "multiband: the row range must be the whole frame");
+  if (t->out_format == EU_OUT_SRGBA8) return fail(EU_ERR_ARGUMENT, "multiband: EU_OUT_SRGBA8 is not blended, render floats");
+  for (int f = 0; srcs && f < nsrc; f++)
+    if (srcs[f] && srcs[f]->fct.mask_paint)
+      return fail(EU_ERR_ARGUMENT, "multiband: --mask_for paints facets, a pyramid of paint is no mask");
+  return EU_OK;
+}
+
+// the multi-band levels of a target: columns wrap on a spherical or cylindrical target of 360 degrees
+void multiband_geom(const eu_target *t, eu_mb_geom *g)
+{
+  const bool wrap = (t->projection == EU_SPHERICAL || t->projection == EU_CYLINDRICAL) &&
+                    std::fabs((t->x1 - t->x0) - 2.0 * M_PI) < .000001;
+  eu_mb_levels(t->width, t->height, t->bands, wrap, g);
 }
 
 int check_target(const eu_target *t)
@@ -118,7 +146,8 @@ std::vector<float> biased_taps(const float *taps, int ntaps)
 void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_multi_params *p)
 {
   p->nch = t->nchannels; p->nfct = nsrc; p->plus = (t->nchannels == 2 || t->nchannels == 4);
-  p->mode = t->synopsis == EU_SYN_HDR_MERGE ? EU_MODE_HDR : t->synopsis == EU_SYN_FEATHER ? EU_MODE_FEATHER : EU_MODE_PANORAMA;
+  p->mode = t->synopsis == EU_SYN_HDR_MERGE ? EU_MODE_HDR : t->synopsis == EU_SYN_FEATHER ? EU_MODE_FEATHER
+            : t->synopsis == EU_SYN_MULTIBAND ? EU_MODE_LAYERS : EU_MODE_PANORAMA;
   float lowest = 100000.0f, highest = -1.0f;
   p->hdr_low = p->hdr_high = -1;
   for (int f = 0; f < nsrc; f++) {

@@ -129,6 +129,8 @@ int eu_hip_render_devices(const eu_target *trg, eu_source *const *srcs, int nsrc
 {
   int rc;
   if (trg && (rc = check_synopsis(trg))) return rc;      // before a device is looked for
+  if (trg && trg->synopsis == EU_SYN_MULTIBAND && nsrc > 1 && nslots_ > 1)
+    return fail(EU_ERR_ARGUMENT, "render_devices: no multiband synopsis on more than one device - the pyramid needs the whole frame on one");
   if ((rc = ensure_init())) return rc;
   if (nslots_ <= 1) return eu_hip_render(trg, srcs, nsrc, out, out_row_stride_bytes, out_on_device, nullptr);
   if (!trg || !srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "no source / no output");

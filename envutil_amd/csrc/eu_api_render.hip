@@ -63,6 +63,7 @@ std::vector<unsigned char> plan_key_of(const eu_target *t, eu_source *const *src
   tk.taps = nullptr; tk.single = nullptr; tk.row_begin = 0; tk.row_end = 0; tk.stage = 0; tk.nchannels = 0; tk.out_format = 0;
   tk.band_rows = 0; tk.band_count = 0; tk.band_index = 0;
   tk.feather = 0.0;                 // the synopsis' business: no table depends on it
+  tk.bands = 0;
   unsigned char *q = key.data();
   memcpy(q, &tk, sizeof tk); q += sizeof tk;
   if (multi) { memcpy(q, &nsrc, sizeof(int)); q += sizeof(int); }
@@ -291,7 +292,7 @@ int build_multi(const eu_target *t, eu_source *const *srcs, int nsrc, float *out
     HIPCHK(hipMemcpyAsync(mp.gen.p, gv.data(), sizeof(eu_generic) * (size_t)nsrc, hipMemcpyHostToDevice, cur().stream));
   }
   // the feathered synopsis' edge-weight table: the job's, like the two above
-  const bool feather = t->synopsis == EU_SYN_FEATHER;
+  const bool feather = t->synopsis == EU_SYN_FEATHER || t->synopsis == EU_SYN_MULTIBAND;
   const std::vector<eu_feather_dev> fth = feather ? feather_table(t, srcs, nsrc) : std::vector<eu_feather_dev>();
   if (feather) {
     HIPCHK(mp.fth.reserve((size_t)nsrc));
@@ -510,7 +511,8 @@ namespace eu_host __attribute__((visibility("hidden"))) {
 // Radiance quads (no tables; render_frame has ordered `st`); with `yc`, the encode to the planes `yc` names (out_dev is
 // not used; the tables are in enc.steps as for `enc`)
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
-                     const eu_switches &sw, hipStream_t st, const eu_encode *enc, bool rgbe, const ycbcr_dst *yc)
+                     const eu_switches &sw, hipStream_t st, const eu_encode *enc, bool rgbe, const ycbcr_dst *yc,
+                     eu_mb_times *mb_times)
 {
   int rc;
   const bool multi = nsrc > 1;
@@ -533,7 +535,34 @@ int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, flo
     eu_multi_params mp;
     int mdeg = 0;
     if ((rc = build_multi(&tf, srcs, nsrc, fout, fstride, sw, &mp, &mdeg))) return rc;
-    if (eu_launch_render_multi(&mp, mdeg, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+    if (trg->synopsis == EU_SYN_MULTIBAND) {
+      // stage A writes the facets' layers into the scratch, the pyramid kernels blend them into the frame
+      if ((rc = check_multiband(trg, srcs, nsrc))) return rc;
+      eu_mb_geom g;
+      multiband_geom(trg, &g);
+      const bool alpha = trg->nchannels == 2 || trg->nchannels == 4;
+      const int ncol = alpha ? trg->nchannels - 1 : trg->nchannels;
+      if ((rc = multiband_reserve(eu_mb_scratch_floats(g, ncol, nsrc), st))) return rc;
+      mp.lay = cur().mband.buf.p; mp.lay_plane = (long long)g.off[1];
+      // (the stage-time diagnostic: stage A between two events of its own, destroyed whatever happens)
+      struct stage_events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~stage_events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+      } se;
+      if (mb_times) { HIPCHK(hipEventCreate(&se.a)); HIPCHK(hipEventCreate(&se.b)); HIPCHK(hipEventRecord(se.a, st)); }
+      if (eu_launch_render_multi(&mp, mdeg, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+      if (mb_times) {
+        float ms = 0.0f;
+        HIPCHK(hipEventRecord(se.b, st));
+        HIPCHK(hipEventSynchronize(se.b));
+        HIPCHK(hipEventElapsedTime(&ms, se.a, se.b));
+        mb_times->ms[EU_MB_T_STAGE_A] += ms;
+        mb_times->bytes[EU_MB_T_STAGE_A] += 4.0 * ((double)nsrc * (ncol + 1) + 3) * (double)g.off[1];   // what it writes
+      }
+      const eu_mb_out mo { fout, (long long)(fstride / sizeof(float)), trg->nchannels, alpha ? 1 : 0, 1 };
+      if (eu_launch_mb_blend(cur().mband.buf.p, &g, ncol, nsrc, &mo, st, mb_times)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
+      if (st != cur().stream) HIPCHK(cur().mband.readers.note(st));
+    } else if (eu_launch_render_multi(&mp, mdeg, st)) return fail(EU_ERR_NO_DEVICE, "kernel launch failed");
   } else {
     eu_render_params p;
     if ((rc = build_params(&tf, srcs, nsrc, fout, fstride, sw, &p))) return rc;
@@ -634,6 +663,7 @@ static int upload_steps(const eu_encode *enc, hipStream_t st)
 static int check_render_sources(const eu_target *trg, eu_source *const *srcs, int nsrc)
 {
   if (nsrc > 1 && trg->stage) return fail(EU_ERR_ARGUMENT, "stage outputs exist for single-facet jobs only");
+  { int rcm = check_multiband(trg, srcs, nsrc); if (rcm) return rcm; }
   for (int f = 0; f < nsrc; f++) {
     if (!srcs[f]) return fail(EU_ERR_HANDLE, "null source");
     // a masking job adapts channel counts with mono_t, which knows 1 and 2 output channels only
@@ -675,7 +705,8 @@ static int render_frame(const eu_target *trg, eu_source *const *srcs, int nsrc, 
   // chunks render - the link (57 GB/s pinned, 21 ms for the 1.2 GB headline frame) is the
   // whole cost, the kernels hide under the first copy. Samples and quads: the encode runs behind each chunk's render,
   // and the link carries a quarter, half or a third of the bytes.
-  const size_t nchunk = rows >= 1024 ? 4 : 1;
+  // (a multi-band job is one chunk: its pyramid needs the whole frame)
+  const size_t nchunk = rows >= 1024 && !(nsrc > 1 && trg->synopsis == EU_SYN_MULTIBAND) ? 4 : 1;
   if (!cur().out.copy) HIPCHK(hipStreamCreateWithFlags(&cur().out.copy, hipStreamNonBlocking));
   for (size_t c = 0; c < 4; c++)
     if (!cur().out.chunk_done[c]) HIPCHK(hipEventCreateWithFlags(&cur().out.chunk_done[c], hipEventDisableTiming));
@@ -709,6 +740,7 @@ int eu_hip_render(const eu_target *trg, eu_source *const *srcs, int nsrc, float 
 {
   int rc;
   if (trg && (rc = check_synopsis(trg))) return rc;      // before a device is looked for
+  if (trg && srcs && (rc = check_multiband(trg, srcs, nsrc))) return rc;
   if ((rc = ensure_init())) return rc;
   if (!trg) return fail(EU_ERR_ARGUMENT, "null target");
   if (!srcs || nsrc < 1 || !out) return fail(EU_ERR_ARGUMENT, "no source / no output");

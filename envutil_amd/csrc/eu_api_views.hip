@@ -253,6 +253,8 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
   if (nsrc == 1)
     return eu_hip_render_views(trg, views, nviews, srcs[0], out, out_row_stride_bytes, out_view_stride_bytes,
                                out_on_device, stream);
+  if (trg->synopsis == EU_SYN_MULTIBAND)
+    return fail(EU_ERR_ARGUMENT, "render_views_multi: no multiband synopsis - a pyramid per view is a job per view, call eu_hip_render");
   struct {
     const eu_target *trg;
     eu_source *const *srcs;

@@ -15,6 +15,7 @@
 #include <new>
 #include "eu_device.h"
 #include "eu_launch.h"
+#include "eu_multiband.h"
 
 struct eu_source {
   eu_facet fct;
@@ -174,6 +175,13 @@ struct context {
     eu_readers readers;                           // all of them: behind every reload on a caller's stream
     eu_readers own;                               // a mark on the library's own stream, for a caller's stream to wait for
   } reload;
+  // EU_SYN_MULTIBAND / eu_hip_blend_layers: the layer planes and pyramids of one job (eu_multiband.h has the layout),
+  // kept for the next one; `in` and `frame` stage host pictures and a host frame of eu_hip_blend_layers
+  struct {
+    eu_dev_buf<float> buf, in, frame;
+    eu_readers readers;                           // all of them: behind every job on a caller's stream
+    bool own = false;                             // the library's own stream has used them since a caller's stream last waited
+  } mband;
   // the way out of a frame: nothing here is read after the call that used it but scr, which `tables` guards
   struct {
     eu_dev_buf<float> stage;                      // host-output staging
@@ -244,6 +252,10 @@ inline size_t frame_row_bytes(const eu_target *t)
 int local_rows(int height, int band_rows, int band_count, int band_index);
 int check_target(const eu_target *t);
 int check_synopsis(const eu_target *t);
+int check_multiband(const eu_target *t, eu_source *const *srcs, int nsrc);
+void multiband_geom(const eu_target *t, eu_mb_geom *g);
+// `st` is about to rewrite the multi-band scratch: behind the jobs that used it before; then reserve() it
+int multiband_reserve(size_t floats, hipStream_t st);
 std::vector<float> biased_taps(const float *taps, int ntaps);
 void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_multi_params *p);
 
@@ -277,7 +289,7 @@ struct ycbcr_dst {
 // eu_api_render.hip. One job, everything on the device: what eu_hip_render_devices takes from the render family
 int render_on_device(const eu_target *trg, eu_source *const *srcs, int nsrc, float *out_dev, size_t stride_bytes,
                      const eu_switches &sw, hipStream_t st, const eu_encode *enc = nullptr, bool rgbe = false,
-                     const ycbcr_dst *yc = nullptr);
+                     const ycbcr_dst *yc = nullptr, eu_mb_times *mb_times = nullptr);
 
 // mean GPU time of `iters` calls of once() on the library's stream between two events, after one untimed call (which
 // builds whatever the first call builds: a plan's tables, derived copies)

@@ -15,7 +15,8 @@
 #define EU_REJ_STRIDE (EU_REJ_HDR + EU_REJ_N)
 
 // how a multi-facet job composes its facets: eu_target::synopsis (EU_SYN_*), one kernel family per mode
-enum { EU_MODE_PANORAMA = 0, EU_MODE_HDR = 1, EU_MODE_FEATHER = 2 };
+// (EU_MODE_LAYERS: stage A of EU_SYN_MULTIBAND, eu_synopsis_layers - the feathered loop writing layer planes)
+enum { EU_MODE_PANORAMA = 0, EU_MODE_HDR = 1, EU_MODE_FEATHER = 2, EU_MODE_LAYERS = 3 };
 
 // feathered seams (eu_synopsis_feather): what the edge weight of one facet needs. It belongs to the JOB - the
 // width is the target's - and not to the resident source, so it travels beside eu_src_dev: 16 bytes per facet,
@@ -39,7 +40,9 @@ struct eu_multi_params {
   int band_shift, band_count, band_index;   // eu_frame_row
   int mode;                                 // EU_MODE_*
   int hdr_low, hdr_high;                    // _hdr_merge_syn: the facets that rule the shadows / the highlights
-  const eu_feather_dev *fth;                // [nfct], EU_MODE_FEATHER only: the job's edge-weight table
+  const eu_feather_dev *fth;                // [nfct], EU_MODE_FEATHER / EU_MODE_LAYERS: the job's edge-weight table
+  float *lay;                               // EU_MODE_LAYERS: the layer planes (eu_multiband.h), `out` is not written
+  long long lay_plane;                      // floats from one plane to the next: width * rows
   const eu_generic *gen;                    // [nfct] or nullptr: facets stepped by generic_stepper (translation)
   eu_inv_planar inv;                        // tf22 of a --single job
   const float *rej;                         // [nfct][EU_REJ_STRIDE] or nullptr: early-miss tables (eu_multi_maybe)

@@ -592,6 +592,85 @@ __device__ __forceinline__ void eu_synopsis_feather(const eu_multi_params &p, co
   if constexpr (alpha) out[NCH - 1] = count == 1 ? one[NCH - 1] : amax;
 }
 
+// The layer form of eu_synopsis_feather, stage A of the multi-band synopsis (EU_SYN_MULTIBAND, eu_multiband.hip):
+// the same loop - ray, early miss, exact hit, eu_env_facet, ramp - but nothing is summed over the facets except
+// qsum: per facet the colour X_f (de-associated with alpha; 0 where the weight is not positive) and the weight
+// Q_f (0 on a miss) go to planes of the frame's size, p.lay_plane floats apart - facet f's ncol colour planes, then
+// its Q - and behind all facets' the pixel's qsum, amax and count (as a float). Every plane is written for every
+// live pixel, so the scratch needs no clearing. Whole frames only (no twining: the entry points refuse it).
+template <int NCH, int DEG, bool GEN>
+__device__ __forceinline__ void eu_synopsis_layers(const eu_multi_params &p, const eu_pix &px, bool live)
+{
+  constexpr bool alpha = NCH == 2 || NCH == 4;
+  constexpr int ncol = alpha ? NCH - 1 : NCH;
+  float qsum = 0.0f, amax = 0.0f;
+  int count = 0;
+  const long long at = (long long)(px.y - p.row_begin) * p.width + px.x;
+#pragma unroll 1
+  for (int f = 0; f < p.nfct; f++) {
+    float *lay = p.lay + (long long)f * (ncol + 1) * p.lay_plane + at;
+    float rx, ry, rz, sx = 0.0f, sy = 0.0f;
+    int face;
+    eu_syn_ray<GEN>(p, f, px, false, 0.0f, 0.0f, rx, ry, rz);
+    const eu_src_dev &s = p.srcs[f];
+    bool hit = false;
+    if (!s.mask_all) {
+      if (__ballot(eu_multi_maybe(p, f, s, rx, ry, rz))) hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    } else {
+      hit = eu_source_coordinate(s, rx, ry, rz, sx, sy, face);
+    }
+    if (!__ballot(hit)) {                       // a wavefront without a hit: no gathers, empty layers
+      if (live) {
+#pragma unroll
+        for (int c = 0; c <= ncol; c++) lay[c * p.lay_plane] = 0.0f;
+      }
+      continue;
+    }
+    float v[NCH];
+    eu_env_facet<NCH, DEG>(s, hit, sx, sy, v);
+    const eu_feather_dev &w = p.fth[f];         // f is wave-uniform: scalar loads
+    float e = 1.0f;
+    if (w.border) {
+      const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
+      const float d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
+      e = d * w.rcp;
+      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
+      e = e > 1.0f ? 1.0f : e;
+    }
+    float q = 0.0f, col[ncol];
+#pragma unroll
+    for (int c = 0; c < ncol; c++) col[c] = 0.0f;
+    if (hit) {
+      q = e;
+      if constexpr (!alpha) {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) col[c] = v[c];
+      } else {
+        const float a = v[NCH - 1];
+        q = a * e;
+#pragma unroll
+        for (int c = 0; c < ncol; c++)
+          if (a > 0.000001f) col[c] = v[c] / a;
+        amax = eu_std_max(amax, a);
+      }
+      qsum = qsum + q;
+      count++;
+    }
+    if (live) {
+      const bool m = q > 0.0f;
+#pragma unroll
+      for (int c = 0; c < ncol; c++) lay[c * p.lay_plane] = m ? col[c] : 0.0f;
+      lay[ncol * p.lay_plane] = q;
+    }
+  }
+  if (live) {
+    float *pix = p.lay + (long long)p.nfct * (ncol + 1) * p.lay_plane + at;
+    pix[0] = qsum;
+    pix[p.lay_plane] = amax;
+    pix[2 * p.lay_plane] = (float)count;
+  }
+}
+
 // The synopsis kernels are bound by the latency of their gathers (six 1-GB sources,
 // little locality) more than by anything else: capping the registers for 5 waves per
 // SIMD (a few spills) beats the 2-3 waves the allocator settles on by itself - config 5:
@@ -625,7 +704,11 @@ static int eu_multi_ladder(const eu_multi_params &p, int degree, const L &launch
     case 3: launch.template go<3, M, false, false>(lds); break;                      \
     default: launch.template go<-1, M, false, false>(lds); break;                    \
   }
-  if (p.mode == EU_MODE_FEATHER) {
+  if (p.mode == EU_MODE_LAYERS) {
+    // stage A of the multi-band synopsis: the one-job launcher alone has it
+    if (!L::layers || !p.fth || !p.lay || p.twine) return -2;
+    if constexpr (L::layers) { EU_LADDER_MODE(EU_MODE_LAYERS) }
+  } else if (p.mode == EU_MODE_FEATHER) {
     if (!p.fth) return -2;
     EU_LADDER_MODE(EU_MODE_FEATHER)
   } else if (p.mode == EU_MODE_HDR) {

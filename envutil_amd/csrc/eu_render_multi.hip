@@ -54,6 +54,11 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
   sl.z = eu_dyn_lds + threadIdx.x;
   sl.sx = sl.z + p.nfct * 256;
   sl.sy = sl.sx + p.nfct * 256;
+  if constexpr (SYN == EU_MODE_LAYERS) {
+    // stage A of the multi-band synopsis: the layers go to their planes, no frame is written
+    eu_synopsis_layers<NCH, DEG, GEN>(p, px, live);
+    return;
+  }
   float out[NCH];
   if (!p.twine) {
     if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, GEN>(p, px, false, 0.0f, 0.0f, out);
@@ -80,6 +85,7 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
 
 template <int NCH, bool PLUS>
 struct launch_multi {
+  static constexpr bool layers = true;          // EU_MODE_LAYERS is instantiated here
   const eu_multi_params &p;
   hipStream_t st;
   template <int DEG, int SYN, bool GEN, bool BIG>

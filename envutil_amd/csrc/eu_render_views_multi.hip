@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
 // GEN falls away: the one kernel of each (DEG, SYN, BIG)
 template <int NCH, bool PLUS>
 struct launch_views_multi {
+  static constexpr bool layers = false;         // no EU_MODE_LAYERS: eu_hip_render_views_multi refuses the multi-band synopsis
   const eu_multi_params &p;
   const eu_view_strides &vs;
   int nviews;

@@ -131,6 +131,8 @@ struct arguments : public facet_base
   // --synopsis feather: the width of the blending ramp in source pixels, 0: half the shorter side of each facet's
   // window (eu_target::feather)
   double feather = 0.0;
+  // --synopsis multiband: the pyramid levels above level 0, 0: what the frame allows, 8 at the most (eu_target::bands)
+  int bands = 0;
   int solo = -1, single = -1, mask_for = -1;
   std::vector<std::array<float, 3>> twine_spread;
   int support_min = 8, tile_size = 64;
@@ -303,7 +305,9 @@ struct hip_dispatch : public dispatch_base
     if (args.tethered ? !args.p_screen_data : !args.p_output && !args.p_output_samples && !args.p_output_rgbe && !args.p_output_ycbcr) return EU_ERR_ARGUMENT;
     // an unknown synopsis is the reference's assert(false) (envutil_payload.cc:2316-2318)
     // ("feather" is this project's own: eu_target::feather)
-    if (args.synopsis != "panorama" && args.synopsis != "hdr_merge" && args.synopsis != "feather") return EU_ERR_ARGUMENT;
+    // (and so is "multiband": eu_target::bands)
+    if (args.synopsis != "panorama" && args.synopsis != "hdr_merge" && args.synopsis != "feather" && args.synopsis != "multiband")
+      return EU_ERR_ARGUMENT;
     // --split is the caller's loop over --single jobs (core(), envutil_main.cc:1676-1722)
     if (args.single >= int(args.facet_spec_v.size()) || args.solo >= int(args.facet_spec_v.size())) return EU_ERR_ARGUMENT;
     std::vector<eu_source *> srcs;
@@ -424,8 +428,10 @@ struct hip_dispatch : public dispatch_base
       t.crop_x0 = args.p_crop_x0; t.crop_y0 = args.p_crop_y0; t.crop_w = w; t.crop_h = h;
     }
     t.row_begin = 0; t.row_end = h; t.stage = 0;
-    t.synopsis = args.synopsis == "hdr_merge" ? EU_SYN_HDR_MERGE : args.synopsis == "feather" ? EU_SYN_FEATHER : EU_SYN_PANORAMA;
+    t.synopsis = args.synopsis == "hdr_merge" ? EU_SYN_HDR_MERGE : args.synopsis == "feather" ? EU_SYN_FEATHER
+                 : args.synopsis == "multiband" ? EU_SYN_MULTIBAND : EU_SYN_PANORAMA;
     t.feather = args.feather;
+    t.bands = args.bands;
     // --single: args carries the facet's geometry ((facet_base&) args = fspec); its lens and translation
     // parameters reach the library through eu_target.single
     eu_facet single_fct {};

@@ -147,7 +147,7 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
     { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 }, { "--frames", 2 }, { "--ycbcr_matrix", 1 },
-    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 }, { "--feather", 1 } };
+    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 }, { "--feather", 1 }, { "--bands", 1 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
@@ -210,13 +210,20 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
   // --synopsis feather (no counterpart in the reference: eu_hip.h, eu_target::feather) and its --feather WIDTH in
   // source pixels, 0 for the default. ArgParse's get<float> again; a double from there on, as the library takes it
   a.feather = fl("--feather", 0.0f);
+  // --synopsis multiband (this project's own as well: eu_target::bands) and its --bands N, the pyramid levels above
+  // level 0, 0 for the default; it reads --feather as the feather synopsis does
+  a.bands = in("--bands", 0);
   if (bad) return false;
+  if (has("--bands")) {
+    if (a.bands < 0) { err = "--bands " + opt["--bands"] + ": the number of pyramid levels, 0 (the default: what the frame allows, 8 at the most) or more"; return false; }
+    if (a.synopsis != "multiband") { err = "--bands goes with --synopsis multiband"; return false; }
+  }
   if (has("--feather")) {
     if (!std::isfinite(a.feather) || a.feather < 0.0) {
       err = "--feather " + opt["--feather"] + ": a width in source pixels, 0 (the default: half the facet's shorter side) or more";
       return false;
     }
-    if (a.synopsis != "feather") { err = "--feather goes with --synopsis feather"; return false; }
+    if (a.synopsis != "feather" && a.synopsis != "multiband") { err = "--feather goes with --synopsis feather"; return false; }
   }
   if (a.prefilter_degree < 0) a.prefilter_degree = a.spline_degree;
   a.projection = projection_t(projection_index(a.projection_str));
@@ -478,6 +485,17 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     }
     if (a.single >= 0 || !a.split.empty()) { err = "--ray_map does not go with --single / --split"; return false; }
     a.twine = 0;                   // automatic twining is not applied either
+  }
+
+  // --synopsis multiband blends whole frames, and the library refuses a twined multi-band job: automatic twining
+  // (--twine -1, the default) is not applied to it, and twining that was asked for is refused here with its reason.
+  // A job of one facet (--solo too) ignores the synopsis and twines as ever.
+  if (a.synopsis == "multiband" && a.nfacets > 1 && a.solo < 0) {
+    if ((has("--twine") && a.twine > 1) || !a.twf_file.empty()) {
+      err = "--synopsis multiband blends whole frames through a pyramid: no --twine above 1 and no --twf_file";
+      return false;
+    }
+    a.twine = 0;
   }
 
   // --layer IMAGE OUTPUT: further pictures of the single facet's geometry, each with an output of its own. What

@@ -106,6 +106,42 @@ typedef struct eu_container {
 typedef struct eu_target {
   int32_t projection;
   int32_t width, height;
+  /* EU_SYN_MULTIBAND: multi-band (Burt-Adelson) blending, this library's own like EU_SYN_FEATHER; `bands` is the
+   * number of pyramid levels above level 0, 0 for the default, negative: EU_ERR_ARGUMENT. `feather` is read as
+   * under EU_SYN_FEATHER. Float32 throughout, one operation at a time, no contraction.
+   * Stage A, per target pixel, facets in job order: feather's own steps (ray, early miss, exact hit, the facet's
+   * pixel, the ramp e). A facet the ray hits gives q = e and the colour c = pixel, with alpha a: q = a * e and
+   * c = a > 1e-6 ? v / a : 0. Layers: Q_f = q on a hit, else 0; M_f = Q_f > 0 ? 1 : 0; X_f = M_f ? c : 0 per
+   * colour channel. qsum = sum Q_f, amax = the largest alpha over the hits, count = the hits;
+   * W_f = qsum > 0 ? Q_f / qsum : 0.
+   * Levels: w_{l+1} = (w_l + 1) >> 1, h likewise. L = bands clamped to L_max, the largest L whose coarsest level
+   * keeps min(w_L, h_L) >= 4 (L_max may be 0: the frame is then the level-0 blend alone); bands = 0:
+   * min(L_max, 8). Column indices wrap (i mod n) when the target is spherical or cylindrical with 360 degrees,
+   * and L_max is then further limited so that width % 2^L == 0; otherwise, and for rows always, indices clamp.
+   * Reduce R, along the rows first:
+   *   h[r, i] = (((A[r, 2i-2] + A[r, 2i+2]) + 4 * (A[r, 2i-1] + A[r, 2i+1])) + 6 * A[r, 2i]) * 0.0625
+   * then the same formula down the rows 2j-2 .. 2j+2 of h. Expand E to the finer level's size, along the rows
+   * first, then the same down the columns of the result: even 2i: ((A[i-1] + A[i+1]) + 6 * A[i]) * 0.125,
+   * odd 2i+1: (A[i] + A[i+1]) * 0.5.
+   * Pyramids per facet: X^{l+1} = R(X^l), M^{l+1} = R(M^l), W^{l+1} = R(W^l). Bands, facets in job order, only
+   * where M_f^l > 0: l < L: B = X^l / M^l - E(X^{l+1}) / E(M^{l+1}), the second term 0 where E(M^{l+1}) is not
+   * positive; l = L: B = X^L / M^L; num^l += W_f^l * B, den^l += W_f^l.
+   * Collapse: O^L = den > 0 ? num / den : 0; O^l = (den^l > 0 ? num^l / den^l : 0) + E(O^{l+1}).
+   * Pixel: zeros where count == 0; without alpha O^0; with alpha O^0 * amax and alpha = amax.
+   * Unlike EU_SYN_FEATHER, a pixel that only ONE facet covers is NOT that facet's pixel bit for bit: it has been
+   * through the pyramid. Another facet's weights reach 4 * 2^l pixels beyond it on level l, so next to a seam the
+   * low bands of the neighbour are mixed in, by design. Out of every other facet's reach a facet of ONE colour comes
+   * back within rounding; a textured facet comes back changed in the pixels near its own border too, because there
+   * E(X^{l+1}) / E(M^{l+1}) is not E(X^{l+1} / M^{l+1}), and within rounding only in its interior, where M is 1.
+   * The pyramid needs the whole frame at once: twining, a row range other than the whole frame, row bands, a crop
+   * window, EU_OUT_SRGBA8, --mask_for facets, eu_hip_render_devices with more than one slot and
+   * eu_hip_render_views_multi are refused with EU_ERR_ARGUMENT before a device is looked for. The scratch lives
+   * in the device context: eu_hip_multiband_scratch_bytes, eu_hip_multiband_scratch_release.
+   * Other synopses ignore the field; set it (0) always.
+   * The field lies in what was the 4-byte alignment gap in front of x0: the structure's size and every other
+   * field's offset are what they were, so callers built against the older header keep working (they never set
+   * EU_SYN_MULTIBAND, and the field is read under that synopsis alone).                                                       */
+  int32_t bands;
   double  x0, x1, y0, y1;
   double  yaw, pitch, roll;
   int32_t nchannels;
@@ -205,7 +241,31 @@ unsigned long long eu_hip_listed_tiles(void);
 int  eu_hip_band_rows(int height, int band_rows, int band_count, int band_index);
 
 enum { EU_OUT_FLOAT = 0, EU_OUT_SRGBA8 = 1 };
-enum { EU_SYN_PANORAMA = 0, EU_SYN_HDR_MERGE = 1, EU_SYN_FEATHER = 2 };
+/* (3 is not assigned: it stays an unknown synopsis, refused with EU_ERR_ARGUMENT) */
+enum { EU_SYN_PANORAMA = 0, EU_SYN_HDR_MERGE = 1, EU_SYN_FEATHER = 2, EU_SYN_MULTIBAND = 4 };
+
+/* ---- multi-band blending (eu_target::bands has the definition) ------------- */
+/* Bytes of device scratch an EU_SYN_MULTIBAND job of `nsrc` facets on `trg` takes (0 for nsrc < 2); a host
+ * function, no device is looked for. With S_l = w_l * h_l, T = S_0 + .. + S_L and ncol colour channels (the
+ * channels without alpha): 4 * (S_0 * (nsrc * (ncol + 1) + 3) + ncol * (T - S_0) + 2 * T + (ncol + 1) * T).   */
+size_t eu_hip_multiband_scratch_bytes(const eu_target *trg, int nsrc);
+/* waits for every multi-band job so far and frees the scratch they share (all device slots) */
+int  eu_hip_multiband_scratch_release(void);
+/* The pyramid on the caller's own remapped pictures - what a multi-band render runs behind stage A: `colour` is
+ * (nlayers, height, width, nchannels) float32 and plays c, `weight` is (nlayers, height, width) and plays Q
+ * (a weight that is not positive counts as 0); there is no alpha and no count: every pixel is O^0. Strides in
+ * bytes, multiples of 4; pixels are dense. `in_on_device` says where colour and weight lie, `out_on_device` where
+ * `out` (height rows of width * nchannels floats) lies; `stream` as for eu_hip_render (NULL: the library's own; a
+ * host buffer on either side makes the call return when `out` is complete). wrap != 0: column indices wrap.
+ * EU_ERR_ARGUMENT, before a device is looked for: null pointers, nlayers < 1, nchannels outside 1 .. 4, sizes
+ * below 1, negative bands, strides smaller than a row / a picture or no multiple of 4. EU_ERR_MEMORY: the scratch
+ * could not be allocated.                                                                                     */
+int  eu_hip_blend_layers(const float *colour, size_t colour_row_stride_bytes, size_t colour_layer_stride_bytes,
+                         const float *weight, size_t weight_row_stride_bytes, size_t weight_layer_stride_bytes,
+                         int in_on_device, int nlayers, int width, int height, int nchannels, int bands, int wrap,
+                         float *out, size_t out_row_stride_bytes, int out_on_device, void *stream);
+/* the levels a width x height frame gets for `bands` (eu_target::bands): L, or a negative eu_status */
+int  eu_hip_multiband_levels(int width, int height, int bands, int wrap);
 
 /* ---- device / lifecycle ------------------------------------------------- */
 int  eu_hip_device_count(void);

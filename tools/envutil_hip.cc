@@ -343,7 +343,15 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
   if (args.verbose) std::printf("using %s (%s)\n", dp->hwy_target_name.c_str(), dp->hwy_target_str.c_str());
   if (args.verbose && args.facet_spec_v.size() > 1) {
     // how the facets are composed; feather: the ramp's width in source pixels
-    if (args.synopsis != "feather") std::printf("synopsis %s\n", args.synopsis.c_str());
+    if (args.synopsis == "multiband") {
+      // the levels the frame gets: columns wrap on a spherical or cylindrical target of 360 degrees
+      const bool wrap = (args.projection == SPHERICAL || args.projection == CYLINDRICAL) && std::fabs(args.hfov - 2.0 * M_PI) < .000001;
+      std::printf("synopsis multiband, %d levels above level 0%s", eu_hip_multiband_levels(args.width, args.height, args.bands, wrap),
+                  wrap ? ", columns wrap" : "");
+      if (args.feather > 0.0) std::printf(", width %g source pixels\n", args.feather);
+      else std::printf(", width: half of each facet's shorter side\n");
+    }
+    else if (args.synopsis != "feather") std::printf("synopsis %s\n", args.synopsis.c_str());
     else if (args.feather > 0.0) std::printf("synopsis feather, width %g source pixels\n", args.feather);
     else std::printf("synopsis feather, width: half of each facet's shorter side\n");
   }
@@ -558,8 +566,10 @@ int main(int argc, const char **argv)
         "envutil_hip - envutil's reprojection on an MI355X (options as in envutil, envutil_main.cc:190-372)\n"
         "  source:   --facet IMAGE PROJECTION HFOV YAW PITCH ROLL (repeatable) | --photo IMAGE | --pto FILE [--pto_line LINE]\n"
         "            projections: spherical cylindrical rectilinear stereographic fisheye cubemap biatan6\n"
-        "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge|feather\n"
-        "            --feather WIDTH  with --synopsis feather: the blending ramp in source pixels (0: half the shorter side)\n"
+        "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge|feather|multiband\n"
+        "            --feather WIDTH  with --synopsis feather or multiband: the blending ramp in source pixels (0: half the shorter side)\n"
+        "            --bands N  with --synopsis multiband: pyramid levels above level 0 (0: what the frame allows, 8 at the most);\n"
+        "                       a multiband job of several facets is not twined: no automatic twining, --twine above 1 is refused\n"
         "  rays:     --ray_map FILE.pfm  the single facet's image at the rays x y z of a 3-channel PFM, in the facet's\n"
         "            frame (no yaw / pitch / roll, no twining); the output has the map's size\n"
         "  layers:   --layer IMAGE OUTPUT (repeatable)  a further picture of the single facet's geometry - same size and\n"
