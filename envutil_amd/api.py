@@ -144,6 +144,10 @@ def lib():
     L.eu_hip_source_load_ycbcr.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.eu_hip_ycbcr_floats.argtypes = [vp, i32, i32, i32, vp]
     L.eu_hip_source_reload.argtypes = [vp, vp, i32, vp]
+    L.eu_hip_source_load_pixels.argtypes = [vp, vp, i32, i32, i32, i32, C.c_uint, vp]
+    L.eu_hip_source_edge_distance.argtypes = [vp, vp, C.c_size_t, i32, vp]
+    L.eu_hip_source_has_edges.argtypes = [vp]
+    L.eu_hip_source_edge_device_ptr.argtypes = [vp, vp]
     L.eu_hip_facet_alpha_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.eu_hip_facet_alpha_rows.argtypes = [i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32]
     L.eu_hip_source_adopt.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -298,6 +302,7 @@ class YcbcrOut(C.Structure):
 
 
 PX_FLOATS, PX_SAMPLES, PX_RGBE, PX_YCBCR = 0, 1, 2, 3
+LOAD_EDGES = 1                # eu_hip_source_load_pixels: keep the distance plane (feathering to alpha edges)
 
 
 class Pixels(C.Structure):
@@ -876,18 +881,52 @@ class Source:
         return px, e if edited else None, (hold, hold2)
 
     @classmethod
+    def _load_pixels(cls, fct, px, e, spline_degree, prefilter_degree, support_min, tile_size, flags):
+        """eu_hip_source_load_pixels: the one load for every feed, with flags"""
+        if e is not None:
+            px.edit = C.cast(C.pointer(e), C.c_void_p)
+        cf = fct.c_struct()
+        h = C.c_void_p()
+        _check(lib().eu_hip_source_load_pixels(C.byref(cf), C.byref(px), spline_degree, prefilter_degree, support_min,
+                                               tile_size, flags, C.byref(h)))
+        return cls(h, fct, spline_degree)
+
+    @property
+    def has_edges(self):
+        """the source keeps a distance plane (it was loaded with edges=True)"""
+        return bool(self.handle) and bool(lib().eu_hip_source_has_edges(self.handle))
+
+    def edge_device_ptr(self):
+        """the device address of the distance plane, or None"""
+        p = C.c_void_p()
+        _check(lib().eu_hip_source_edge_device_ptr(self.handle, C.byref(p)))
+        return p.value
+
+    def edge_distance(self):
+        """(h, w) float32: the distance plane of a source loaded with edges=True - per window pixel the distance, in
+        source pixels, to the nearest pixel whose alpha is not positive (eu_hip_source_edge_distance)"""
+        out = np.zeros((self.fct.window[1], self.fct.window[0]), np.float32)
+        _check(lib().eu_hip_source_edge_distance(self.handle, _ptr(out), out.strides[0], 0, None))
+        return out
+
+    @classmethod
     def load(cls, fct, pixels, spline_degree, prefilter_degree=None, support_min=8,
-             tile_size=64, masks=(), crop=None, crop_kind=0):
+             tile_size=64, masks=(), crop=None, crop_kind=0, edges=False):
         """pixels -> braced + prefiltered coefficients, on the device. `pixels`: a numpy array or a
         float32 torch tensor on the library's device. masks (PTO exclude polygons, a list of (xs, ys)),
         crop (x0, x1, y0, y1) with crop_kind 1 rectangular / 2 elliptic: source_t's alpha edit, made on
         the device on the way into the container (eu_hip_source_load_edited); the pixels may then have
-        one channel fewer than the facet, which gains its alpha channel here."""
+        one channel fewer than the facet, which gains its alpha channel here. edges=True (a facet of 2 or 4 channels):
+        the source also keeps its distance plane - see edge_distance() -, which the feathered synopses take into the
+        blend weight (eu_hip_source_load_pixels with EU_LOAD_EDGES)."""
         if prefilter_degree is None:
             prefilter_degree = spline_degree
         cf = fct.c_struct()
         h = C.c_void_p()
         ptr, pch, on_device, e, hold = cls._float_feed(fct, pixels, masks, crop, crop_kind)
+        if edges:
+            px = Pixels(PX_FLOATS, ptr, pch, int(on_device), None, None, None, None)
+            return cls._load_pixels(fct, px, e, spline_degree, prefilter_degree, support_min, tile_size, LOAD_EDGES)
         if e is not None:
             _check(lib().eu_hip_source_load_edited(C.byref(cf), ptr, C.byref(e), spline_degree, prefilter_degree,
                                                    support_min, tile_size, C.byref(h)))
@@ -899,7 +938,7 @@ class Source:
     @classmethod
     def load_samples(cls, fct, samples, colour_table=None, alpha_table=None, maxval=None, big_endian=False,
                      spline_degree=1, prefilter_degree=None, support_min=8, tile_size=64, masks=(), crop=None,
-                     crop_kind=0):
+                     crop_kind=0, edges=False):
         """8- or 16-bit integer samples -> the same source as load() of table[samples], decoded on the device
         (eu_hip_source_load_samples): the samples go up as they are, no float copy is made on the host.
         `samples`: a uint8 / uint16 numpy array or a contiguous torch tensor of those dtypes on the library's
@@ -910,6 +949,9 @@ class Source:
         if prefilter_degree is None:
             prefilter_degree = spline_degree
         sm, e, hold = cls._samples_feed(fct, samples, colour_table, alpha_table, maxval, big_endian, masks, crop, crop_kind)
+        if edges:
+            px = Pixels(PX_SAMPLES, None, 0, 0, C.cast(C.pointer(sm), C.c_void_p), None, None, None)
+            return cls._load_pixels(fct, px, e, spline_degree, prefilter_degree, support_min, tile_size, LOAD_EDGES)
         cf = fct.c_struct()
         h = C.c_void_p()
         _check(lib().eu_hip_source_load_samples(C.byref(cf), C.byref(sm), C.byref(e) if e is not None else None,
@@ -918,7 +960,7 @@ class Source:
 
     @classmethod
     def load_rgbe(cls, fct, quads, colour_table=None, spline_degree=1, prefilter_degree=None, support_min=8,
-                  tile_size=64, masks=(), crop=None, crop_kind=0):
+                  tile_size=64, masks=(), crop=None, crop_kind=0, edges=False):
         """Radiance RGBE pixels -> the same source as load() of their decoded floats, decoded on the device
         (eu_hip_source_load_rgbe): the quads go up as they are, no float copy is made on the host. `quads`: a uint8
         numpy array or a contiguous torch uint8 tensor on the library's device, (h, w, 4): R, G, B, E. fct.nchannels is
@@ -927,6 +969,9 @@ class Source:
         if prefilter_degree is None:
             prefilter_degree = spline_degree
         px, e, hold = cls._rgbe_feed(quads, colour_table, masks, crop, crop_kind)
+        if edges:
+            pp = Pixels(PX_RGBE, None, 0, 0, None, C.cast(C.pointer(px), C.c_void_p), None, None)
+            return cls._load_pixels(fct, pp, e, spline_degree, prefilter_degree, support_min, tile_size, LOAD_EDGES)
         cf = fct.c_struct()
         h = C.c_void_p()
         _check(lib().eu_hip_source_load_rgbe(C.byref(cf), C.byref(px), C.byref(e) if e is not None else None,
@@ -935,7 +980,7 @@ class Source:
 
     @classmethod
     def load_ycbcr(cls, fct, y, chroma, matrix, y_table=None, c_table=None, spline_degree=1, prefilter_degree=None,
-                   support_min=8, tile_size=64, masks=(), crop=None, crop_kind=0):
+                   support_min=8, tile_size=64, masks=(), crop=None, crop_kind=0, edges=False):
         """The planes of a Y'CbCr frame -> the same source as load() of ycbcr_floats() of them, decoded on the device
         (eu_hip_source_load_ycbcr): the planes go up as their rows lie, no float copy is made on the host. `y`: (h, w)
         uint8 or uint16, a numpy array or a torch tensor on the library's device. `chroma`: a pair (cb, cr) of (ch, cw)
@@ -948,6 +993,9 @@ class Source:
         if prefilter_degree is None:
             prefilter_degree = spline_degree
         px, e, hold = cls._ycbcr_feed(y, chroma, matrix, y_table, c_table, masks, crop, crop_kind)
+        if edges:
+            pp = Pixels(PX_YCBCR, None, 0, 0, None, None, C.cast(C.pointer(px), C.c_void_p), None)
+            return cls._load_pixels(fct, pp, e, spline_degree, prefilter_degree, support_min, tile_size, LOAD_EDGES)
         cf = fct.c_struct()
         h = C.c_void_p()
         _check(lib().eu_hip_source_load_ycbcr(C.byref(cf), C.byref(px), C.byref(e) if e is not None else None,

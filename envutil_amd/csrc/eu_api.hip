@@ -148,6 +148,11 @@ void fill_synopsis(const eu_target *t, eu_source *const *srcs, int nsrc, eu_mult
   p->nch = t->nchannels; p->nfct = nsrc; p->plus = (t->nchannels == 2 || t->nchannels == 4);
   p->mode = t->synopsis == EU_SYN_HDR_MERGE ? EU_MODE_HDR : t->synopsis == EU_SYN_FEATHER ? EU_MODE_FEATHER
             : t->synopsis == EU_SYN_MULTIBAND ? EU_MODE_LAYERS : EU_MODE_PANORAMA;
+  // a facet with a distance plane (EU_LOAD_EDGES): the loops that sample it; every other job keeps its kernels
+  bool planes = false;
+  for (int f = 0; f < nsrc; f++) planes = planes || srcs[f]->edge;
+  if (planes && p->mode == EU_MODE_FEATHER) p->mode = EU_MODE_FEATHER_EDGES;
+  if (planes && p->mode == EU_MODE_LAYERS) p->mode = EU_MODE_LAYERS_EDGES;
   float lowest = 100000.0f, highest = -1.0f;
   p->hdr_low = p->hdr_high = -1;
   for (int f = 0; f < nsrc; f++) {
@@ -166,6 +171,7 @@ std::vector<eu_feather_dev> feather_table(const eu_target *t, eu_source *const *
 {
   std::vector<eu_feather_dev> v((size_t)nsrc);
   for (int f = 0; f < nsrc; f++) {
+    memset(&v[f], 0, sizeof v[f]);              // (the padding too: the table is compared and hashed as bytes)
     const eu_source *s = srcs[f];
     const eu_facet &fc = s->fct;
     const bool closed = eu_cube_source(fc.projection) || s->sd.mask_all;
@@ -176,6 +182,11 @@ std::vector<eu_feather_dev> feather_table(const eu_target *t, eu_source *const *
     v[f].lim_x = (float)fc.window_width - 0.5f;
     v[f].lim_y = (float)fc.window_height - 0.5f;
     v[f].border = (wrap0 ? 0 : 1) | (wrap1 ? 0 : 2);
+    // the distance plane of a source loaded with EU_LOAD_EDGES: its rows close where the load made axis 0 periodic
+    v[f].dist = s->edge;
+    v[f].dist_w = s->edge ? fc.window_width : 0;
+    v[f].dist_h = s->edge ? fc.window_height : 0;
+    v[f].cyclic = s->edge && s->bc[0] == EU_BC_PERIODIC;
   }
   return v;
 }

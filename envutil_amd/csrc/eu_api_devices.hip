@@ -19,7 +19,7 @@ int replica_of(eu_source *src, int k, eu_source **out)
     eu_source *r = new (std::nothrow) eu_source(*src);
     if (!r) return fail(EU_ERR_NO_DEVICE, "out of host memory");
     for (int j = 0; j < EU_MAX_SLOTS; j++) r->replica[j] = nullptr;
-    r->is_replica = true; r->slot = k; r->dev = nullptr;
+    r->is_replica = true; r->slot = k; r->dev = nullptr; r->edge = nullptr;
     r->readers = eu_readers(); r->written = eu_readers(); r->own_written = false;      // the original's events stay its own
     int rc = set_slot(k);
     if (rc) { delete r; return rc; }
@@ -29,6 +29,16 @@ int replica_of(eu_source *src, int k, eu_source **out)
         e = hipMemcpyAsync(r->dev, src->dev, src->nfloats * sizeof(float), hipMemcpyDeviceToDevice, cur().stream);
       else
         e = hipMemcpyPeerAsync(r->dev, ctx_[k].device, src->dev, ctx_[src->slot].device, src->nfloats * sizeof(float), cur().stream);
+    }
+    if (e == hipSuccess && src->edge) {
+      // the distance plane of a source loaded with EU_LOAD_EDGES travels with the container
+      const size_t nb = (size_t)src->fct.window_width * (size_t)src->fct.window_height * sizeof(float);
+      e = hipMalloc((void **)&r->edge, nb);
+      if (e != hipSuccess) r->edge = nullptr;
+      else if (ctx_[k].device == ctx_[src->slot].device)
+        e = hipMemcpyAsync(r->edge, src->edge, nb, hipMemcpyDeviceToDevice, cur().stream);
+      else
+        e = hipMemcpyPeerAsync(r->edge, ctx_[k].device, src->edge, ctx_[src->slot].device, nb, cur().stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(cur().stream);
     if (e != hipSuccess) { destroy_source(r); return fail(EU_ERR_NO_DEVICE, hipGetErrorString(e)); }

@@ -4,6 +4,7 @@
 #include "eu_setup_math.h"
 #include "eu_imageprep.h"
 #include "eu_alpha.h"
+#include "eu_edges.h"
 #include "eu_decode.h"
 #include "eu_rgbe_dev.h"
 #include "eu_ycbcr_dev.h"
@@ -270,6 +271,7 @@ struct fill_scratch {
   const bool resident;
   eu_dev_tmp<char> t_block;
   eu_dev_tmp<float> t_staged, t_faces;
+  eu_dev_tmp<int32_t> t_edges;
   std::vector<float> tabs;           // a load's tables on their way up: alive until the load has synchronised
   explicit fill_scratch(bool res) : resident(res) {}
 
@@ -317,6 +319,12 @@ struct fill_scratch {
   {
     const hipError_t e = resident ? grow(cur().reload.staged, n) : t_staged.alloc(n);
     *p = resident ? cur().reload.staged.p : t_staged.p;
+    return e;
+  }
+  hipError_t edges(size_t n, int32_t **p)
+  {
+    const hipError_t e = resident ? grow(cur().reload.edges, n) : t_edges.alloc(n);
+    *p = resident ? cur().reload.edges.p : t_edges.p;
     return e;
   }
   hipError_t faces(size_t n, float **p)
@@ -488,6 +496,16 @@ fill_result fill_source(eu_source *s, int prefilter_degree, const load_feed &fee
       if (!prc && eu_launch_facet_alpha(&p, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
     }
   }
+  // the distance plane of a source that keeps one (EU_LOAD_EDGES; never a cubemap): from the alpha channel of the plane
+  // as the prefilter is about to read it, behind the edit and in front of the finish
+  if (e == hipSuccess && !prc && s->edge) {
+    eu_edges_params ep {};
+    ep.plane = dst; ep.pitch = dst_pitch; ep.w = w; ep.h = h; ep.nch = nch;
+    ep.cyclic = s->bc[0] == EU_BC_PERIODIC;
+    ep.dist = s->edge;
+    e = sc.edges(npix, &ep.scratch);
+    if (e == hipSuccess && eu_launch_edges(&ep, st)) prc = fail(EU_ERR_NO_DEVICE, who + ": kernel launch failed");
+  }
   // the finish: the IR image of a cubemap from its faces, or prefilter + brace of the container (a core narrower
   // than the spline's frame on an axis is braced slice by slice in zimt's order, eu_setup.hip: brace_seq_kernel)
   if (e == hipSuccess && !prc)
@@ -510,13 +528,22 @@ int fill_status(const fill_result &r, hipError_t e2)
   return EU_OK;
 }
 
+// flags: eu_hip_source_load_pixels' (EU_LOAD_EDGES: the source gets its distance plane, which fill_source then fills)
 int load_source(const eu_facet *fct, int spline_degree, int prefilter_degree, int support_min, int tile_size,
-                const load_feed &feed, eu_source **out)
+                const load_feed &feed, unsigned flags, eu_source **out)
 {
   int rc, bc0, bc1;
   source_bcs(fct, &bc0, &bc1);
   eu_source *s = nullptr;
   if ((rc = new_source(fct, spline_degree, bc0, bc1, support_min, tile_size, &s))) return rc;
+  if (flags & EU_LOAD_EDGES) {
+    const hipError_t ee = hipMalloc((void **)&s->edge, size_t(fct->window_width) * size_t(fct->window_height) * sizeof(float));
+    if (ee != hipSuccess) {
+      s->edge = nullptr;
+      destroy_source(s);
+      return fail(EU_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(ee));
+    }
+  }
   fill_scratch sc(false);            // freed by scope, after the synchronisation
   const fill_result r = fill_source(s, prefilter_degree, feed, cur().stream, sc);
   rc = fill_status(r, hipStreamSynchronize(cur().stream));
@@ -659,8 +686,8 @@ int eu_hip_source_adopt(const eu_facet *fct, const float *container, int spline_
   return EU_OK;
 }
 
-int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degree,
-                       int prefilter_degree, int support_min, int tile_size, eu_source **out)
+static int load_flagged(const eu_facet *fct, const float *pixels, int spline_degree,
+                       int prefilter_degree, int support_min, int tile_size, unsigned flags, eu_source **out)
 {
   int rc;
   if ((rc = ensure_init())) return rc;
@@ -669,7 +696,7 @@ int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degr
   if (prefilter_degree < 0 || prefilter_degree > EU_MAX_DEGREE)
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   const load_feed feed { FEED_HOST_FLOATS, "source_load", pixels, false, fct->nchannels, nullptr, false, nullptr, nullptr, nullptr };
-  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, flags, out);
 }
 
 int eu_hip_facet_alpha_rows(int width, int height, const eu_mask_polygon *polygons, int npolygons, int crop_kind,
@@ -722,8 +749,8 @@ int eu_hip_facet_alpha_dev(void *pixels_dev, int width, int height, int nchannel
   return note_caller(cur().alpha.readers, stream, EU_OK);
 }
 
-int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
-                              int prefilter_degree, int support_min, int tile_size, eu_source **out)
+static int load_edited_flagged(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
+                              int prefilter_degree, int support_min, int tile_size, unsigned flags, eu_source **out)
 {
   int rc;
   if ((rc = check_facet(fct))) return rc;
@@ -735,15 +762,15 @@ int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_
   if ((rc = check_edit(edit, fct->nchannels, "source_load_edited", &asked))) return rc;
   const bool on_device = edit && edit->pixels_on_device;
   if (!asked && !on_device)
-    return eu_hip_source_load(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min,
-                              tile_size, out);
+    return load_flagged(fct, static_cast<const float *>(pixels), spline_degree, prefilter_degree, support_min, tile_size,
+                        flags, out);
   if ((rc = ensure_init())) return rc;
   const load_feed feed { FEED_EDITED_FLOATS, "source_load_edited", pixels, on_device, edit->pixel_channels, edit, asked, nullptr, nullptr, nullptr };
-  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, flags, out);
 }
 
-int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
-                               int prefilter_degree, int support_min, int tile_size, eu_source **out)
+static int load_samples_flagged(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
+                               int prefilter_degree, int support_min, int tile_size, unsigned flags, eu_source **out)
 {
   int rc;
   if ((rc = check_facet(fct))) return rc;
@@ -756,11 +783,11 @@ int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
   const load_feed feed { FEED_SAMPLES, "source_load_samples", smp->data, smp->on_device != 0, smp->pixel_channels, &ed, edited, smp, nullptr, nullptr };
-  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, flags, out);
 }
 
-int eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
-                            int prefilter_degree, int support_min, int tile_size, eu_source **out)
+static int load_rgbe_flagged(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
+                            int prefilter_degree, int support_min, int tile_size, unsigned flags, eu_source **out)
 {
   int rc;
   if ((rc = check_facet(fct))) return rc;
@@ -773,11 +800,11 @@ int eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_fac
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
   const load_feed feed { FEED_RGBE, "source_load_rgbe", px->data, px->on_device != 0, 3, &ed, edited, nullptr, px->colour_table, nullptr };
-  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, flags, out);
 }
 
-int eu_hip_source_load_ycbcr(const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit, int spline_degree,
-                             int prefilter_degree, int support_min, int tile_size, eu_source **out)
+static int load_ycbcr_flagged(const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit, int spline_degree,
+                             int prefilter_degree, int support_min, int tile_size, unsigned flags, eu_source **out)
 {
   int rc;
   if ((rc = check_facet(fct))) return rc;
@@ -790,7 +817,107 @@ int eu_hip_source_load_ycbcr(const eu_facet *fct, const eu_ycbcr *px, const eu_f
     return fail(EU_ERR_ARGUMENT, "prefilter degree out of range");
   if ((rc = ensure_init())) return rc;
   const load_feed feed { FEED_YCBCR, "source_load_ycbcr", px->y, px->on_device != 0, 3, &ed, edited, nullptr, nullptr, px };
-  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, out);
+  return load_source(fct, spline_degree, prefilter_degree, support_min, tile_size, feed, flags, out);
+}
+
+// The five loads of the ABI, as they have always been: the bodies above without flags.
+int eu_hip_source_load(const eu_facet *fct, const float *pixels, int spline_degree,
+                       int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  return load_flagged(fct, pixels, spline_degree, prefilter_degree, support_min, tile_size, 0u, out);
+}
+int eu_hip_source_load_edited(const eu_facet *fct, const void *pixels, const eu_facet_edit *edit, int spline_degree,
+                              int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  return load_edited_flagged(fct, pixels, edit, spline_degree, prefilter_degree, support_min, tile_size, 0u, out);
+}
+int eu_hip_source_load_samples(const eu_facet *fct, const eu_samples *smp, const eu_facet_edit *edit, int spline_degree,
+                               int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  return load_samples_flagged(fct, smp, edit, spline_degree, prefilter_degree, support_min, tile_size, 0u, out);
+}
+int eu_hip_source_load_rgbe(const eu_facet *fct, const eu_rgbe *px, const eu_facet_edit *edit, int spline_degree,
+                            int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  return load_rgbe_flagged(fct, px, edit, spline_degree, prefilter_degree, support_min, tile_size, 0u, out);
+}
+int eu_hip_source_load_ycbcr(const eu_facet *fct, const eu_ycbcr *px, const eu_facet_edit *edit, int spline_degree,
+                             int prefilter_degree, int support_min, int tile_size, eu_source **out)
+{
+  return load_ycbcr_flagged(fct, px, edit, spline_degree, prefilter_degree, support_min, tile_size, 0u, out);
+}
+
+// One load for every feed (eu_hip.h, "feathering to alpha edges"): the flags' own refusals, then the matching load's
+// body - its checks, in its order, with its messages.
+int eu_hip_source_load_pixels(const eu_facet *fct, const eu_pixels *px, int spline_degree, int prefilter_degree,
+                              int support_min, int tile_size, unsigned flags, eu_source **out)
+{
+  int rc;
+  if ((rc = check_facet(fct))) return rc;
+  if (!px) return fail(EU_ERR_ARGUMENT, "source_load_pixels: null pixels (px)");
+  if (flags & ~unsigned(EU_LOAD_EDGES)) return fail(EU_ERR_ARGUMENT, "source_load_pixels: unknown flag bit (flags)");
+  if (flags & EU_LOAD_EDGES) {
+    if (eu_cube_source(fct->projection))
+      return fail(EU_ERR_ARGUMENT, "source_load_pixels: EU_LOAD_EDGES on a cubemap: a distance plane belongs to a facet with a window");
+    if (fct->nchannels != 2 && fct->nchannels != 4)
+      return fail(EU_ERR_ARGUMENT, "source_load_pixels: EU_LOAD_EDGES needs an alpha channel: nchannels 2 or 4");
+    if (fct->window_width > EU_EDGES_MAX_SIDE || fct->window_height > EU_EDGES_MAX_SIDE)
+      return fail(EU_ERR_ARGUMENT, "source_load_pixels: EU_LOAD_EDGES on a window side above 32768 (window_width, window_height)");
+    if (fct->window_width < 1 || fct->window_height < 1)
+      return fail(EU_ERR_ARGUMENT, "source_load_pixels: EU_LOAD_EDGES on an empty window (window_width, window_height)");
+  }
+  switch (px->kind) {
+    case EU_PX_FLOATS: {
+      eu_facet_edit ed {};
+      if (px->edit) ed = *px->edit;
+      ed.pixel_channels = px->pixel_channels;
+      ed.pixels_on_device = px->on_device;
+      return load_edited_flagged(fct, px->floats, &ed, spline_degree, prefilter_degree, support_min, tile_size, flags, out);
+    }
+    case EU_PX_SAMPLES:
+      return load_samples_flagged(fct, px->samples, px->edit, spline_degree, prefilter_degree, support_min, tile_size, flags, out);
+    case EU_PX_RGBE:
+      return load_rgbe_flagged(fct, px->rgbe, px->edit, spline_degree, prefilter_degree, support_min, tile_size, flags, out);
+    case EU_PX_YCBCR:
+      return load_ycbcr_flagged(fct, px->ycbcr, px->edit, spline_degree, prefilter_degree, support_min, tile_size, flags, out);
+  }
+  return fail(EU_ERR_ARGUMENT, "source_load_pixels: unknown kind (px->kind)");
+}
+
+int eu_hip_source_has_edges(const eu_source *src) { return src && src->edge ? 1 : 0; }
+
+int eu_hip_source_edge_device_ptr(const eu_source *src, void **dev_ptr)
+{
+  if (!src) return fail(EU_ERR_HANDLE, "null source");
+  if (dev_ptr) *dev_ptr = src->edge;
+  return EU_OK;
+}
+
+int eu_hip_source_edge_distance(const eu_source *src, float *out, size_t row_stride_bytes, int out_on_device, void *stream)
+{
+  if (!src) return fail(EU_ERR_HANDLE, "source_edge_distance: null source (src)");
+  if (!out) return fail(EU_ERR_ARGUMENT, "source_edge_distance: null out");
+  if (!src->edge)
+    return fail(EU_ERR_ARGUMENT, "source_edge_distance: the source keeps no distance plane: it was not loaded with EU_LOAD_EDGES");
+  const size_t w = size_t(src->fct.window_width), h = size_t(src->fct.window_height), row = w * sizeof(float);
+  if (row_stride_bytes < row || row_stride_bytes % sizeof(float))
+    return fail(EU_ERR_ARGUMENT, "source_edge_distance: row_stride_bytes is a multiple of 4 and at least a row");
+  int rc;
+  if ((rc = ensure_init())) return rc;
+  const int back = cur_slot_;
+  if (src->slot != back && (rc = set_slot(src->slot))) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : cur().stream;
+  // behind the reload that may still be writing the plane, on a caller's stream or on the library's own
+  hipError_t e = hipSuccess;
+  if (src->own_written && st != cur().stream) e = hipStreamSynchronize(cur().stream);
+  if (e == hipSuccess) e = src->written.order_after(st);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(out, row_stride_bytes, src->edge, row, row, h, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !out_on_device) e = hipStreamSynchronize(st);
+  if (src->slot != back && (rc = set_slot(back))) return rc;
+  if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, std::string("source_edge_distance: ") + hipGetErrorString(e));
+  // a copy left on a caller's stream reads the plane as a render reads the container
+  return out_on_device ? note_caller(const_cast<eu_source *>(src)->readers, stream, EU_OK) : EU_OK;
 }
 
 int eu_hip_ycbcr_floats(const eu_ycbcr *px, int width, int height, int nchannels, float *out)
@@ -905,14 +1032,14 @@ int eu_hip_reload_scratch_release(void)
   for (int k = 0; k < nslots_; k++) {
     context &c = ctx_[k];
     if (c.device < 0) continue;
-    if (!c.reload.tables.dev.p && !c.reload.block.p && !c.reload.staged.p && !c.reload.faces.p) continue;
+    if (!c.reload.tables.dev.p && !c.reload.block.p && !c.reload.staged.p && !c.reload.faces.p && !c.reload.edges.p) continue;
     const int back = cur_slot_;
     int rc;
     if ((rc = set_slot(k))) return rc;
     hipError_t e = c.reload.readers.host_wait();
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
     auto drop = [&](auto &b) { if (b.p) { const hipError_t f = hipFree(b.p); if (e == hipSuccess) e = f; } b.p = nullptr; b.cap = 0; };
-    drop(c.reload.tables.dev); drop(c.reload.block); drop(c.reload.staged); drop(c.reload.faces);
+    drop(c.reload.tables.dev); drop(c.reload.block); drop(c.reload.staged); drop(c.reload.faces); drop(c.reload.edges);
     c.reload.tables.host.clear();
     if ((rc = set_slot(back))) return rc;
     if (e != hipSuccess) return fail(EU_ERR_NO_DEVICE, std::string("reload_scratch_release: ") + hipGetErrorString(e));

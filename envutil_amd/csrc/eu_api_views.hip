@@ -266,7 +266,7 @@ int eu_hip_render_views_multi(const eu_target *trg, const eu_view *views, int nv
       p.width = trg->width; p.height = trg->height; p.row_begin = 0; p.row_end = trg->height;
       p.form = form; p.norm_mode = norm_mode; p.twine = trg->ntaps > 0; p.ntaps = trg->ntaps;
       fill_synopsis(trg, srcs, nsrc, &p);
-      p.fth = p.mode == EU_MODE_FEATHER ? cur().views.fth.p : nullptr;
+      p.fth = eu_mode_feather(p.mode) ? cur().views.fth.p : nullptr;
       p.col = cur().views.col.p; p.row = cur().views.row.p; p.taps = cur().views.taps.dev.p; p.srcs = cur().views.src.p;
     }
     int launch(int nv, const eu_view_strides &vs, const eu_switches &, hipStream_t st)

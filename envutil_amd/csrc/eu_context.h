@@ -39,6 +39,10 @@ struct eu_source {
   // caller's stream has waited for it since. Copies on other slots have neither: they are dropped by a reload.
   eu_readers readers, written;
   bool own_written = false;
+  // EU_LOAD_EDGES: the distance plane D of the window (eu_edges.hip), window_width x window_height floats, dense; it is
+  // written wherever the container is - by the load and by every reload, on the same stream -, so the container's
+  // guards are its own. nullptr: the source keeps none.
+  float *edge = nullptr;
 };
 
 namespace eu_host __attribute__((visibility("hidden"))) {
@@ -172,6 +176,7 @@ struct context {
     held_table tables;
     eu_dev_buf<char> block;
     eu_dev_buf<float> staged, faces;
+    eu_dev_buf<int32_t> edges;                    // the scratch plane of a distance transform (eu_edges.h)
     eu_readers readers;                           // all of them: behind every reload on a caller's stream
     eu_readers own;                               // a mark on the library's own stream, for a caller's stream to wait for
   } reload;
@@ -273,6 +278,7 @@ inline void destroy_source(eu_source *s)
 {
   if (!s) return;
   if (s->dev) (void)hipFree(s->dev);
+  if (s->edge) (void)hipFree(s->edge);
   if (s->readers.ev) (void)hipEventDestroy(s->readers.ev);
   if (s->written.ev) (void)hipEventDestroy(s->written.ev);
   delete s;

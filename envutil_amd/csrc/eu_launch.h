@@ -16,15 +16,23 @@
 
 // how a multi-facet job composes its facets: eu_target::synopsis (EU_SYN_*), one kernel family per mode
 // (EU_MODE_LAYERS: stage A of EU_SYN_MULTIBAND, eu_synopsis_layers - the feathered loop writing layer planes)
-enum { EU_MODE_PANORAMA = 0, EU_MODE_HDR = 1, EU_MODE_FEATHER = 2, EU_MODE_LAYERS = 3 };
+// EU_MODE_FEATHER_EDGES, EU_MODE_LAYERS_EDGES: the same two loops in jobs where some facet keeps a distance plane
+// (EU_LOAD_EDGES) - instantiations of their own, so that every other job runs the kernels it ran without them
+enum { EU_MODE_PANORAMA = 0, EU_MODE_HDR = 1, EU_MODE_FEATHER = 2, EU_MODE_LAYERS = 3, EU_MODE_FEATHER_EDGES = 4,
+       EU_MODE_LAYERS_EDGES = 5 };
+constexpr bool eu_mode_feather(int m) { return m == EU_MODE_FEATHER || m == EU_MODE_FEATHER_EDGES; }
+constexpr bool eu_mode_layers(int m) { return m == EU_MODE_LAYERS || m == EU_MODE_LAYERS_EDGES; }
 
 // feathered seams (eu_synopsis_feather): what the edge weight of one facet needs. It belongs to the JOB - the
-// width is the target's - and not to the resident source, so it travels beside eu_src_dev: 16 bytes per facet,
+// width is the target's - and not to the resident source, so it travels beside eu_src_dev: 40 bytes per facet,
 // read wave-uniformly through the scalar cache.
 struct eu_feather_dev {
   float rcp;                 // float(1.0 / width_px): the ramp's slope per window pixel
   float lim_x, lim_y;        // float(window size) - 0.5f: the far border in pixel coordinates
   int border;                // bit 0: axis 0 has a border, bit 1: axis 1; 0: the weight is 1
+  const float *dist;         // the facet's distance plane (EU_LOAD_EDGES), dist_w x dist_h floats, dense; nullptr: none
+  int dist_w, dist_h;
+  int cyclic;                // the plane's rows close: column indices wrap
 };
 
 struct eu_multi_params {
@@ -38,7 +46,7 @@ struct eu_multi_params {
   long long out_stride;
   int tiles_x, tiles_y;
   int band_shift, band_count, band_index;   // eu_frame_row
-  int mode;                                 // EU_MODE_*
+  int mode;                                 // EU_MODE_* (fill_synopsis: the _EDGES forms where a facet has a plane)
   int hdr_low, hdr_high;                    // _hdr_merge_syn: the facets that rule the shadows / the highlights
   const eu_feather_dev *fth;                // [nfct], EU_MODE_FEATHER / EU_MODE_LAYERS: the job's edge-weight table
   float *lay;                               // EU_MODE_LAYERS: the layer planes (eu_multiband.h), `out` is not written

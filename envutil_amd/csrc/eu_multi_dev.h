@@ -512,6 +512,61 @@ __device__ __forceinline__ float eu_std_min(float a, float b) { return b < a ? b
 
 #define EU_FEATHER_FLOOR 0x1p-16f
 
+// The edge weight e of a facet at a source coordinate, for eu_synopsis_feather and eu_synopsis_layers alike: the ramp
+// towards the window's borders and - EDGES, for a facet that keeps a distance plane (EU_LOAD_EDGES; eu_hip.h has the
+// definition) - towards the nearest pixel without alpha, a bilinear sample of the plane. The four loads happen under
+// `hit` alone; a lane that misses gets a weight nobody reads. Without EDGES this is the code both loops had.
+template <bool EDGES>
+__device__ __forceinline__ float eu_feather_weight(const eu_feather_dev &w, bool hit, float sx, float sy)
+{
+  float e = 1.0f;
+  if constexpr (!EDGES) {
+    if (w.border) {
+      const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
+      const float d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
+      e = d * w.rcp;
+      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
+      e = e > 1.0f ? 1.0f : e;
+    }
+  } else {
+    const float *dist = w.dist;                 // wave-uniform, like everything in w
+    if (w.border || dist) {
+      float d = 0.0f;
+      if (w.border) {
+        const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
+        d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
+      }
+      if (dist) {
+        float dm = 0.0f;
+        if (hit) {
+          const float flx = floorf(sx), fly = floorf(sy);
+          const float fx = sx - flx, fy = sy - fly;
+          const int ix = (int)flx, iy = (int)fly;
+          const int dw = w.dist_w, dh = w.dist_h;
+          int x0, x1;
+          if (w.cyclic) {
+            x0 = ix % dw; x0 = x0 < 0 ? x0 + dw : x0;
+            x1 = x0 + 1 == dw ? 0 : x0 + 1;
+          } else {
+            x0 = min(max(ix, 0), dw - 1);
+            x1 = min(max(ix + 1, 0), dw - 1);
+          }
+          const int y0 = min(max(iy, 0), dh - 1), y1 = min(max(iy + 1, 0), dh - 1);
+          const float *r0 = dist + (long long)y0 * dw, *r1 = dist + (long long)y1 * dw;
+          const float d00 = r0[x0], d10 = r0[x1], d01 = r1[x0], d11 = r1[x1];
+          const float top = d00 + (d10 - d00) * fx, bot = d01 + (d11 - d01) * fx;
+          dm = (top + (bot - top) * fy) - 0.5f;
+        }
+        d = w.border ? eu_std_min(dm, d) : dm;
+      }
+      e = d * w.rcp;
+      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
+      e = e > 1.0f ? 1.0f : e;
+    }
+  }
+  return e;
+}
+
 // Feathered seams. No counterpart in the reference: the definition is this project's own (DESIGN.md 1,
 // tests/feather_model.py restates it in numpy). Every facet the ray HITS is weighted by its distance to the
 // nearest border of the facet's window, a ramp of the job's width clamped to [2^-16, 1]; a miss contributes nothing
@@ -520,7 +575,8 @@ __device__ __forceinline__ float eu_std_min(float a, float b) { return b < a ? b
 // facet alone covers is that facet's pixel as it is, so where facets do not overlap the frame is eu_synopsis's.
 // Per pixel, nothing per vector, nothing kept per facet: no limit on the facets, no dynamic LDS.
 // Every operation is one of its own (-ffp-contract=off); the facets are walked in job order.
-template <int NCH, int DEG, bool GEN>
+// EDGES: the job has a facet with a distance plane (eu_feather_weight); other jobs run the instantiation without.
+template <int NCH, int DEG, bool GEN, bool EDGES>
 __device__ __forceinline__ void eu_synopsis_feather(const eu_multi_params &p, const eu_pix &px,
                                                     bool tap, float cx, float cy, float *out)
 {
@@ -549,15 +605,7 @@ __device__ __forceinline__ void eu_synopsis_feather(const eu_multi_params &p, co
     if (!__ballot(hit)) continue;               // a wavefront without a hit: no gathers
     float v[NCH];
     eu_env_facet<NCH, DEG>(s, hit, sx, sy, v);
-    const eu_feather_dev &w = p.fth[f];         // f is wave-uniform: scalar loads
-    float e = 1.0f;
-    if (w.border) {
-      const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
-      const float d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
-      e = d * w.rcp;
-      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
-      e = e > 1.0f ? 1.0f : e;
-    }
+    const float e = eu_feather_weight<EDGES>(p.fth[f], hit, sx, sy);        // f is wave-uniform: scalar loads
     if (hit) {
       float q = e;
       if constexpr (!alpha) {
@@ -598,7 +646,7 @@ __device__ __forceinline__ void eu_synopsis_feather(const eu_multi_params &p, co
 // Q_f (0 on a miss) go to planes of the frame's size, p.lay_plane floats apart - facet f's ncol colour planes, then
 // its Q - and behind all facets' the pixel's qsum, amax and count (as a float). Every plane is written for every
 // live pixel, so the scratch needs no clearing. Whole frames only (no twining: the entry points refuse it).
-template <int NCH, int DEG, bool GEN>
+template <int NCH, int DEG, bool GEN, bool EDGES>
 __device__ __forceinline__ void eu_synopsis_layers(const eu_multi_params &p, const eu_pix &px, bool live)
 {
   constexpr bool alpha = NCH == 2 || NCH == 4;
@@ -628,15 +676,7 @@ __device__ __forceinline__ void eu_synopsis_layers(const eu_multi_params &p, con
     }
     float v[NCH];
     eu_env_facet<NCH, DEG>(s, hit, sx, sy, v);
-    const eu_feather_dev &w = p.fth[f];         // f is wave-uniform: scalar loads
-    float e = 1.0f;
-    if (w.border) {
-      const float dx = eu_std_min(sx + 0.5f, w.lim_x - sx), dy = eu_std_min(sy + 0.5f, w.lim_y - sy);
-      const float d = w.border == 1 ? dx : (w.border == 2 ? dy : eu_std_min(dx, dy));
-      e = d * w.rcp;
-      e = e < EU_FEATHER_FLOOR ? EU_FEATHER_FLOOR : e;
-      e = e > 1.0f ? 1.0f : e;
-    }
+    const float e = eu_feather_weight<EDGES>(p.fth[f], hit, sx, sy);        // f is wave-uniform: scalar loads
     float q = 0.0f, col[ncol];
 #pragma unroll
     for (int c = 0; c < ncol; c++) col[c] = 0.0f;
@@ -704,13 +744,19 @@ static int eu_multi_ladder(const eu_multi_params &p, int degree, const L &launch
     case 3: launch.template go<3, M, false, false>(lds); break;                      \
     default: launch.template go<-1, M, false, false>(lds); break;                    \
   }
-  if (p.mode == EU_MODE_LAYERS) {
+  if (eu_mode_layers(p.mode)) {
     // stage A of the multi-band synopsis: the one-job launcher alone has it
     if (!L::layers || !p.fth || !p.lay || p.twine) return -2;
-    if constexpr (L::layers) { EU_LADDER_MODE(EU_MODE_LAYERS) }
+    if constexpr (L::layers) {
+      if (p.mode == EU_MODE_LAYERS) { EU_LADDER_MODE(EU_MODE_LAYERS) }
+      else { EU_LADDER_MODE(EU_MODE_LAYERS_EDGES) }
+    }
   } else if (p.mode == EU_MODE_FEATHER) {
     if (!p.fth) return -2;
     EU_LADDER_MODE(EU_MODE_FEATHER)
+  } else if (p.mode == EU_MODE_FEATHER_EDGES) {
+    if (!p.fth) return -2;
+    EU_LADDER_MODE(EU_MODE_FEATHER_EDGES)
   } else if (p.mode == EU_MODE_HDR) {
     EU_LADDER_MODE(EU_MODE_HDR)
   } else {

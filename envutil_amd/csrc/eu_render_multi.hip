@@ -54,14 +54,14 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
   sl.z = eu_dyn_lds + threadIdx.x;
   sl.sx = sl.z + p.nfct * 256;
   sl.sy = sl.sx + p.nfct * 256;
-  if constexpr (SYN == EU_MODE_LAYERS) {
+  if constexpr (eu_mode_layers(SYN)) {
     // stage A of the multi-band synopsis: the layers go to their planes, no frame is written
-    eu_synopsis_layers<NCH, DEG, GEN>(p, px, live);
+    eu_synopsis_layers<NCH, DEG, GEN, SYN == EU_MODE_LAYERS_EDGES>(p, px, live);
     return;
   }
   float out[NCH];
   if (!p.twine) {
-    if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, GEN>(p, px, false, 0.0f, 0.0f, out);
+    if constexpr (eu_mode_feather(SYN)) eu_synopsis_feather<NCH, DEG, GEN, SYN == EU_MODE_FEATHER_EDGES>(p, px, false, 0.0f, 0.0f, out);
     else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, false, 0.0f, 0.0f, out);
     else if constexpr (BIG) eu_synopsis_big<NCH, DEG, GEN>(p, px, live, false, 0.0f, 0.0f, sl, out);
     else eu_synopsis<NCH, DEG, PLUS, GEN>(p, px, live, false, 0.0f, 0.0f, sl, out);
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_render_multi_kernel(const
     for (int k = 0; k < p.ntaps; k++) {
       const float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
       float help[NCH];
-      if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, GEN>(p, px, true, cx, cy, help);
+      if constexpr (eu_mode_feather(SYN)) eu_synopsis_feather<NCH, DEG, GEN, SYN == EU_MODE_FEATHER_EDGES>(p, px, true, cx, cy, help);
       else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, GEN>(p, px, live, true, cx, cy, help);
       else if constexpr (BIG) eu_synopsis_big<NCH, DEG, GEN>(p, px, live, true, cx, cy, sl, help);
       else eu_synopsis<NCH, DEG, PLUS, GEN>(p, px, live, true, cx, cy, sl, help);

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
   sl.sy = sl.sx + p.nfct * 256;
   float out[NCH];
   if (!p.twine) {
-    if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, false>(p, px, false, 0.0f, 0.0f, out);
+    if constexpr (eu_mode_feather(SYN)) eu_synopsis_feather<NCH, DEG, false, SYN == EU_MODE_FEATHER_EDGES>(p, px, false, 0.0f, 0.0f, out);
     else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, false, 0.0f, 0.0f, out);
     else if constexpr (BIG) eu_synopsis_big<NCH, DEG, false>(p, px, live, false, 0.0f, 0.0f, sl, out);
     else eu_synopsis<NCH, DEG, PLUS, false>(p, px, live, false, 0.0f, 0.0f, sl, out);
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) EU_MULTI_OCC void eu_views_multi_kernel(const 
     for (int k = 0; k < p.ntaps; k++) {
       const float cx = p.taps[3 * k], cy = p.taps[3 * k + 1], cw = p.taps[3 * k + 2];
       float help[NCH];
-      if constexpr (SYN == EU_MODE_FEATHER) eu_synopsis_feather<NCH, DEG, false>(p, px, true, cx, cy, help);
+      if constexpr (eu_mode_feather(SYN)) eu_synopsis_feather<NCH, DEG, false, SYN == EU_MODE_FEATHER_EDGES>(p, px, true, cx, cy, help);
       else if constexpr (SYN == EU_MODE_HDR) eu_synopsis_hdr<NCH, DEG, false>(p, px, live, true, cx, cy, help);
       else if constexpr (BIG) eu_synopsis_big<NCH, DEG, false>(p, px, live, true, cx, cy, sl, help);
       else eu_synopsis<NCH, DEG, PLUS, false>(p, px, live, true, cx, cy, sl, help);

@@ -114,6 +114,9 @@ struct facet_spec : public facet_base
   // The asset is resident and its picture has changed - the next frame of a sequence: payload() refills the resident
   // container in place from the feed above (eu_hip_source_reload) where it would otherwise use it as it is
   bool refill = false;
+  // --feather_edges: the source keeps the distance plane of its alpha channel (eu_hip_source_load_pixels with
+  // EU_LOAD_EDGES) and the feathered synopses weight it towards mask, crop and alpha edges too; a refill follows
+  bool edges = false;
 };
 
 struct arguments : public facet_base
@@ -131,6 +134,8 @@ struct arguments : public facet_base
   // --synopsis feather: the width of the blending ramp in source pixels, 0: half the shorter side of each facet's
   // window (eu_target::feather)
   double feather = 0.0;
+  // --feather_edges, with either of the two: facets with an alpha channel are loaded with facet_spec::edges
+  bool feather_edges = false;
   // --synopsis multiband: the pyramid levels above level 0, 0: what the frame allows, 8 at the most (eu_target::bands)
   int bands = 0;
   int solo = -1, single = -1, mask_for = -1;
@@ -343,26 +348,26 @@ struct hip_dispatch : public dispatch_base
           sm.pixel_channels = fct.pixel_channels ? fct.pixel_channels : fct.nchannels;
           sm.colour_table = fct.colour_table; sm.alpha_table = fct.alpha_table;
           feed.kind = EU_PX_SAMPLES; feed.samples = &sm;
-          if (!refill)
+          if (!refill && !fct.edges)
             rc = eu_hip_source_load_samples(&e, &sm, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
                                             args.support_min, args.tile_size, &s);
         } else if (fct.rgbe && !fct.pixels) {
           // Radiance quads: uploaded as they are, decoded on the device, through the same edit
           px.data = fct.rgbe; px.colour_table = fct.rgbe_table;
           feed.kind = EU_PX_RGBE; feed.rgbe = &px;
-          if (!refill)
+          if (!refill && !fct.edges)
             rc = eu_hip_source_load_rgbe(&e, &px, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
                                          args.support_min, args.tile_size, &s);
         } else if (fct.ycbcr && !fct.pixels) {
           // the planes of a video frame: uploaded as their rows lie, decoded on the device, through the same edit
           feed.kind = EU_PX_YCBCR; feed.ycbcr = fct.ycbcr;
-          if (!refill)
+          if (!refill && !fct.edges)
             rc = eu_hip_source_load_ycbcr(&e, fct.ycbcr, edit ? &ed : nullptr, args.spline_degree, args.prefilter_degree,
                                           args.support_min, args.tile_size, &s);
         } else {
           feed.kind = EU_PX_FLOATS; feed.floats = fct.pixels;
           feed.pixel_channels = edit ? ed.pixel_channels : fct.nchannels;
-          if (refill) {}
+          if (refill || fct.edges) {}
           else if (edit)
             rc = eu_hip_source_load_edited(&e, fct.pixels, &ed, args.spline_degree, args.prefilter_degree,
                                            args.support_min, args.tile_size, &s);
@@ -370,6 +375,10 @@ struct hip_dispatch : public dispatch_base
             rc = eu_hip_source_load(&e, fct.pixels, args.spline_degree, args.prefilter_degree,
                                     args.support_min, args.tile_size, &s);
         }
+        // a facet that keeps its distance plane: the one load for every feed, through the same eu_pixels
+        if (!refill && fct.edges)
+          rc = eu_hip_source_load_pixels(&e, &feed, args.spline_degree, args.prefilter_degree, args.support_min, args.tile_size,
+                                         EU_LOAD_EDGES, &s);
         if (refill) {
           // the next frame of a sequence: the resident container refilled in place, then the facet as ever
           rc = eu_hip_source_reload(it->second, &feed, args.prefilter_degree, nullptr);

@@ -147,7 +147,8 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     { "--twine_threshold", 1 }, { "--twine_max", 1 }, { "--photo", 1 }, { "--facet", 6 }, { "--oiio", 1 },
     { "--input_colour_space", 1 }, { "--pto", 1 }, { "--pto_line", 1 }, { "--solo", 1 }, { "--mask_for", 1 },
     { "--nchannels", 1 }, { "--ray_map", 1 }, { "--layer", 2 }, { "--frames", 2 }, { "--ycbcr_matrix", 1 },
-    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 }, { "--feather", 1 }, { "--bands", 1 } };
+    { "--ycbcr_range", 1 }, { "--y4m_format", 1 }, { "--y4m_depth", 1 }, { "--fps", 1 }, { "--feather", 1 }, { "--bands", 1 },
+    { "--feather_edges", 0 } };
   std::map<std::string, std::string> opt;
   std::vector<std::vector<std::string>> facets, layers;
   std::vector<std::string> photos, addenda;
@@ -224,6 +225,13 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
       return false;
     }
     if (a.synopsis != "feather" && a.synopsis != "multiband") { err = "--feather goes with --synopsis feather"; return false; }
+  }
+  // --feather_edges: the ramp of the two blending synopses also falls towards mask, crop and alpha edges - every facet
+  // that ends up with an alpha channel keeps a distance plane (eu_hip.h: EU_LOAD_EDGES; facet_spec::edges below)
+  a.feather_edges = has("--feather_edges");
+  if (a.feather_edges && a.synopsis != "feather" && a.synopsis != "multiband") {
+    err = "--feather_edges goes with --synopsis feather or multiband: the other synopses have no ramp to take to the alpha edges";
+    return false;
   }
   if (a.prefilter_degree < 0) a.prefilter_degree = a.spline_degree;
   a.projection = projection_t(projection_index(a.projection_str));
@@ -540,6 +548,10 @@ inline bool init_arguments(int argc, const char *const *argv, const image_probe 
     if (m.nchannels == 2 || m.nchannels == 4) alpha_seen = true;
     if (m.nchannels > a.nchannels) a.nchannels = m.nchannels;
     m.masked = a.mask_for == -1 ? -1 : (m.facet_no == a.mask_for ? 1 : 0);
+    // --feather_edges: the facets that end up with an alpha channel - their own, or gained from a mask or a crop - and
+    // have a window to measure in (no cubemaps); a resident asset with a plane is another asset than one without
+    m.edges = a.feather_edges && (m.nchannels == 2 || m.nchannels == 4) && m.projection != CUBEMAP && m.projection != BIATAN6;
+    if (m.edges) m.asset_key += " +edges";
   }
   if (alpha_seen && a.nchannels == 3) a.nchannels = 4;
   const int nch = in("--nchannels", 0);

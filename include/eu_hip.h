@@ -486,6 +486,55 @@ int  eu_hip_source_reload(eu_source *src, const eu_pixels *px, int prefilter_deg
 /* waits for every reload so far and frees the scratch they share ("A source refilled in place") */
 int  eu_hip_reload_scratch_release(void);
 
+/* ---- feathering to alpha edges: a distance plane per source ------------------------------------------------
+ * eu_hip_source_load_pixels is the load eu_hip_source_reload is the second half of: one call for every feed, through
+ * eu_pixels. flags == 0 builds, bit for bit, what the matching eu_hip_source_load* call builds (EU_PX_FLOATS:
+ * eu_hip_source_load_edited with px->edit, px->pixel_channels and px->on_device in the edit's place) and refuses what
+ * that call refuses. EU_LOAD_EDGES also keeps the distance plane D of the facet's window, 4 bytes per window pixel
+ * (a quarter on top of an RGBA container's core), which the feathered synopses (EU_SYN_FEATHER, EU_SYN_MULTIBAND)
+ * then take into the blend weight: the ramp falls towards mask, crop and alpha edges too, not only towards the window.
+ * The definition, for a source of 2 or 4 channels that is no cubemap, window w x h, both at most 32768:
+ *   Outside set  O = { (u, v) : not (alpha(u, v) > 0) }, alpha the last channel of the plane the prefilter reads -
+ *                behind the decode, a gained channel, the edit and its binomial. An IEEE compare: NaN, negative values
+ *                and both zeros are outside, a positive denormal is inside.
+ *   Row distance g(x, y) = the smallest |x - u| over (u, y) in O; where the load chose the periodic boundary condition
+ *                for axis 0 (a 360-degree spherical or cylindrical source) the smallest min(|x - u|, w - |x - u|).
+ *                A row without an outside pixel has none.
+ *   D2(x, y)     = the smallest g(x, v)^2 + (y - v)^2 over the rows v that have a g(x, v), an exact int32
+ *                (2 * 32767^2 < 2^31); 2^31 - 1 if no row has one. Rows never wrap: the distance does not cross
+ *                the pole of a full sphere.
+ *   D(x, y)      = sqrt(float(D2)): int32 to float32 rounded to nearest, then a correctly rounded float32 root.
+ *   Sampling, per facet the ray hits, float32, every operation rounded on its own, no contraction:
+ *                ix = floor(sx), fx = sx - float(ix), iy and fy likewise; ix and ix + 1 wrap modulo w where the rows
+ *                are periodic and clamp to [0, w - 1] otherwise, iy and iy + 1 clamp;
+ *                top = D00 + (D10 - D00) * fx, bot = D01 + (D11 - D01) * fx, dm = (top + (bot - top) * fy) - 0.5f
+ *                (D10: column ix + 1, row iy). The - 0.5 measures to the outside pixel's edge, as the window ramp
+ *                measures to the border at -0.5.
+ *   Weight       d = the smaller of dm and the window ramp's d (eu_target::feather), dm alone where no axis has a
+ *                border; e = clamp(d * float(1.0 / width), 2^-16, 1). Everything behind e is eu_target::feather's and
+ *                eu_target::bands' definition, unchanged - a pixel ONE facet hits is still that facet's pixel as it is.
+ * A facet without a plane is weighted as before, also beside facets that have one; jobs in which no facet has a plane
+ * run the kernels they ran before. Out of scope: cubemap sources, per-facet widths, a metric in ray space.
+ * Refused with EU_ERR_ARGUMENT before a device is looked for: an unknown flag bit; EU_LOAD_EDGES on a cubemap, on a
+ * facet whose nchannels is not 2 or 4, on a window side above 32768.
+ * eu_hip_source_reload of a source with a plane refills the plane too, in the same stream order, at the same device
+ * address; eu_hip_source_release frees it; the copies eu_hip_render_devices makes carry it. eu_hip_source_adopt and
+ * eu_hip_source_alloc make sources without a plane. */
+enum { EU_LOAD_EDGES = 1 };
+int  eu_hip_source_load_pixels(const eu_facet *fct, const eu_pixels *px, int spline_degree, int prefilter_degree,
+                               int support_min, int tile_size, unsigned flags, eu_source **out);
+/* D of a source loaded with EU_LOAD_EDGES: window_height rows of window_width floats into `out`, rows
+ * row_stride_bytes apart (a multiple of 4, at least a row); out_on_device != 0: `out` is device memory and the copy is
+ * queued on `stream` (NULL: the library's own) behind the load or reload that wrote the plane; else the call returns
+ * when `out` is complete. EU_ERR_ARGUMENT for a source without a plane. */
+int  eu_hip_source_edge_distance(const eu_source *src, float *out, size_t row_stride_bytes, int out_on_device,
+                                 void *stream);
+/* 1: the source keeps a distance plane, 0: it does not (also for a null handle) */
+int  eu_hip_source_has_edges(const eu_source *src);
+/* the plane where it lies on the device, as eu_hip_source_device_ptr gives the container: window_width x
+ * window_height floats, dense; it stays there for the source's life, reloads included. NULL without a plane. */
+int  eu_hip_source_edge_device_ptr(const eu_source *src, void **dev_ptr);
+
 /* ---- the hot path --------------------------------------------------------- */
 /* zimt::process(shape, stepper, environment|twine_t, storer): renders rows
  * [row_begin,row_end) of the target into `out` (row stride in bytes).

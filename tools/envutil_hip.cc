@@ -425,6 +425,9 @@ static int core(int argc, const char *const *argv, bool pipe_mode = false)
     }
     kind = as_ycbcr ? KIND_YCBCR : as_samples ? (sbits == 8 ? KIND_SAMPLES_8 : KIND_SAMPLES_16) : as_rgbe ? KIND_RGBE : KIND_FLOATS;
     if (args.verbose) std::printf("%s: %s\n", file.c_str(), kind_name[kind]);
+    if (args.verbose && f.edges)
+      std::printf("%s: a distance plane of its alpha channel is built on the device (--feather_edges), %d x %d\n", file.c_str(),
+                  f.window_width, f.window_height);
     // read_image_data: from the facet's colour space - Csp clause / --input_colour_space, else what the file's
     // format says - to the working one (envutil_basic.h:950-977). A video frame stays in its own non-linear space,
     // as its tables leave it
@@ -568,6 +571,8 @@ int main(int argc, const char **argv)
         "            projections: spherical cylindrical rectilinear stereographic fisheye cubemap biatan6\n"
         "            --solo N  --single N  --split FORMAT(%d)  --mask_for N  --synopsis panorama|hdr_merge|feather|multiband\n"
         "            --feather WIDTH  with --synopsis feather or multiband: the blending ramp in source pixels (0: half the shorter side)\n"
+        "            --feather_edges  with either: the ramp also falls towards mask, crop and alpha edges (a distance plane\n"
+        "            per facet with alpha, 4 bytes per pixel)\n"
         "            --bands N  with --synopsis multiband: pyramid levels above level 0 (0: what the frame allows, 8 at the most);\n"
         "                       a multiband job of several facets is not twined: no automatic twining, --twine above 1 is refused\n"
         "  rays:     --ray_map FILE.pfm  the single facet's image at the rays x y z of a 3-channel PFM, in the facet's\n"
